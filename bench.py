@@ -3,11 +3,19 @@
 
 Headline workload = the point BASELINE.json's north_star quotes the metric on: 512 concurrent self-play games per
 GPU, 100 MCTS simulations per move, THREADS_PER_MCTS 2 (the reference's default, src/settings.h:44), random-init
-20-block / 256-filter net, bf16 MFMA contractions with fp32 accumulation.  At N = 1 the other two single-GPU
-configurations of BASELINE.json (configs[1] 256 x 100 and configs[2] 2048 x 400) run in the same invocation and are
+20-block / 256-filter net, bf16 MFMA contractions with fp32 accumulation.  A plain run measures that headline and nothing
+else: set-up, warm-up, the timed steps, the result line (its roofline and tree-step figures come from the same timed region).
+
+--full adds everything else (--no-extra, --no-cpu-baseline and --no-full-games drop parts of it again): at N = 1 the other two
+single-GPU configurations of BASELINE.json (configs[1] 256 x 100 and configs[2] 2048 x 400) run in the same invocation and are
 reported under "extra_configs", each with its own roofline (+ the headline point on NET_F32X and NET_F16); "midgame_leg" = the headline
 entered in the middle of games; "config0_play" = BASELINE configs[0] through the host CLI; "optimiser_step" and "arena_100" = the other
-two legs of a learn iteration at their stated shapes (batch 512; 100 mirrored games).
+two legs of a learn iteration at their stated shapes (batch 512; 100 mirrored games); "cpu_baseline" = the oracle on the host cores;
+and, at any N, the untimed tail below.
+
+--dump-outputs DIR writes what the headline's self-play held after its last timed step, read back through the C-ABI as a caller
+would (states, RNG streams, status, root statistics, counters of the timed region, and finished records once a game has finished),
+as float32 / float64 .npy files, none of them empty; the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 
 One "step" = one MOVE's worth of the hot path for every game of the batch: S/T + 1 passes, a pass being one tree step
 (expand + backup of the previous leaves, PUCT descents to the next leaves — and, when a search completes, the move,
@@ -18,10 +26,11 @@ in the timed region except the final counters.
 Multi-GPU (weak scaling): one process per GPU, games sharded with disjoint seed streams, NO data-path collective.
 `python bench.py --gpus N` starts the N ranks itself (before anything touches torch or HIP); under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is one of them.  The path's one exchange — the
-all_gather of finished (s, pi, z) records, alphazero_trainer.cpp:59-62 — is measured on real records after an untimed
+all_gather of finished (s, pi, z) records, alphazero_trainer.cpp:59-62 — is measured (--full) on real records after an untimed
 tail that plays games to their end, and reported under "exchange" (records, bytes, gather_ms).
 
     python bench.py [--gpus N --steps K --warmup W] [--games 512 --sims 100 --threads 2 --blocks 20 --dtype bf16]
+                    [--full] [--dump-outputs DIR]
 """
 import argparse
 import ctypes as C
@@ -246,7 +255,44 @@ def arena_leg(pkg, blocks, games=100, slots=128, sims=100, threads=2):
                     "passes queued without a read-back; k_tower_sc while both nets' launches fit the CUs, one board per workgroup otherwise"}
 
 
-def run_config(ctx, games, sims, threads, steps, warmup, tail, dtype=None, midgame=False):
+COUNTER_KEYS = ["simulations", "evaluations", "levels", "decisions", "games_finished", "samples", "errors", "nodes_dropped",
+                "records_dropped"]
+DUMP_RECORDS_MAX = 32768   # x 265 values x 4 B = 35 MB of records
+DUMP_GAMES_MAX = 16384     # x 292 values x 4 B = 19 MB of per-game arrays: the dump stays under 64 MB at any size
+
+
+def dump_outputs(eng, shard, dev, out_dir, prefix, delta):
+    """--dump-outputs: the engine's self-play after the last timed step, read back as a caller of the C-ABI would, one .npy per array.
+    Finished records come out of the ring in the order in which their games finished inside a pass (an atomic slot counter), so they
+    are sorted by their bytes; above DUMP_RECORDS_MAX records / DUMP_GAMES_MAX games a fixed-seed sample of them is kept.  A record
+    exists only once its game has finished: while none has (the headline's 20 steps end in the opening), no record_* file is written,
+    so that every file holds data.  Their number is a function of the arguments, so two builds write the same set of files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n, q, p = eng.root_stats()
+    games = np.arange(len(n))
+    if len(games) > DUMP_GAMES_MAX:
+        games = np.sort(np.random.default_rng(20260004).choice(len(games), DUMP_GAMES_MAX, replace=False))
+    rec = shard.device_records_to_torch(eng, dev).cpu().numpy()   # copies, the records stay buffered
+    rec = rec[np.lexsort(rec.T[::-1])]
+    if len(rec) > DUMP_RECORDS_MAX:
+        rec = rec[np.sort(np.random.default_rng(20260003).choice(len(rec), DUMP_RECORDS_MAX, replace=False))]
+    rec = np.ascontiguousarray(rec)
+    arrays = {
+        "states": eng.get_states()[games].astype(np.float32),         # [G][160] state images (azr_engine_get_states)
+        "rng": eng.get_rng()[games].astype(np.float64),               # [G] each game's minstd_rand0 state
+        "status": eng.status()[games].astype(np.float32),             # [G] game status
+        "root_visits": n[games].astype(np.float32), "root_q": q[games], "root_prior": p[games],   # [G][43] each game's current root
+        "counters": np.array([delta[k] for k in COUNTER_KEYS], np.float64),   # COUNTER_KEYS over the timed steps
+    }
+    if len(rec):   # rec265 = i8 player | in88 | f32 z | f32 pi[43]
+        arrays.update(record_player=rec[:, 0].astype(np.int8).astype(np.float32), record_input=rec[:, 1:89].astype(np.float32),
+                      record_z=rec[:, 89:93].copy().view(np.float32).reshape(-1), record_pi=rec[:, 93:].copy().view(np.float32))
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), x)
+
+
+def run_config(ctx, games, sims, threads, steps, warmup, tail, dtype=None, midgame=False, dump=None):
     """K steps of one configuration on this rank's GPU; returns the per-rank measurements (reduced by the caller)"""
     a, pkg, shard, torch, dist = ctx["a"], ctx["pkg"], ctx["shard"], ctx["torch"], ctx["dist"]
     dtype = dtype or a.dtype
@@ -307,8 +353,9 @@ def run_config(ctx, games, sims, threads, steps, warmup, tail, dtype=None, midga
     prof = {"net_ms": sum(p_["net_ms"] * p_["launches"] for p_ in profs) / nl,
             "tree_ms": sum(p_["tree_ms"] * p_["launches"] for p_ in profs) / nl, "launches": sum(p_["launches"] for p_ in profs)}
     delta = {k: c1[k] - c0[k] for k in c1}
-    keys = ["simulations", "evaluations", "levels", "decisions", "games_finished", "samples", "errors", "nodes_dropped",
-            "records_dropped"]
+    if dump:
+        dump_outputs(eng, shard, dev, dump, f"rank{rank}_" if world > 1 else "", delta)
+    keys = COUNTER_KEYS
     tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
     tot = torch.tensor([delta[k] for k in keys], dtype=torch.int64, device=cdev)
     if use_dist:
@@ -428,10 +475,16 @@ def main():
     ap.add_argument("--blocks", type=int, default=20)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32", "f32x"],
                     help="bf16 (the benchmarked tower) | f16 (the same kernels on fp16 operands) | f32x (fp32-equivalent fp16-pair MFMA tower) | f32 (fp32 VALU kernels)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip BASELINE configs[1] / configs[2] (N = 1 runs them by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: extra configurations and legs, CPU baseline, untimed tail with the "
+                         "record exchange (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the headline's self-play outputs as float32 / float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip BASELINE configs[1] / configs[2] and the other legs "
+                                                            "(N = 1 runs them by default)")
     ap.add_argument("--no-full-games", action="store_true",
-                    help="skip the untimed tail (whole self-play games/s, and the record exchange on real records)")
+                    help="with --full: skip the untimed tail (whole self-play games/s, and the record exchange on real records)")
     ap.add_argument("--tail-seconds", type=float, default=75.0)
     a = ap.parse_args()
     if a.gpus < 1 or a.steps < 1 or a.warmup < 0:
@@ -480,9 +533,9 @@ def main():
     shard = importlib.import_module("alphazero-risk_amd.shard")
     ctx = dict(a=a, pkg=pkg, shard=shard, torch=torch, dist=dist, rank=rank, world=world, local=local, dev=dev, cdev=cdev,
                backend=backend, use_dist=use_dist)
-    head = run_config(ctx, a.games, a.sims, a.threads, a.steps, a.warmup, tail=not a.no_full_games)
+    head = run_config(ctx, a.games, a.sims, a.threads, a.steps, a.warmup, tail=a.full and not a.no_full_games, dump=a.dump_outputs)
     extras, mid = [], None
-    if world == 1 and not a.no_extra:
+    if world == 1 and a.full and not a.no_extra:
         for g, s, t in EXTRA_CONFIGS:
             if (g, s, t) == (a.games, a.sims, a.threads):
                 continue
@@ -515,9 +568,9 @@ def main():
         if mid is not None:
             out["midgame_leg"] = mid
             out["midgame_leg"]["vs_headline"] = mid["value"] / out["value"]
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.blocks, a.sims, a.threads)
-        if world == 1 and not a.no_extra:
+        if world == 1 and a.full and not a.no_extra:
             out["config0_play"] = config0_play(a.blocks)
             # the two other legs of the reference's learn iteration, each at its stated shape, ~12 s together
             out["optimiser_step"] = optimiser_step_leg(pkg, a.blocks)

@@ -36,7 +36,7 @@ def _env(**kw):
 def test_bench_record_exchange_over_rccl_with_one_rank():
     """bench.py's exchange leg on real finished records: counts + padded all_gather of DEVICE tensors over backend nccl"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--games", "32", "--sims", "8", "--blocks", "1", "--steps", "2",
-           "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--tail-seconds", "30"]
+           "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--tail-seconds", "30"]
     r = subprocess.run(cmd, env=_env(AZR_FORCE_DIST="1"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -158,7 +158,7 @@ def test_bench_five_ranks_over_gloo():
     """`python bench.py --gpus 5` (its own spawner: a parent that never touches HIP starts the ranks) with the gloo rehearsal backend:
     5 disjoint seed streams, weak-scaling totals, the padded record gather of 5 ragged counts"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "5", "--games", "16", "--sims", "8", "--blocks", "1", "--steps", "2",
-           "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--tail-seconds", "40"]
+           "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--tail-seconds", "40"]
     r = subprocess.run(cmd, env=_env(AZR_BENCH_BACKEND="gloo", AZR_BENCH_DEADLINE_S="600"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:] + r.stdout[-1000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
