@@ -82,7 +82,7 @@ EXPORTS = [
     "azr_mcts_apply", "azr_mcts_root_stats", "azr_mcts_policy", "azr_mcts_pick", "azr_selfplay_start", "azr_selfplay_start_games", "azr_selfplay_start_from_states",
     "azr_selfplay_run", "azr_selfplay_counters", "azr_samples_drain", "azr_samples_device_view", "azr_samples_copy_device", "azr_profile_last_run",
     "azr_device_synchronize", "azr_debug_tower_clock", "azr_debug_tower_trace", "azr_debug_tower_plan", "azr_arena_start", "azr_arena_run", "azr_arena_results", "azr_arena_log",
-    "azr_arena_set_opponent_net", "azr_arena_collect_samples",
+    "azr_arena_set_opponent_net", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
 ]
 
 
@@ -144,6 +144,7 @@ def load_library(test_hooks=False):
         L.azr_arena_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.azr_arena_set_opponent_net.argtypes = [C.c_void_p, C.c_void_p]
         L.azr_arena_collect_samples.argtypes = [C.c_void_p, C.c_int]
+        L.azr_arena_collect_scripted_samples.argtypes = [C.c_void_p, C.c_int]
         L.azr_arena_results.argtypes = [C.c_void_p, C.c_void_p]
         L.azr_arena_log.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[test_hooks] = L
@@ -456,6 +457,11 @@ class Engine:
 
     def arena_collect_samples(self, on=True):
         self._chk(self.L.azr_arena_collect_samples(self.h, int(on)))
+
+    def arena_collect_scripted_samples(self, on=True):
+        """ScriptPlayer / RandomPlayer record one-hot (s, move) samples (include/azr.h); set before arena_start, and drain
+        after every arena_run: a run may return unfinished while slots wait for ring room"""
+        self._chk(self.L.azr_arena_collect_scripted_samples(self.h, int(on)))
 
     def arena_run(self, passes):
         fin = C.c_int(0)

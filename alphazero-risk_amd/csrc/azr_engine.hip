@@ -599,9 +599,31 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 // the reference: games in mirrored pairs with alternating starts, AlphaZeroPlayer::takeTurn (alphazero_player.cpp:3-21)
 // through the search above, ScriptPlayer / RandomPlayer as wave-resident code (azr_players.hpp).
 // ================================================================================================
-__global__ __launch_bounds__(64) void k_arena_step(Dev E)
+// ring room for scripted collection (azr_arena_collect_scripted_samples): ring_count[1] = records flushed and not yet drained +
+// SCAP per game in progress.  A game is dealt only once its SCAP records are claimed, so a flush always lands inside the ring.
+__device__ __forceinline__ bool ring_reserve(const Dev& E)
 {
-    __shared__ int8_t scratch[128];
+    uint32_t ok = 0;
+    if (lane_id() == 0) {
+        unsigned long long* claim = E.ring_count + 1;
+        unsigned long long cur = atomicAdd(claim, 0ULL);
+        while (cur + (unsigned long long)E.SCAP <= E.ring_cap) {
+            const unsigned long long prev = atomicCAS(claim, cur, cur + (unsigned long long)E.SCAP);
+            if (prev == cur) { ok = 1; break; }
+            cur = prev;
+        }
+    }
+    return rfl(ok) != 0;
+}
+__device__ __forceinline__ void ring_release(const Dev& E, uint32_t n)
+{
+    if (lane_id() == 0 && n) atomicAdd(E.ring_count + 1, (unsigned long long)(-(long long)n));
+}
+
+// SREC: ScriptPlayer / RandomPlayer record their moves (StageRec); without it they get NoRec and this is the arena as it was
+template <bool SREC>
+__device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
+{
     const int g = blockIdx.x;
     if (E.lc_zero >= 0 && g == 0 && threadIdx.x < 2) E.leaf_count[E.lc_zero + threadIdx.x] = 0;   // the next pass's counts (the last readers are done)
     Ctl c;
@@ -644,6 +666,7 @@ __global__ __launch_bounds__(64) void k_arena_step(Dev E)
             const long long pr = (long long)lane + (long long)c.slot_games * L;   // pairs are assigned statically
             const bool capped = E.arena_slot_cap > 0 && (int)c.slot_games >= E.arena_slot_cap;
             if (capped || g >= 2 * L || pr >= (long long)(E.arena_total / 2)) { c.arena_state = 2; break; }
+            if (SREC && !ring_reserve(E)) break;   // no ring room for this game: wait for the next drain, the pair stays this slot's
             const uint32_t pseed = E.base_seed + (uint32_t)pr;
             root.rng = rng_seed(pseed);
             new_game(root);
@@ -661,12 +684,20 @@ __global__ __launch_bounds__(64) void k_arena_step(Dev E)
             c.arena_state = 1;
         }
         if (c.arena_state == 0) {  // Game::newGame (game.cpp:170-191) for the next Game::playGames(1)
+            if (SREC) {   // ring room first: a slot that has to wait takes nothing from the quota
+                const bool capped = c.pair_phase == 0 && E.arena_slot_cap > 0 && (int)c.slot_games >= E.arena_slot_cap;
+                if (!capped && !ring_reserve(E)) break;
+            }
             if (c.pair_phase == 0) {  // Counter::hasNext(2) (game.cpp:14-26)
                 int taken = 0;
                 const bool capped = E.arena_slot_cap > 0 && (int)c.slot_games >= E.arena_slot_cap;
                 if (!capped && lane_id() == 0) taken = atomicAdd(E.arena_taken, 2);
                 taken = (int)rfl((uint32_t)taken);
-                if (capped || taken + 2 > E.arena_total) { c.arena_state = 2; break; }
+                if (capped || taken + 2 > E.arena_total) {
+                    if (SREC && !capped) ring_release(E, (uint32_t)E.SCAP);
+                    c.arena_state = 2;
+                    break;
+                }
             }
             if (E.arena_mirror && c.player_start != 0) {
                 uint32_t keep = root.rng;
@@ -701,7 +732,8 @@ __global__ __launch_bounds__(64) void k_arena_step(Dev E)
                 }
             }
             if (c.slot_games < (uint32_t)ALOG) ws_store(root, E.alog_final + ((size_t)g * ALOG + c.slot_games) * GREC);
-            if (E.arena_collect && c.nsamples) {  // Player::gameFinished -> NNTrainDataStorage::updateValues for both players
+            if (SREC) ring_release(E, (uint32_t)E.SCAP - c.nsamples);   // the game's n records stay claimed until they are drained
+            if ((SREC || E.arena_collect) && c.nsamples) {  // Player::gameFinished -> NNTrainDataStorage::updateValues for both players
                 wave_mem_sync();
                 flush_samples(E, g, c.nsamples, gs, k.ringdrop);
                 k.samples += c.nsamples;
@@ -718,10 +750,16 @@ __global__ __launch_bounds__(64) void k_arena_step(Dev E)
         const int kind = p == 0 ? E.kind0 : E.kind1;
         bool fail = false;
         if (kind == 1) {
-            if (p == 0) script_take_turn(sp[0], root, R); else script_take_turn(sp[1], root, R);
+            if (SREC) {
+                const StageRec rec{E.stage + (size_t)g * E.SCAP * STAGE_BYTES, (uint32_t)E.SCAP, c.nsamples, k.ringdrop};
+                if (p == 0) script_take_turn(sp[0], root, R, rec); else script_take_turn(sp[1], root, R, rec);
+            } else {
+                if (p == 0) script_take_turn(sp[0], root, R, NoRec{}); else script_take_turn(sp[1], root, R, NoRec{});
+            }
             fail = root.err != 0 || (root.cur == p && game_status(root, R) == ST_NOT_ENDED);  // "Turn was not incremented"
         } else if (kind == 2) {
-            random_take_turn(root, R);
+            if (SREC) random_take_turn(root, R, StageRec{E.stage + (size_t)g * E.SCAP * STAGE_BYTES, (uint32_t)E.SCAP, c.nsamples, k.ringdrop});
+            else random_take_turn(root, R, NoRec{});
             fail = root.err != 0 || (root.cur == p && game_status(root, R) == ST_NOT_ENDED);
         } else {
             const uint32_t w = kind == 3 ? 1u : 0u;   // which AlphaZeroPlayer: its tree and its network
@@ -772,6 +810,7 @@ __global__ __launch_bounds__(64) void k_arena_step(Dev E)
             c.player_start = 0; c.pair_phase = 0; c.arena_state = 0;
             c.pending = 0; c.search_active = 0; c.turn_started = 0;
             if (E.arena_mirror == AZR_MIRROR_CONCURRENT) c.slot_games++;   // statically assigned: go on with the slot's next pair
+            if (SREC) { ring_release(E, (uint32_t)E.SCAP); c.nsamples = 0; }   // the game's staged records go with it
         }
     }
     if (two && lane_id() == 0) { uint32_t* d2 = E.tctl2 + (size_t)g * 4; d2[0] = x2.search_id; d2[1] = x2.nfree; d2[2] = x2.hiwater; }
@@ -794,6 +833,17 @@ __global__ __launch_bounds__(64) void k_arena_step(Dev E)
     }
     ctl_store(c, &E.ctl[g]);
     flush_counters(E, g, c, k, false, cnt0);
+}
+
+__global__ __launch_bounds__(64) void k_arena_step(Dev E)
+{
+    __shared__ int8_t scratch[128];
+    arena_step<false>(E, scratch);
+}
+__global__ __launch_bounds__(64) void k_arena_step_rec(Dev E)
+{
+    __shared__ int8_t scratch[128];
+    arena_step<true>(E, scratch);
 }
 
 __global__ __launch_bounds__(64) void k_arena_start(Dev E)
@@ -1016,7 +1066,7 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     HIPCHK(h, dmalloc(&d.stage, G * d.SCAP * STAGE_BYTES));
     d.ring_cap = (unsigned long long)G * d.SCAP;
     HIPCHK(h, dmalloc(&d.ring, (size_t)d.ring_cap * AZR_RECORD_BYTES));
-    HIPCHK(h, dmalloc(&d.ring_count, 1));
+    HIPCHK(h, dmalloc(&d.ring_count, 2));   // [0] records in the ring, [1] ring room claimed by scripted collection (ring_reserve)
     HIPCHK(h, dmalloc(&d.counters, G));   // one row per game
     HIPCHK(h, dmalloc(&d.active, 1));
     HIPCHK(h, dmalloc(&d.arena_taken, 1));
@@ -1037,7 +1087,7 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     HIPCHK(h, hipMemsetAsync(d.leaf_in, 0, GT * LEAF_STRIDE, h->stream));
     HIPCHK(h, hipMemsetAsync(d.net_pi, 0, GT * PI_STRIDE * sizeof(float), h->stream));
     HIPCHK(h, hipMemsetAsync(d.net_v, 0, GT * sizeof(float), h->stream));
-    HIPCHK(h, hipMemsetAsync(d.ring_count, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.ring_count, 0, 2 * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(d.counters, 0, (size_t)d.G * sizeof(Counters), h->stream));
     HIPCHK(h, hipMemsetAsync(d.active, 0, sizeof(uint32_t), h->stream));
     int rc = net_alloc(h);
@@ -1111,6 +1161,12 @@ struct DevBuf {
     do {                                                                              \
         hipLaunchKernelGGL(kern, dim3((h)->d.G), dim3(64), 0, (h)->stream, __VA_ARGS__); \
         HIPCHK(h, hipGetLastError());                                                 \
+    } while (0)
+// the arena step of this handle: with the scripted players' recorder (azr_arena_collect_scripted_samples) or without
+#define ARENA_STEP(h, dev)                                                       \
+    do {                                                                         \
+        if ((h)->arena_rec) LAUNCH(h, k_arena_step_rec, dev);                    \
+        else LAUNCH(h, k_arena_step, dev);                                       \
     } while (0)
 #define ENTER(h)                                 \
     if (!(h)) return AZR_E_BAD_HANDLE;           \
@@ -1522,6 +1578,13 @@ extern "C" int azr_samples_drain(azr_engine* h, void* rec265, size_t cap, size_t
         SYNC(h);
     }
     HIPCHK(h, hipMemcpyAsync(h->d.ring_count, &left, 8, hipMemcpyHostToDevice, h->stream));
+    if (h->arena_rec) {   // the drained records give their ring room back (no kernel runs: the stream is synchronised)
+        unsigned long long claim = 0;
+        D2H(h, &claim, h->d.ring_count + 1, 8);
+        SYNC(h);
+        claim = claim > take ? claim - take : 0;
+        HIPCHK(h, hipMemcpyAsync(h->d.ring_count + 1, &claim, 8, hipMemcpyHostToDevice, h->stream));
+    }
     SYNC(h);
     if (n_out) *n_out = take;
     return AZR_OK;
@@ -1583,7 +1646,8 @@ extern "C" int azr_arena_start(azr_engine* h, int player1, int player2, int game
     }
     Dev& d = h->d;
     d.nodes2 = usesB ? h->tree2[0] ? (uint8_t*)h->tree2[0] : nullptr : nullptr;
-    if (d.arena_collect) HIPCHK(h, hipMemsetAsync(d.ring_count, 0, sizeof(unsigned long long), h->stream));
+    h->arena_rec = h->arena_script;
+    if (d.arena_collect || h->arena_rec) HIPCHK(h, hipMemsetAsync(d.ring_count, 0, 2 * sizeof(unsigned long long), h->stream));
     d.kind0 = player1; d.kind1 = player2; d.arena_total = games; d.arena_slot_cap = games_per_slot_cap;
     d.arena_mirror = mirror_games; d.base_seed = base_seed;
     h->mode = 3;
@@ -1622,7 +1686,7 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
             const int row = 2 * (int)(h->arena_pass++ & 1u);
             Dev e = h->d;
             e.lc_base = row; e.lc_zero = 2 - row;
-            LAUNCH(h, k_arena_step, e);
+            ARENA_STEP(h, e);
             const int* cnt_dev = h->d.leaf_count + row;
             const bool beside = h->d.nodes2 && h->opponent != h;   // two launches on two streams (one handle on both sides: one stream, one after the other)
             if (h->d.nodes2) {   // the opponent's net on the opponent's stream, side by side with this one's: after the tree step, before the next
@@ -1648,7 +1712,7 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
         if (!h->arena_ev) HIPCHK(h, hipEventCreateWithFlags(&h->arena_ev, hipEventDisableTiming));
         for (int p = 0; p < passes; p++) {
             HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, 2 * sizeof(int), h->stream));
-            LAUNCH(h, k_arena_step, h->d);
+            ARENA_STEP(h, h->d);
             int cnt[2] = {0, 0};
             D2H(h, cnt, h->d.leaf_count, sizeof cnt);
             SYNC(h);
@@ -1669,7 +1733,7 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
     } else
     for (int p = 0; p < passes; p++) {
         if (needs_net) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, sizeof(int), h->stream));
-        LAUNCH(h, k_arena_step, h->d);
+        ARENA_STEP(h, h->d);
         if (needs_net) {   // one network: evaluate the waiting leaf slots only (one count read-back per pass)
             int cnt = 0;
             D2H(h, &cnt, h->d.leaf_count, sizeof cnt);
@@ -1730,6 +1794,13 @@ extern "C" int azr_arena_collect_samples(azr_engine* h, int on)
 {
     if (!h) return AZR_E_BAD_HANDLE;
     h->d.arena_collect = on ? 1 : 0;
+    return AZR_OK;
+}
+
+extern "C" int azr_arena_collect_scripted_samples(azr_engine* h, int on)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    h->arena_script = on != 0;
     return AZR_OK;
 }
 

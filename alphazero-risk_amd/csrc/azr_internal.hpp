@@ -137,6 +137,8 @@ struct azr_engine {
     unsigned arena_pass = 0;         // passes of the running arena that were queued without a read-back (parity = leaf_count row)
     hipEvent_t arena_ev2 = nullptr;  // ... and this stream's tree step done -> the opponent's net launch may start
     hipEvent_t arena_ev = nullptr;   // two-net arena: the opponent's net launch (on ITS stream) done -> this stream may go on
+    bool arena_script = false;    // azr_arena_collect_scripted_samples
+    bool arena_rec = false;       // ... as azr_arena_start found it: this arena's steps run k_arena_step_rec
     bool sp_tail = false;         // quota self-play: no game is left to start, slots go idle -> compacted net batches
     void* train = nullptr;        // azr_train.hip: optimiser state + activation slabs, created by the first azr_nn_train*
     void* dp_comm = nullptr;      // azr_dp_init: this handle's RCCL communicator (ncclComm_t), rank and world

@@ -33,6 +33,31 @@ __device__ __forceinline__ void script_init(ScriptW& p)
     p.land_to = NONE; p.land_from = NONE; p.attack_from_army = 0; p.pad = 0; p.owned_attack_mask_unused = 0;
 }
 
+// ---- Player::addTrainingSample (player/base/player.cpp:9-17) -------------------------------------------------------
+// The players below call `rec(s, move)` at exactly the reference's addTrainingSample sites, with the state as it is at
+// that call.  NoRec is the arena without scripted collection: it compiles to nothing, so that build is the same code.
+struct NoRec {
+    __device__ __forceinline__ void operator()(const WS&, uint32_t) const {}
+};
+// StageRec stages (encode88(s), one-hot pi = e_move over 43 entries, player = s.cur) into the slot's staging buffer, in the
+// layout the AlphaZero decisions use (azr_engine.hip, k_arena_step); a record past the buffer's end is counted, not staged
+struct StageRec {
+    uint8_t* stage;              // the slot's [cap][STAGE_BYTES]
+    uint32_t cap;
+    uint32_t& n;                 // records staged for the running game
+    unsigned long long& over;    // records that did not fit
+    __device__ __forceinline__ void operator()(const WS& s, uint32_t move) const
+    {
+        if (n >= cap) { over++; return; }
+        uint8_t* rec = stage + (size_t)n * STAGE_BYTES;
+        encode88(s, rec);
+        const uint32_t l = lane_id();
+        if (l < MOVES) reinterpret_cast<float*>(rec + 88)[l] = l == move ? 1.0f : 0.0f;
+        if (l == 0) rec[260] = (uint8_t)s.cur;
+        n++;
+    }
+};
+
 // ---- State:: move primitives the players call directly (state/state.cpp) ---------------------------------------
 __device__ __forceinline__ void reinforcement_move(WS& s, uint32_t amount, uint32_t to)  // :976-998 (+ addLandArmy :241-256)
 {
@@ -222,7 +247,8 @@ __device__ __forceinline__ void script_update(ScriptW& p, const WS& s, uint64_t 
 }
 
 // ScriptPlayer::attackLand (:82-135)
-__device__ __forceinline__ void script_attack_land(ScriptW& p, WS& s, const Rules& R)
+template <class Rec>
+__device__ __forceinline__ void script_attack_land(ScriptW& p, WS& s, const Rules& R, const Rec& rec)
 {
     if (p.land_from == NONE || p.land_to == NONE) { s.err = E_LOGIC; return; }
     while (s.reinf > 0) {
@@ -240,6 +266,7 @@ __device__ __forceinline__ void script_attack_land(ScriptW& p, WS& s, const Rule
         if (reinforcement == 0) { s.err = E_LOGIC; return; }
         while (reinforcement > 0) {
             const uint32_t step = (int)reinforcement < R.min_unit_move ? reinforcement : (uint32_t)R.min_unit_move;
+            rec(s, to);  // :105
             reinforcement_move(s, step, to);
             if (s.err) return;
             reinforcement -= step;
@@ -248,6 +275,7 @@ __device__ __forceinline__ void script_attack_land(ScriptW& p, WS& s, const Rule
     p.attack_from_army = land_army(s, p.land_from);
     while (p.attack_from_army > 1) {
         const uint32_t owner_before = land_owner(s, p.land_to);
+        rec(s, p.land_to);  // :115
         attack_move(s, p.land_from, p.land_to);
         if (s.err) return;
         const bool captured = land_owner(s, p.land_to) != owner_before;
@@ -255,6 +283,7 @@ __device__ __forceinline__ void script_attack_land(ScriptW& p, WS& s, const Rule
         if (captured && p.attack_from_army > 1) {
             uint32_t max_move = p.attack_from_army - 1;
             while (max_move > 0) {
+                rec(s, p.land_to);  // :125
                 const uint32_t step = (int)max_move < R.min_unit_move ? max_move : (uint32_t)R.min_unit_move;
                 max_move -= step;
                 attack_reinforcement_move(s, step);
@@ -266,18 +295,21 @@ __device__ __forceinline__ void script_attack_land(ScriptW& p, WS& s, const Rule
 }
 
 // ScriptPlayer::takeTurn (:162-227)
-__device__ __forceinline__ void script_take_turn(ScriptW& p, WS& s, const Rules& R)
+template <class Rec>
+__device__ __forceinline__ void script_take_turn(ScriptW& p, WS& s, const Rules& R, const Rec& rec)
 {
     const uint32_t me = s.cur, en = s.cur ^ 1u;
     if (s.phase == PH_SETUP) {
         script_update(p, s, m_owned(s, me), m_attack(s, me));
         if (p.land_from == NONE) { s.err = E_LOGIC; return; }
+        rec(s, p.land_from);  // :176
         setup_reinforcement_move(s, p.land_from);
         if (s.err) return;
         const uint64_t neutral = ALL_LANDS & ~m_owned(s, me) & ~m_owned(s, en);
         uint64_t nte = neutral & m_attack(s, en) & ~m_attack(s, me);
         if (nte == 0) nte = neutral & m_attack(s, en);
         const uint64_t pick = nte != 0 ? rng_random_mask(s, nte) : rng_random_mask(s, neutral);
+        rec(s, (uint32_t)ctz64(pick));  // :198
         setup_reinforcement_neutral_move(s, (uint32_t)ctz64(pick));
         return;
     }
@@ -285,7 +317,7 @@ __device__ __forceinline__ void script_take_turn(ScriptW& p, WS& s, const Rules&
     play_cards(s);
     while (attack_mask != 0 || s.reinf > 0) {
         script_update(p, s, owned_attack_mask, attack_mask);
-        script_attack_land(p, s, R);
+        script_attack_land(p, s, R, rec);
         if (s.err) return;
         owned_attack_mask = m_owned_army(s, me);
         attack_mask = m_attack_army(s, me);
@@ -296,33 +328,43 @@ __device__ __forceinline__ void script_take_turn(ScriptW& p, WS& s, const Rules&
             uint32_t amount = (land_army(s, c.from) - 1u) & 0xffu;
             const uint32_t space = (uint32_t)(ARMY_MAX - (int)land_army(s, c.to)) & 0xffu;
             amount = amount < space ? amount : space;
+            rec(s, c.to);  // :151
             fortify_move(s, amount, c.from, c.to);
             if (s.err) return;
-        }
+        } else rec(s, (uint32_t)SKIP);  // :157
     }
     next_player_game_turn(s);
 }
 
 // ---- RandomPlayer (random_player.cpp:22-111) ----------------------------------------------------------------------
-__device__ __forceinline__ void random_take_turn(WS& s, const Rules& R)
+// (the attack-from pick is not recorded; mobilisation records mobilizationTo for a move, mobilizationFrom for a stop)
+template <class Rec>
+__device__ __forceinline__ void random_take_turn(WS& s, const Rules& R, const Rec& rec)
 {
     const uint32_t me = s.cur, en = s.cur ^ 1u;
     while (s.err == 0 && game_status(s, R) == ST_NOT_ENDED && s.cur == me) {
         if (s.phase == PH_SETUP) {
             const uint64_t m = m_owned(s, me);
             if (m == 0) { s.err = E_INVALID_ARGUMENT; return; }
-            setup_reinforcement_move(s, (uint32_t)ctz64(rng_random_mask(s, m)));
+            const uint32_t to = (uint32_t)ctz64(rng_random_mask(s, m));
+            rec(s, to);  // :29
+            setup_reinforcement_move(s, to);
         } else if (s.phase == PH_SETUP_NEUTRAL) {
             const uint64_t m = ALL_LANDS & ~m_owned(s, me) & ~m_owned(s, en);
             if (m == 0) { s.err = E_INVALID_ARGUMENT; return; }
-            setup_reinforcement_neutral_move(s, (uint32_t)ctz64(rng_random_mask(s, m)));
+            const uint32_t to = (uint32_t)ctz64(rng_random_mask(s, m));
+            rec(s, to);  // :35
+            setup_reinforcement_neutral_move(s, to);
         } else if (s.phase == PH_REINFORCEMENT) {
             play_cards(s);
             const uint64_t m = m_owned(s, me) & ~m_owned_full(s, me);
             if (m == 0) { s.err = E_INVALID_ARGUMENT; return; }
-            reinforcement_move(s, 1, (uint32_t)ctz64(rng_random_mask(s, m)));
+            const uint32_t to = (uint32_t)ctz64(rng_random_mask(s, m));
+            rec(s, to);  // :43
+            reinforcement_move(s, 1, to);
         } else if (s.phase == PH_ATTACK) {
             const uint64_t mv = rng_random_mask(s, m_attack_army(s, me) | SKIP_MASK);
+            rec(s, (uint32_t)ctz64(mv));  // :49
             if (mv & SKIP_MASK) goto_fortify(s);
             else {
                 const uint32_t to = (uint32_t)ctz64(mv);
@@ -333,10 +375,15 @@ __device__ __forceinline__ void random_take_turn(WS& s, const Rules& R)
         } else if (s.phase == PH_ATTACK_MOBILIZATION) {
             if (rng_float(s) > 0.5f) {
                 const int v = (int)land_army(s, s.mob_from) - 1;
+                rec(s, s.mob_to);  // :68
                 attack_reinforcement_move(s, (uint32_t)(v < R.min_unit_move ? v : R.min_unit_move) & 0xffu);
-            } else goto_attack(s);
+            } else {
+                rec(s, s.mob_from);  // :73
+                goto_attack(s);
+            }
         } else if (s.phase == PH_FORTIFY) {
             const uint64_t mv = rng_random_mask(s, (m_owned(s, me) & ~m_owned_full(s, me)) | SKIP_MASK);
+            rec(s, (uint32_t)ctz64(mv));  // :82
             if (mv != SKIP_MASK) {
                 const uint32_t to = (uint32_t)ctz64(mv);
                 // component of `to` (order-free: mask flooding by ballots)

@@ -643,31 +643,87 @@ GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup
     return all;
 }
 
-GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, int otherKind, int games)
+// the arena's records so far, all of them, appended to `st` (the scripted-collection contract: drain after every run)
+static void drainAll(Engine& e, NNTrainDataStorage& st)
+{
+    std::vector<uint8_t> buf((size_t)65536 * AZR_RECORD_BYTES);
+    for (size_t n = 65536; n == 65536;) {
+        e.check(azr_samples_drain(e.h, buf.data(), 65536, &n), "drain");
+        st.appendPacked(buf.data(), n);
+    }
+}
+
+// CONCURRENT pairs need two slots (azr_arena_start): an engine with one slot plays them one after the other
+static int scriptedMirrorMode(const Engine& e)
+{
+    const int m = SETTINGS.arenaMirrorMode();
+    return m == AZR_MIRROR_CONCURRENT && e.games < 2 ? AZR_MIRROR_SEQUENTIAL : m;
+}
+
+GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, int otherKind, int games, NNTrainDataStorage* tds)
 {
     const uint32_t arenaCallsBase = ++arenaCallCounter;
     const int P = (int)pg1.nnGroup->size();
     printf("Playing games %d\n", games);
     std::vector<azr_game_results> res(P);
+    std::vector<NNTrainDataStorage> st(P);
     const int pairs = games / 2;
-    const int mirror = SETTINGS.arenaMirrorMode();
     forEachGpu(P, "benchmark games", [&](int i) {
         Engine& e = *pg1.nnGroup->getNN(i)->engine;
         const int share = 2 * (pairs / P + (i < pairs % P ? 1 : 0));
         memset(&res[i], 0, sizeof res[i]);
         if (share == 0) return;
+        const int mirror = tds ? scriptedMirrorMode(e) : SETTINGS.arenaMirrorMode();
+        e.check(azr_arena_collect_samples(e.h, tds ? 1 : 0), "arena_collect_samples");
+        e.check(azr_arena_collect_scripted_samples(e.h, tds ? 1 : 0), "arena_collect_scripted_samples");
         e.check(azr_arena_start(e.h, AZR_PLAYER_ALPHAZERO, otherKind, share, 0, mirror,
                                 SETTINGS.BASE_SEED + 104729u * arenaCallsBase + (uint32_t)i * (1u << 24)), "arena_start");
         int fin = 0;
-        while (!fin) e.check(azr_arena_run(e.h, 4 * (SETTINGS.MCTS_SIMULATIONS + 2), &fin), "arena_run");
+        while (!fin) {
+            e.check(azr_arena_run(e.h, 4 * (SETTINGS.MCTS_SIMULATIONS + 2), &fin), "arena_run");
+            if (tds) drainAll(e, st[i]);
+        }
         e.check(azr_arena_results(e.h, &res[i]), "arena_results");
+        e.check(azr_arena_collect_samples(e.h, 0), "arena_collect_samples");
+        e.check(azr_arena_collect_scripted_samples(e.h, 0), "arena_collect_scripted_samples");
     });
+    if (tds) for (auto& s : st) tds->extend(s);
     GameResults all;
     for (auto& r : res) {
         all.count += r.count; all.draw += r.draw;
         for (int p = 0; p < 2; p++) { all.players[p].win += r.win[p]; all.players[p].winAndStartedGame += r.win_and_started[p]; }
     }
     return all;
+}
+
+int GameGroup::playScripted(AlphaZeroNNGroup& group, int kind0, int kind1, int games, NNTrainDataStorage& tds)
+{
+    const uint32_t arenaCallsBase = ++arenaCallCounter;
+    const int P = (int)group.size();
+    const int pairs = (games + 1) / 2;   // the arena plays whole mirrored pairs
+    std::vector<NNTrainDataStorage> st(P);
+    std::vector<int> played(P, 0);
+    forEachGpu(P, "scripted games", [&](int i) {
+        Engine& e = *group.getNN(i)->engine;
+        const int share = 2 * (pairs / P + (i < pairs % P ? 1 : 0));
+        if (share == 0) return;
+        e.check(azr_arena_collect_samples(e.h, 0), "arena_collect_samples");
+        e.check(azr_arena_collect_scripted_samples(e.h, 1), "arena_collect_scripted_samples");
+        e.check(azr_arena_start(e.h, kind0, kind1, share, 0, scriptedMirrorMode(e),
+                                SETTINGS.BASE_SEED + 15485863u * arenaCallsBase + (uint32_t)i * (1u << 24)), "arena_start");
+        int fin = 0;
+        while (!fin) {   // no network: one pass plays every slot's games to the end, or until the ring waits for a drain
+            e.check(azr_arena_run(e.h, 2, &fin), "arena_run");
+            drainAll(e, st[i]);
+        }
+        azr_game_results r{};
+        e.check(azr_arena_results(e.h, &r), "arena_results");
+        played[i] = r.count;
+        e.check(azr_arena_collect_scripted_samples(e.h, 0), "arena_collect_scripted_samples");
+    });
+    int n = 0;
+    for (int i = 0; i < P; i++) { tds.extend(st[i]); n += played[i]; }
+    return n;
 }
 
 // ---- trainer: model selection (alphazero_trainer.cpp:121-198) ----------------------------------------------------------
@@ -728,6 +784,69 @@ bool AlphaZeroTrainer::updateIfImprovement(std::shared_ptr<AlphaZeroNNGroup> tra
     AlphaZeroPlayerGroup generateAZPG(generateGroup);
     if (doBenchmark) benchmark(generateAZPG);
     return true;
+}
+
+// ---- trainer: training without self-play (alphazero_trainer.cpp:200-317) -------------------------------------------------
+void AlphaZeroTrainer::trainOnScript(std::shared_ptr<AlphaZeroNNGroup> nnGroup, std::shared_ptr<AlphaZeroNNGroup> oldNNGroup)
+{
+    trainStorage.loadTrainingSamples(SETTINGS.DEFAULT_SAMPLES);
+    AlphaZeroPlayerGroup azpGroup(nnGroup);
+    printf("Started training on script player\n");
+    for (trainIteration = 0; trainIteration < SETTINGS.TRAIN_ITERATIONS; trainIteration++) {
+        printf("Train iteration %ld\n", trainIteration);
+        GameResults gr = GameGroup::playGames(azpGroup, AZR_PLAYER_SCRIPT, SETTINGS.TRAIN_ITERATION_GAMES * 2, &trainStorage);
+        logFile("log/azr-benchmark-log.txt") << trainIteration << ",,,," << gr << std::endl;
+        trainStorage.trimOldExamples();
+        nnGroup->train(trainStorage.data, SETTINGS.EPOCHS);
+        if (updateIfImprovement(nnGroup, oldNNGroup, false)) trainStorage.updateOldGamesIndex();
+    }
+    trainStorage.saveTrainingSamples(SETTINGS.DEFAULT_SAMPLES);
+}
+
+void AlphaZeroTrainer::trainOnGeneratedData(std::shared_ptr<AlphaZeroNNGroup> trainGroup, std::shared_ptr<AlphaZeroNNGroup> generatorGroup)
+{
+    printf("Started training on generated data\n");
+    for (int e = 0; e < SETTINGS.DATA_TRAIN_LOOPS; e++) {
+        printf("===> Train loop %d\n", e);
+        NNTrainDataStorage storage;
+        const auto t0 = std::chrono::steady_clock::now();
+        int played = 0;
+        if (SETTINGS.DATA_GAMES_SS > 0) {
+            printf("Generating training data with Script vs Script games %d\n", SETTINGS.DATA_GAMES_SS);
+            const size_t before = storage.data.size();
+            const int n = GameGroup::playScripted(*trainGroup, AZR_PLAYER_SCRIPT, AZR_PLAYER_SCRIPT, SETTINGS.DATA_GAMES_SS, storage);
+            if (n != SETTINGS.DATA_GAMES_SS) printf("Played %d games (whole mirrored pairs)\n", n);
+            printf("Samples generated %d\n", int(storage.data.size() - before));
+            played += n;
+        }
+        if (SETTINGS.DATA_GAMES_SR > 0) {
+            printf("Generating training data with Script vs Random games: %d\n", SETTINGS.DATA_GAMES_SR);
+            const size_t before = storage.data.size();
+            const int n = GameGroup::playScripted(*trainGroup, AZR_PLAYER_SCRIPT, AZR_PLAYER_RANDOM, SETTINGS.DATA_GAMES_SR, storage);
+            if (n != SETTINGS.DATA_GAMES_SR) printf("Played %d games (whole mirrored pairs)\n", n);
+            printf("Samples generated %d\n", int(storage.data.size() - before));
+            played += n;
+        }
+        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        printf("Generated %zu samples from %d games in %.2f s\n", storage.data.size(), played, dt);
+        trainGroup->train(storage.data, 3);
+        {
+            printf("Playing comparison games betweean new and old model\n");
+            AlphaZeroPlayerGroup azpGroup(trainGroup), oldAzpGroup(generatorGroup);
+            GameResults grc = GameGroup::playGames(azpGroup, oldAzpGroup, SETTINGS.COMPARE_GAMES);
+            logFile("log/azr-improvement-log.txt") << grc << std::endl;
+            if (isModelImproved(grc)) {
+                printf("Model improved\n");
+                trainGroup->saveCheckpoint(SETTINGS.DEFAULT_CHECKPOINT_DIR + "/checkpoint-data-epoch-" + std::to_string(e) + ".bin");
+                trainGroup->saveCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
+                generatorGroup->loadCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
+                printf("Playing benchmark games\n");
+                GameResults grb = GameGroup::playGames(azpGroup, AZR_PLAYER_SCRIPT, SETTINGS.BENCHMARK_GAMES_SCRIPT);
+                logFile("log/azr-benchmark-log.txt") << grb << std::endl;
+            }
+            trainGroup->saveCheckpoint(SETTINGS.DEFAULT_CHECKPOINT_TEMP);   // keep the latest model on disk at all times
+        }
+    }
 }
 
 }  // namespace azrhost

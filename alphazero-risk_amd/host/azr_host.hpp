@@ -240,7 +240,14 @@ std::ostream& operator<<(std::ostream& os, const GameResults& gr);
 class GameGroup {
 public:
     static GameResults playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup& pg2, int games, NNTrainDataStorage* tds = nullptr);
-    static GameResults playGames(AlphaZeroPlayerGroup& pg1, int otherKind /* AZR_PLAYER_SCRIPT | RANDOM */, int games);
+    // `tds` (optional, train-script): both sides' records — the AlphaZero player's (s, pi) and the ScriptPlayer's / RandomPlayer's
+    // one-hot moves (player.cpp:9-17) — game by game in move order (GameGroup::playGames(.., tds), game.cpp:256-275)
+    static GameResults playGames(AlphaZeroPlayerGroup& pg1, int otherKind /* AZR_PLAYER_SCRIPT | RANDOM */, int games,
+                                 NNTrainDataStorage* tds = nullptr);
+    // Game::playGames(games) between two scripted players (kinds AZR_PLAYER_SCRIPT / RANDOM) with one storage attached to
+    // both (train-data, alphazero_trainer.cpp:240-275), on the device arena of `group`'s engines, split over the GPUs;
+    // returns the games played (whole mirrored pairs: an odd count is rounded up)
+    static int playScripted(AlphaZeroNNGroup& group, int kind0, int kind1, int games, NNTrainDataStorage& tds);
 };
 
 struct SelfPlayReport {
@@ -259,6 +266,9 @@ public:
     void train(std::shared_ptr<AlphaZeroNNGroup> trainGroup, std::shared_ptr<AlphaZeroNNGroup> generateGroup);
     bool updateIfImprovement(std::shared_ptr<AlphaZeroNNGroup> trainGroup, std::shared_ptr<AlphaZeroNNGroup> generateGroup, bool doBenchmark);
     void benchmark(AlphaZeroPlayerGroup& azpg);
+    // `-m train-script` (alphazero_trainer.cpp:200-225) and `-m train-data` (:227-317)
+    void trainOnScript(std::shared_ptr<AlphaZeroNNGroup> nnGroup, std::shared_ptr<AlphaZeroNNGroup> oldNNGroup);
+    void trainOnGeneratedData(std::shared_ptr<AlphaZeroNNGroup> trainGroup, std::shared_ptr<AlphaZeroNNGroup> generatorGroup);
     static bool isModelImproved(const GameResults& gr);
 };
 

@@ -82,6 +82,20 @@ static void executePlay()
     printf("\nGames: %d\nDraws:%d\nPlayer 1:%d\nPlayer 2:%d\n", gr.count, gr.draw, gr.win[0], gr.win[1]);
 }
 
+// `-m train-script` / `-m train-data` (src/alphazero_risk.cpp:84-111): the same two groups as `-m train`
+static void executeTrainWithout(bool script)
+{
+    auto cluster = std::make_shared<AlphaZeroCluster>();
+    cluster->initGpus(SETTINGS.NUMBER_OF_GPUS);
+    auto trainGroup = cluster->initPlayerGroup("az_train", SETTINGS.GRAPH_DEF_PB_1);
+    trainGroup->loadCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
+    auto generateGroup = cluster->initPlayerGroup("az_generate", SETTINGS.GRAPH_DEF_PB_1);
+    generateGroup->loadCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
+    AlphaZeroTrainer trainer;
+    if (script) trainer.trainOnScript(trainGroup, generateGroup);
+    else trainer.trainOnGeneratedData(trainGroup, generateGroup);
+}
+
 int main(int argc, char* argv[])
 {
     SETTINGS.init(argc, argv);
@@ -89,6 +103,8 @@ int main(int argc, char* argv[])
     try {
         if (SETTINGS.MODE == "train") executeTrain();
         else if (SETTINGS.MODE == "play") executePlay();
+        else if (SETTINGS.MODE == "train-script") executeTrainWithout(true);
+        else if (SETTINGS.MODE == "train-data") executeTrainWithout(false);
         else printf("Mode '%s' is outside this round's hot-path scope (SURVEY §8f)\n", SETTINGS.MODE.c_str());
     } catch (const std::exception& ex) {
         fprintf(stderr, "fatal: %s\n", ex.what());

@@ -256,8 +256,29 @@ int azr_arena_run(azr_engine* h, int passes, int* finished_out);
 int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other);
 /* INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES (alphazero_trainer.cpp:143-146): AlphaZero players push (s, pi) at every decision
  * (alphazero_player.cpp:15-18); a finished game's records get their z and go to the record ring (azr_samples_drain),
- * game by game in decision order (the reference appends player by player).  Set before azr_arena_start. */
+ * game by game in decision order (the reference appends player by player).  Set before azr_arena_start.  Its sibling
+ * azr_arena_collect_scripted_samples records the ScriptPlayer / RandomPlayer side; either, both or neither may be on. */
 int azr_arena_collect_samples(azr_engine* h, int on);
+/* Player::addTrainingSample with a trainStorage attached (player/base/player.cpp:9-17; train-data / train-script,
+ * alphazero_trainer.cpp:200-317): ScriptPlayer and RandomPlayer push (player = current player, NNInputData(state),
+ * pi = one-hot: 1.0 at the move's index, 0.0 elsewhere, SKIP = 42) with the state as it is at the reference's call sites:
+ *   ScriptPlayer (script_player.cpp): setup landAttackFrom :176; setup neutral land :198; every reinforcement step
+ *     reinforcmentTo :105; every attack roll landAttackTo :115; every post-capture mobilisation step landAttackTo :125;
+ *     fortify landFortifyTo :151, or SKIP :157 when it has lands with army but no fortify move
+ *   RandomPlayer (random_player.cpp): setup :29; neutral :35; reinforcement :43; attack target or SKIP :49 (the
+ *     attack-from pick is not recorded); mobilisation mobilizationTo on a move :68, mobilizationFrom on a stop :73;
+ *     fortify target or SKIP :82
+ * Recording draws nothing from the RNG and changes no move.  A finished game's records get z = updateValues
+ * (alphazero_nn_data.cpp:51-65) and go to the record ring as one block, in move order: with azr_arena_collect_samples
+ * also on, the AlphaZero and scripted records of a game interleave in the order the moves were made (train-data's one
+ * shared storage, alphazero_trainer.cpp:240-275).  More than sample_capacity records of one game: the rest are counted
+ * in records_dropped.
+ * Ring room: a game is dealt only once sample_capacity ring records are reserved for it (given back at its end, less
+ * what it wrote).  A slot without room waits, taking nothing from the quota and keeping its seed and pairs, so
+ * azr_arena_run may return *finished = 0 only because slots wait for a drain: call azr_samples_drain (all records)
+ * after every azr_arena_run, then azr_arena_run again.  Nothing is dropped for want of ring room.
+ * Set before azr_arena_start. */
+int azr_arena_collect_scripted_samples(azr_engine* h, int on);
 int azr_arena_results(azr_engine* h, azr_game_results* out);
 /* per slot: games finished, and for its first 16 games status / round count / final state image */
 int azr_arena_log(azr_engine* h, int32_t* games_per_slot_host, int8_t* status_host /*[G][16]*/,
