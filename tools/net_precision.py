@@ -2,7 +2,12 @@
 """Where every evaluation of the 20-block net stands against a float64 evaluation of the same graph (PyTorch on the CPU,
 tests/torch_train_ref.py): the oracle's fp32 CPU net (stand-in for the reference's fp32 TensorFlow session), and the engine's
 NET_F32 (fp32 VALU), NET_F32X (fp16-pair MFMA), NET_F16 and NET_BF16 towers, on the 128 distinct boards of tests/test_gpu_net.py.
-    python tools/net_precision.py [blocks]"""
+    python tools/net_precision.py [blocks]
+    python tools/net_precision.py --order-noise [blocks]   (CPU only)
+--order-noise: the CPU model of the bf16 / fp16 towers (tests/precision_ref.py: the kernels' rounding points) with fp32 against
+float64 accumulation, on 64 golden boards and make_net_flat(seed=3, perturb_bn=True) — how far summation order alone moves pi and v
+on a Glorot net, next to what truncation instead of RNE and the shortcut added after the rounding move them.  It is why
+tests/test_gpu_net_exact.py pins the towers on exact lattice nets instead of a tolerance around such a model."""
 import ctypes as C
 import importlib
 import os
@@ -25,7 +30,26 @@ def f64_forward(flat, blocks, x):
         return torch.softmax(lg, 1).numpy(), v.numpy()
 
 
+def order_noise(blocks):
+    import precision_ref as M
+    g = np.unique(np.load(os.path.join(T.GOLDEN, "encode.npz"))["in88"], axis=0)
+    x = g[np.linspace(0, len(g) - 1, 64).astype(int)].copy()
+    flat = T.make_net_flat(blocks, seed=3, perturb_bn=True)
+    print(f"B = {blocks}, {len(x)} golden boards, make_net_flat(seed=3, perturb_bn=True): max |d pi|, max |d v| against the rounding "
+          "model with float64 accumulation")
+    for el in (M.BF16, M.F16):
+        pi, v, _ = M.forward(flat, blocks, x, el)
+        for name, kw in (("fp32 accumulation", dict(accum="f32")), ("truncation instead of RNE", dict(round_mode="trunc")),
+                         ("shortcut after the rounding", dict(residual="after"))):
+            p2, v2, _ = M.forward(flat, blocks, x, el, **kw)
+            print(f"  {el.name:5s} {name:28s} {np.abs(p2 - pi).max():.1e} {np.abs(v2 - v).max():.1e}")
+
+
 def main():
+    if "--order-noise" in sys.argv:
+        args = [a for a in sys.argv[1:] if a != "--order-noise"]
+        order_noise(int(args[0]) if args else 20)
+        return
     blocks = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     P = importlib.import_module("alphazero-risk_amd")
     g = np.unique(np.load(os.path.join(T.GOLDEN, "encode.npz"))["in88"], axis=0)
