@@ -78,7 +78,7 @@ EXPORTS = [
     "azr_engine_new_games", "azr_engine_set_states", "azr_engine_get_states", "azr_engine_set_rng", "azr_engine_get_rng",
     "azr_engine_valid_moves", "azr_engine_make_moves", "azr_engine_status", "azr_engine_encode",
     "azr_nn_param_count", "azr_nn_init_random", "azr_nn_set_weights", "azr_nn_get_weights", "azr_nn_load", "azr_nn_save",
-    "azr_nn_predict", "azr_nn_train", "azr_nn_train_dp", "azr_dp_unique_id", "azr_dp_init", "azr_dp_shutdown", "azr_nn_train_batch", "azr_nn_train_grads", "azr_nn_train_reset", "azr_mcts_clear", "azr_mcts_trim", "azr_mcts_simulate", "azr_mcts_begin", "azr_mcts_leaves",
+    "azr_nn_predict", "azr_nn_train", "azr_nn_validate", "azr_nn_train_dp", "azr_dp_unique_id", "azr_dp_init", "azr_dp_shutdown", "azr_nn_train_batch", "azr_nn_train_grads", "azr_nn_train_reset", "azr_mcts_clear", "azr_mcts_trim", "azr_mcts_simulate", "azr_mcts_begin", "azr_mcts_leaves",
     "azr_mcts_apply", "azr_mcts_root_stats", "azr_mcts_policy", "azr_mcts_pick", "azr_selfplay_start", "azr_selfplay_start_games", "azr_selfplay_start_from_states",
     "azr_selfplay_run", "azr_selfplay_counters", "azr_samples_drain", "azr_samples_device_view", "azr_samples_copy_device", "azr_profile_last_run",
     "azr_device_synchronize", "azr_debug_tower_clock", "azr_debug_tower_trace", "azr_debug_tower_plan", "azr_arena_start", "azr_arena_run", "azr_arena_results", "azr_arena_log",
@@ -114,6 +114,7 @@ def load_library(test_hooks=False):
         L.azr_nn_train_dp.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, ALLREDUCE_FN,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
         L.azr_nn_train_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.azr_nn_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.azr_dp_unique_id.argtypes = [C.c_void_p]
         L.azr_dp_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.azr_dp_shutdown.argtypes = [C.c_void_p]
@@ -336,6 +337,21 @@ class Engine:
         r = np.ascontiguousarray(rec265, np.uint8).reshape(-1, 265)
         l = np.zeros(2, np.float32)
         self._chk(self.L.azr_nn_train_batch(self.h, _p(r), len(r), _p(l[0:1]), _p(l[1:2])))
+        return float(l[0]), float(l[1])
+
+    def validate(self, rec265, batch_size=512, per_record=False):
+        """azr_nn_validate: the cross-validation loss of these records in inference mode (BN on the moving statistics, no update):
+        (loss_pi, loss_v) averaged over the floor(n / batch_size) batches (NaN when n < batch_size); per_record=True adds the
+        per-record cross-entropy and squared error of the evaluated records"""
+        r = np.ascontiguousarray(rec265, np.uint8).reshape(-1, 265)
+        l = np.zeros(2, np.float32)
+        m = (len(r) // batch_size) * batch_size if batch_size > 0 else 0
+        rp = np.zeros(max(m, 1), np.float32)
+        rv = np.zeros(max(m, 1), np.float32)
+        self._chk(self.L.azr_nn_validate(self.h, _p(r) if len(r) else None, len(r), batch_size, _p(l[0:1]), _p(l[1:2]),
+                                         _p(rp) if per_record else None, _p(rv) if per_record else None))
+        if per_record:
+            return float(l[0]), float(l[1]), rp[:m], rv[:m]
         return float(l[0]), float(l[1])
 
     def train_grads(self):

@@ -1780,6 +1780,30 @@ __global__ __launch_bounds__(256) void t_bn_apply(const float* __restrict__ Y, c
     if (q0) split_store4_f16(o, i, q0, q1);  // fp16 pair: the next layer's 3-pass forward conv
 }
 
+// inference mode (the validation pass, azr_nn_validate): mean / 1/sqrt(var+eps) of every BN layer taken from its MOVING statistics in
+// the AZRW vector w (read only), in the slots t_bn_finalize fills with batch statistics — block 0 the stem's 7 rows, block l of 1 .. L-1
+// conv layer l, block L the three head channels (hstat) — so that the forward kernels run unchanged
+__global__ __launch_bounds__(256) void t_bn_moving(const float* __restrict__ w, int L, float* __restrict__ mean, float* __restrict__ istd,
+                                                   float* __restrict__ hstat)
+{
+    const int l = blockIdx.x, t = threadIdx.x;
+    auto inv_std = [](float var) { return (float)(1.0 / sqrt((double)var + (double)BN_EPS)); };
+    if (l == 0) {
+        const float* bn = w + OFF_STEM_BN;   // g | b | mu | var, 7 each
+        if (t < NG) { mean[t] = bn[2 * NG + t]; istd[t] = inv_std(bn[3 * NG + t]); }
+    } else if (l < L) {
+        const float* bn = w + OFF_BLOCK0 + (size_t)(l - 1) * LAYER + (size_t)9 * NF * NF;
+        mean[l * NF + t] = bn[2 * NF + t];
+        istd[l * NF + t] = inv_std(bn[3 * NF + t]);
+    } else if (t < 3) {
+        const float* hp = w + OFF_BLOCK0 + (size_t)(L - 1) * LAYER;
+        const float* bn = t < 2 ? hp + H_PI_BN : hp + H_V_BN;
+        const int C = t < 2 ? 2 : 1, k = t < 2 ? t : 0;
+        hstat[t] = bn[2 * C + k];
+        hstat[3 + t] = inv_std(bn[3 * C + k]);
+    }
+}
+
 // backward stage 1: dz = dOut * (Apost > 0); partial sums of dz and dz * xhat
 template <bool STEM>
 __global__ __launch_bounds__(1024) void t_bn_bwd_stats(const float* __restrict__ dOut, const float* __restrict__ Apost,
@@ -2053,6 +2077,88 @@ __global__ void t_loss_acc(const float* __restrict__ loss, float* __restrict__ a
     if (threadIdx.x == 0 && blockIdx.x == 0) { acc[0] += loss[0]; acc[1] += loss[1]; }
 }
 
+// The heads of the validation pass, fused: one block of 256 threads per board does t_head_conv's 1x1 convs (one wave per cell, the
+// same lane sums and butterfly), the head BN from hstat (t_bn_moving: the moving statistics), then t_head_fwd's dense layers and
+// losses — lossb[b] = {cross-entropy from the logits, (z - v)^2}.  Nothing for a backward pass is written.
+__global__ __launch_bounds__(256) void t_head_eval(const float* __restrict__ H, const float* __restrict__ hp, const float* __restrict__ hstat,
+                                                   const float* __restrict__ pit, const float* __restrict__ zt, float* __restrict__ lossb)
+{
+    __shared__ float s_pi[84], s_v[42], s_h[256], s_l[44];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    for (int cell = wave; cell < NPOS; cell += 4) {
+        const float4 h = reinterpret_cast<const float4*>(H)[((size_t)b * NPOS + cell) * 64 + lane];
+        const float hv[4] = {h.x, h.y, h.z, h.w};
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int c = lane * 4 + j;
+            s0 += hv[j] * hp[H_PI_W + c * 2];
+            s1 += hv[j] * hp[H_PI_W + c * 2 + 1];
+            s2 += hv[j] * hp[H_V_W + c];
+        }
+        for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        if (lane == 0) {
+            s_pi[cell * 2] = head_bn_relu(hp, hstat, s0, 0);
+            s_pi[cell * 2 + 1] = head_bn_relu(hp, hstat, s1, 1);
+            s_v[cell] = head_bn_relu(hp, hstat, s2, 2);
+        }
+    }
+    __syncthreads();
+    {   // dense_1 42 -> 256 + ReLU
+        float a = hp[H_V1_B + t];
+        for (int k = 0; k < 42; k++) a += s_v[k] * hp[H_V1_W + k * 256 + t];
+        s_h[t] = a > 0.0f ? a : 0.0f;
+    }
+    if (t < 43) {  // dense 84 -> 43
+        float a = hp[H_PD_B + t];
+        for (int k = 0; k < 84; k++) a += s_pi[k] * hp[H_PD_W + k * 43 + t];
+        s_l[t] = a;
+    }
+    __syncthreads();
+    if (t == 0) {
+        float mx = s_l[0];
+        for (int j = 1; j < 43; j++) mx = fmaxf(mx, s_l[j]);
+        float se = 0.0f;
+        for (int j = 0; j < 43; j++) se += expf(s_l[j] - mx);
+        const float lse = mx + logf(se);
+        float lp = 0.0f;
+        for (int j = 0; j < 43; j++) lp -= pit[b * 43 + j] * (s_l[j] - lse);
+        float a = hp[H_V2_B];
+        for (int j = 0; j < 256; j++) a += s_h[j] * hp[H_V2_W + j];
+        const float dv = zt[b] - tanhf(a);
+        lossb[b * 2] = lp;
+        lossb[b * 2 + 1] = dv * dv;
+    }
+}
+
+// per-batch means of the validation pass, t_loss's arithmetic: batch k (one block) = lossb + k * 2 BS; the terms are staged in LDS
+// by the block and summed in board order by one thread per loss -> means[k] = {sum(ce) / BS, sum(se) / BS}
+constexpr int VM_CHUNK = 1024;   // boards per LDS stage
+__global__ __launch_bounds__(256) void t_val_means(const float* __restrict__ lossb, int BS, float* __restrict__ means)
+{
+    __shared__ float s[2 * VM_CHUNK];
+    const int k = blockIdx.x, t = threadIdx.x;
+    const float* lb = lossb + (size_t)k * 2 * BS;
+    float acc = 0.0f;
+    for (int b0 = 0; b0 < BS; b0 += VM_CHUNK) {
+        const int nb = min(VM_CHUNK, BS - b0);
+        __syncthreads();
+        for (int i = t; i < 2 * nb; i += 256) s[i] = lb[2 * b0 + i];
+        __syncthreads();
+        if (t < 2)
+            for (int b = 0; b < nb; b++) acc += s[2 * b + t];
+    }
+    if (t < 2) means[(size_t)k * 2 + t] = acc / (float)BS;
+}
+// out[0..1] = the float sums of the batch means in batch order (t_loss_acc's accumulation)
+__global__ void t_val_sum(const float* __restrict__ means, int nbatch, float* __restrict__ out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float lp = 0.0f, lv = 0.0f;
+    for (int k = 0; k < nbatch; k++) { lp += means[2 * k]; lv += means[2 * k + 1]; }
+    out[0] = lp; out[1] = lv;
+}
+
 // backward of the dense parts; writes dz of the three head BN outputs (dpv [M][4]) and the per-board parameter partials
 __global__ __launch_bounds__(256) void t_head_bwd(const float* __restrict__ hp, const float* __restrict__ pit, const float* __restrict__ zt,
                                                   const float* __restrict__ fpi, const float* __restrict__ fv, const float* __restrict__ h1,
@@ -2284,6 +2390,9 @@ struct TrainCtx {
     size_t perm_cap = 0;
     uint8_t* in88 = nullptr;
     float *pit = nullptr, *zt = nullptr;
+    // validation pass (azr_nn_validate): {loss sums[2], range flag, pad, gather offsets cur[4]} | batch means [nb][2] | per-record terms [nb * BS][2]
+    float* vbuf = nullptr;
+    size_t vbuf_cap = 0;
     std::vector<void*> allocs;
 };
 
@@ -2305,6 +2414,7 @@ void ctx_free(TrainCtx* c)
     for (void* p : c->allocs) hipFree(p);
     if (c->rec) hipFree(c->rec);
     if (c->perm) hipFree(c->perm);
+    if (c->vbuf) hipFree(c->vbuf);
     delete c;
 }
 
@@ -2771,6 +2881,62 @@ int run_step(azr_engine* h, TrainCtx* c)
     return train_step(h, c, c->loss + 2);
 }
 
+// The forward pass of the validation (inference mode) on the minibatch already gathered into c->in88 / pit / zt: train_step's forward
+// kernels at the step's precision, with c->mean / istd / hstat holding the MOVING statistics (t_bn_moving, once per call) instead of
+// the batch's — no statistics kernels, no statistics epilogue in the convs (FUSE = 0), no moving-average update; then the fused heads
+// (t_head_eval) write the per-record losses to lossb.  Reads the weights, writes only the training context's scratch slabs.
+void eval_step(azr_engine* h, TrainCtx* c, float* lossb)
+{
+    hipStream_t st = h->stream;
+    const int M = c->M, BS = c->BS;
+    const float* w = h->net.d_flat;
+    const size_t act = (size_t)M * NF;
+    const float* hp = w + OFF_BLOCK0 + (size_t)2 * c->blocks * LAYER;
+    auto Wl = [&](int l) { return w + OFF_BLOCK0 + (size_t)(l - 1) * LAYER; };
+    auto Yl = [&](int l) { return c->Y + act * l; };
+    auto Al = [&](int l) { return c->A + act * l; };
+    auto Ap = [&](int l) { return Parts{{c->ap[0] + act * l, c->ap[1] + act * l, c->ap[2]}}; };
+    auto Wpf = [&](int l) { const size_t o = (size_t)(l - 1) * KC * NF; return Parts{{c->wpf[0] + o, c->wpf[1] + o, c->wpf[2] + o}}; };
+    const unsigned g4 = (unsigned)((act / 4 + 255) / 256);
+    // the same kernel choice as train_step (azr_nn_validate packed the forward kernels when sb)
+    const bool sb = g_gemm_bf16x3 && M % K3 == 0, f16 = sb && g_fwd_f16;
+    const bool convq = f16 && g_fuse_bwd && g_fuse_apply && g_conv_q && BS <= 128, fap = f16 && g_fuse_bwd && g_fuse_apply;
+    uint16_t* const nil16 = nullptr;
+    const Parts none{{nullptr, nullptr, nullptr}};
+    hipLaunchKernelGGL(t_planes, grid1((size_t)M * SIN, 256), dim3(256), 0, st, c->in88, M, c->X0);
+    hipLaunchKernelGGL((t_im2col<SIN>), grid1((size_t)M * 9, 4), dim3(256), 0, st, c->X0, c->col0, M);
+    gemm<false, false, 64>(st, c->col0, KS, c->wpad, NF, Yl(0), NF, M, NF, KS);
+    hipLaunchKernelGGL((t_bn_apply<true>), dim3(g4), dim3(256), 0, st, Yl(0), c->mean, c->istd, w + OFF_STEM_BN, (const float*)nullptr, Al(0), M,
+                       sb ? c->ap[0] : nil16, c->ap[1], f16 ? nil16 : c->ap[2], f16 ? c->af[0] : nil16, c->af[1]);
+    for (int l = 1; l < c->L; l++) {
+        const float* bn = Wl(l) + (size_t)9 * NF * NF;
+        const float* S = (l % 2 == 0) ? Al(l - 2) : nullptr;
+        if (sb) {
+            if (fap && l >= 2) {   // layer l - 1's normalise step in the staging path, as in the step
+                const int m = l - 1;
+                const ProFuse pf{Yl(m), (m % 2 == 0) ? (const float*)Al(m - 2) : (const float*)nullptr, nullptr, c->mean + m * NF, c->istd + m * NF,
+                                 Wl(m) + (size_t)9 * NF * NF, nullptr, 0.0f, Al(m), const_cast<uint16_t*>(Ap(m).p[0]), const_cast<uint16_t*>(Ap(m).p[1])};
+                if (convq) hipLaunchKernelGGL((t_conv_q<1, 0, true, 1>), dim3(4 * BS), dim3(256), 0, st, none, Wpf(l), Yl(l), BS, BwdFuse{}, 1.0f / FWD_WSCALE, pf);
+                else hipLaunchKernelGGL((t_conv_rs<1, 2, 0, true, 1>), dim3((BS + 1) / 2), dim3(256), 0, st, none, Wpf(l), Yl(l), BS, BwdFuse{}, 1.0f / FWD_WSCALE, pf);
+            } else if (f16) {      // operand = the fp16 pair the previous normalise kernel wrote
+                if (convq) hipLaunchKernelGGL((t_conv_q<1, 0, true, 0>), dim3(4 * BS), dim3(256), 0, st, Parts{{c->af[0], c->af[1], nullptr}}, Wpf(l), Yl(l), BS,
+                                              BwdFuse{}, 1.0f / FWD_WSCALE, ProFuse{});
+                else hipLaunchKernelGGL((t_conv_rs<1, 2, 0, true>), dim3((BS + 1) / 2), dim3(256), 0, st, Parts{{c->af[0], c->af[1], nullptr}}, Wpf(l), Yl(l), BS,
+                                        BwdFuse{}, 1.0f / FWD_WSCALE, ProFuse{});
+            }
+#ifdef AZR_TEST_HOOKS   // AZR_TRAIN_FWD=bf16: three bf16 parts, 6 passes
+            else hipLaunchKernelGGL((t_conv_rs<1, 3>), dim3((BS + 1) / 2), dim3(256), 0, st, Ap(l - 1), Wpf(l), Yl(l), BS, BwdFuse{}, 1.0f, ProFuse{});
+#endif
+        } else gemm<false, false, 64, 1, 0>(st, Al(l - 1), KC, Wl(l), NF, Yl(l), NF, M, NF, KC);
+        if (fap && l + 1 < c->L) continue;   // the next conv normalises this layer's output itself
+        hipLaunchKernelGGL((t_bn_apply<false>), dim3(g4), dim3(256), 0, st, Yl(l), c->mean + l * NF, c->istd + l * NF, bn, S, Al(l), M,
+                           (sb && l + 1 < c->L) ? const_cast<uint16_t*>(Ap(l).p[0]) : nil16, const_cast<uint16_t*>(Ap(l).p[1]), f16 ? nil16 : c->ap[2],
+                           (f16 && l + 1 < c->L) ? c->af[0] : nil16, c->af[1]);
+    }
+    hipLaunchKernelGGL(t_head_eval, dim3(BS), dim3(256), 0, st, (const float*)Al(c->L - 1), hp, (const float*)c->hstat, (const float*)c->pit,
+                       (const float*)c->zt, lossb);
+}
+
 // Behind an epoch (or a single step): did a conv weight leave the range of the fp16-pair forward conv (t_pack_w's flag: |w| >= 64, or
 // not a number), or did the losses stop being numbers?  Then the device copy of the weights and the optimiser state are poisoned: the
 // call fails loudly, the weights the handle had before the call (its host AZRW copy) are put back and the optimiser state is dropped.
@@ -2943,6 +3109,80 @@ extern "C" int azr_nn_train_dp(azr_engine* h, const void* rec265_host, size_t n,
 {
     ENTER(h);
     return train_impl(h, rec265_host, n, epochs, batch_size, shuffle_rng_state, rank, world, allreduce, ctx, loss_pi_host, loss_v_host, true);
+}
+
+// The validation phase of AlphaZeroNN::trainCrossValidation (alphazero_nn.cpp:512-548): every batch of the call is queued back to back
+// (gather with the device-side offset vbuf cur, eval_step), then the batch means and their sum; one read-back at the end.  The handle's
+// state — weights, moving statistics, Adam moments, step count, inference images — is only read.
+extern "C" int azr_nn_validate(azr_engine* h, const void* rec265_host, size_t n, int batch_size, float* loss_pi_out, float* loss_v_out,
+                               float* rec_loss_pi_host, float* rec_loss_v_host)
+{
+    ENTER(h);
+    if (!h->weights_set) { h->err = "azr_nn_validate: no weights"; return AZR_E_STATE; }
+    if ((!rec265_host && n > 0) || batch_size < 2) { h->err = "azr_nn_validate: bad arguments"; return AZR_E_INVALID_ARGUMENT; }
+    const size_t nb = n / (size_t)batch_size;   // the remainder is dropped (alphazero_nn.cpp:519)
+    if (nb == 0) {   // the reference's 0 / 0
+        if (loss_pi_out) *loss_pi_out = NAN;
+        if (loss_v_out) *loss_v_out = NAN;
+        return AZR_OK;
+    }
+    if (nb * (size_t)batch_size > (size_t)INT32_MAX) { h->err = "azr_nn_validate: too many records for one call"; return AZR_E_INVALID_ARGUMENT; }
+    TRY(ctx_ensure(h, batch_size));
+    TrainCtx* c = ctx_of(h);
+    hipStream_t st = h->stream;
+    const int BS = batch_size, B = c->blocks;
+    const size_t nrec = nb * (size_t)BS;
+    constexpr size_t HDR = 8;   // sums[2], range flag, pad, cur[4]
+    const size_t need = HDR + 2 * nb + 2 * nrec;
+    if (need > c->vbuf_cap) {
+        if (c->vbuf) hipFree(c->vbuf);
+        c->vbuf = nullptr; c->vbuf_cap = 0;
+        HIPCHK(h, hipMalloc((void**)&c->vbuf, need * sizeof(float)));
+        c->vbuf_cap = need;
+    }
+    float* means = c->vbuf + HDR;
+    float* lossb = means + 2 * nb;
+    int* flag = reinterpret_cast<int*>(c->vbuf + 2);
+    int* vcur = reinterpret_cast<int*>(c->vbuf + 4);   // {offset in perm, -, 0, -}: t_gather's view of cur
+    TRY(upload_records(h, c, rec265_host, nrec));
+    std::vector<int> id(nrec);
+    for (size_t i = 0; i < nrec; i++) id[i] = (int)i;
+    HIPCHK(h, hipMemcpyAsync(c->perm, id.data(), nrec * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemsetAsync(c->vbuf, 0, HDR * sizeof(float), st));
+    // once per call: the moving statistics into the statistics slots, the padded stem kernel, the packed forward kernels
+    const float* w = h->net.d_flat;
+    hipLaunchKernelGGL(t_bn_moving, dim3(c->L + 1), dim3(256), 0, st, w, c->L, c->mean, c->istd, c->hstat);
+    hipLaunchKernelGGL(t_stem_pad, grid1((size_t)KS * NF, 256), dim3(256), 0, st, w, c->wpad);
+    const bool sb = g_gemm_bf16x3 && c->M % K3 == 0, f16 = sb && g_fwd_f16;
+    if (sb) {
+        const dim3 pg((unsigned)((WPACK / 8 + 255) / 256), 2 * B);
+        hipLaunchKernelGGL((t_pack_w<3>), pg, dim3(256), 0, st, w, 0, c->wpf[0], c->wpf[1], c->wpf[2], f16 ? FWD_WSCALE : 0.0f, flag);
+    }
+    for (size_t k = 0; k < nb; k++) {
+        hipLaunchKernelGGL(t_gather, dim3(BS), dim3(64), 0, st, c->rec, c->perm, (const int*)vcur, BS, c->in88, c->pit, c->zt);
+        hipLaunchKernelGGL(t_tick_batch, dim3(1), dim3(1), 0, st, vcur, BS);
+        eval_step(h, c, lossb + k * 2 * BS);
+    }
+    hipLaunchKernelGGL(t_val_means, dim3((unsigned)nb), dim3(256), 0, st, (const float*)lossb, BS, means);
+    hipLaunchKernelGGL(t_val_sum, dim3(1), dim3(1), 0, st, (const float*)means, (int)nb, c->vbuf);
+    HIPCHK(h, hipGetLastError());
+    const bool per_record = rec_loss_pi_host || rec_loss_v_host;
+    std::vector<float> out(per_record ? need : HDR);
+    HIPCHK(h, hipMemcpyAsync(out.data(), c->vbuf, out.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    int range = 0;
+    memcpy(&range, &out[2], sizeof range);
+    if (range) {
+        h->err = "azr_nn_validate: a conv weight is outside the range of the fp16-pair forward conv (|w| must stay below 64) or is not a number";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    if (loss_pi_out) *loss_pi_out = out[0] / (float)nb;
+    if (loss_v_out) *loss_v_out = out[1] / (float)nb;
+    for (size_t i = 0; per_record && i < nrec; i++) {
+        if (rec_loss_pi_host) rec_loss_pi_host[i] = out[HDR + 2 * nb + 2 * i];
+        if (rec_loss_v_host) rec_loss_v_host[i] = out[HDR + 2 * nb + 2 * i + 1];
+    }
+    return AZR_OK;
 }
 
 // ---- the handle's own RCCL communicator (one process per GPU; the unique id travels by whatever the launcher has: torch.distributed,

@@ -6,9 +6,11 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <iostream>
 #include <map>
+#include <random>
 #include <sstream>
 
 namespace azrhost {
@@ -92,6 +94,8 @@ void Settings::init(int argc, char* argv[])
         {"seed", "[this build] base seed of the per-game RNG streams", std::to_string(BASE_SEED), false},
         {"devices", "[this build] HIP device of every logical gpu, comma separated (default 0,1,..; \"0,0\" rehearses --gpus 2 on one card)", "", false},
         {"pair-halves", "[this build] mirrored pairs: 1 = both games of a pair at the same time on two slots, 0 = one after the other on one slot", std::to_string(CONCURRENT_PAIR_HALVES), true},
+        {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
+        {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
     };
     std::map<std::string, std::string> val;
@@ -166,6 +170,8 @@ void Settings::init(int argc, char* argv[])
     NET_DTYPE = get("dtype");
     BASE_SEED = (uint32_t)strtoul(get("seed").c_str(), nullptr, 10);
     CONCURRENT_PAIR_HALVES = parse_bool(get("pair-halves"));
+    CV_K = atoi(get("cvk").c_str());
+    CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
     DEVICE_MAP.clear();
     {
         std::stringstream ss(get("devices"));
@@ -387,6 +393,95 @@ void AlphaZeroNNId::train(const std::vector<NNTrainData>& trainData, int epochs)
     if (SETTINGS.LOG_NN_TRAINING) logFile("log/azr-nn-training-log.txt") << std::endl;
     const size_t steps = (size_t)epochs * (trainData.size() / SETTINGS.BATCH_SIZE);
     printf("Trained %zu minibatch steps of %d in %.2f s (%.1f ms/step)\n", steps, SETTINGS.BATCH_SIZE, dt, steps ? 1e3 * dt / steps : 0.0);
+}
+
+// ---- cross-validation (`-m analysis`) ---------------------------------------------------------------------------------
+static uint32_t engineState(const std::minstd_rand0& eng)   // minstd_rand0 has no state accessor; operator<< prints it
+{
+    std::ostringstream os;
+    os << eng;
+    return (uint32_t)std::stoul(os.str());
+}
+static std::vector<uint8_t> packRecords(const std::vector<const NNTrainData*>& v)
+{
+    std::vector<uint8_t> buf(v.size() * AZR_RECORD_BYTES);
+    for (size_t i = 0; i < v.size(); i++) {
+        uint8_t* r = buf.data() + i * AZR_RECORD_BYTES;
+        r[0] = (uint8_t)v[i]->playerIndex;
+        memcpy(r + 1, v[i]->in.bytes, AZR_INPUT_BYTES);
+        memcpy(r + 89, &v[i]->out.value, 4);
+        memcpy(r + 93, v[i]->out.policy.data(), 4 * AZR_MOVES);
+    }
+    return buf;
+}
+
+// The reference takes its `lock` (a plain std::mutex) here and then calls initWeights() / saveCheckpoint(), which take it again: as
+// written it deadlocks in the first fold.  This is what it evidently intends, without the lock.  Every draw of the
+// global RNG — the fold shuffle, then per epoch the training-set and the validation-set shuffle — comes from g_shuffle_state, as for
+// `train`.  A fold starts from azr_nn_init_random(20260002 + vi) with the optimiser state dropped (TF's init op resets the Adam slots).
+void AlphaZeroNNId::trainCrossValidation(const std::vector<NNTrainData>& trainData, int k)
+{
+    if (k < 1) throw std::invalid_argument("trainCrossValidation: need k >= 1 folds");
+    std::vector<const NNTrainData*> shuffleTrainData(trainData.size());
+    for (size_t i = 0; i < trainData.size(); i++) shuffleTrainData[i] = &trainData[i];
+    const int crossValidationGroupSize = (int)(shuffleTrainData.size() / k);
+    float previousBestEpochLossV = 0.0f;
+    std::minstd_rand0 eng;
+    printf("Started cross-validation training\n");
+    for (int vi = 0; vi < k; vi++) {
+        printf("Cross-validation step: %d/%d\n", vi, k);
+        engine->check(azr_nn_init_random(engine->h, 20260002ull + (uint64_t)vi), "initWeights");
+        engine->check(azr_nn_train_reset(engine->h), "initWeights");
+        if (vi % k == 0) {
+            eng.seed(g_shuffle_state);
+            std::shuffle(shuffleTrainData.begin(), shuffleTrainData.end(), eng);
+            g_shuffle_state = engineState(eng);
+        }
+        std::vector<const NNTrainData*> trainingSamples, validationSamples;
+        const int start = vi * crossValidationGroupSize, end = (vi + 1) * crossValidationGroupSize;   // (index `start` trains)
+        for (int i = 0; i < (int)shuffleTrainData.size(); i++) (start < i && i < end ? validationSamples : trainingSamples).push_back(shuffleTrainData[i]);
+
+        bool modelLearning = true;
+        int failedImprovement = 0;
+        for (int e = 0; (e < SETTINGS.EPOCHS || modelLearning) && (SETTINGS.CV_MAX_EPOCHS <= 0 || e < SETTINGS.CV_MAX_EPOCHS); e++) {
+            printf("EPOCH %d\n", e);
+            {   // training phase: azr_nn_train shuffles the records it is given with the same engine and state, i.e. it trains on the
+                // minibatches of the shuffled trainingSamples; the host vector takes the same permutation
+                const std::vector<uint8_t> buf = packRecords(trainingSamples);
+                uint32_t st = g_shuffle_state;
+                float lp = NAN, lv = NAN;
+                engine->check(azr_nn_train(engine->h, buf.data(), trainingSamples.size(), 1, SETTINGS.BATCH_SIZE, &st, &lp, &lv), "train");
+                eng.seed(g_shuffle_state);
+                std::shuffle(trainingSamples.begin(), trainingSamples.end(), eng);
+                if (engineState(eng) != st) throw std::logic_error("trainCrossValidation: host and device shuffle streams diverged");
+                std::shuffle(validationSamples.begin(), validationSamples.end(), eng);
+                g_shuffle_state = engineState(eng);
+                printf("Training Loss Policy %f Value: %f\n", lp, lv);
+                saveCheckpoint(SETTINGS.DEFAULT_CHECKPOINT_DIR + "/cross-validation-" + std::to_string(vi) + "-" + std::to_string(e) + " .bin");
+                logFile("log/azr-nn-training-log.txt") << lp << "," << lv;
+            }
+            {   // validation phase: the same loss with batch norm on the moving statistics, no update
+                const std::vector<uint8_t> buf = packRecords(validationSamples);
+                float vlp = NAN, vlv = NAN;
+                engine->check(azr_nn_validate(engine->h, buf.data(), validationSamples.size(), SETTINGS.BATCH_SIZE, &vlp, &vlv, nullptr, nullptr),
+                              "validate");
+                printf("Validation Loss Policy %f Value: %f\n", vlp, vlv);
+                logFile("log/azr-nn-training-log.txt") << "," << vlp << "," << vlv << std::endl;
+                if (e == 0) {
+                    previousBestEpochLossV = vlv;
+                } else {
+                    const float diffAvgLoss = previousBestEpochLossV - vlv;
+                    if (diffAvgLoss > 0 && diffAvgLoss > previousBestEpochLossV * SETTINGS.DYNAMIC_EPOCH_THRESHOLD) {   // improved on validation
+                        previousBestEpochLossV = vlv;
+                        failedImprovement = 0;
+                    } else if (++failedImprovement == 3) {
+                        printf("=> Stopped training model is not learning\n");
+                        modelLearning = false;
+                    }
+                }
+            }
+        }
+    }
 }
 
 void AlphaZeroNNGroup::train(const std::vector<NNTrainData>& trainData, int epochs)

@@ -68,6 +68,8 @@ public:
     uint32_t BASE_SEED = 20260001;
     std::vector<int> DEVICE_MAP;         // --devices: HIP device of logical gpu i (empty = i); "0,0" rehearses --gpus 2 on one card
     bool CONCURRENT_PAIR_HALVES = true;  // --pair-halves: the two games of a mirrored pair on two slots at the same time (AZR_MIRROR_CONCURRENT)
+    int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
+    int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 
     int deviceOf(int gpu) const { return DEVICE_MAP.empty() ? gpu : DEVICE_MAP.at(gpu); }
     int arenaMirrorMode() const { return !MIRROR_GAMES ? AZR_MIRROR_OFF : CONCURRENT_PAIR_HALVES ? AZR_MIRROR_CONCURRENT : AZR_MIRROR_SEQUENTIAL; }
@@ -155,6 +157,9 @@ public:
     // AlphaZeroNN::train (alphazero_nn.cpp:351-410) through azr_nn_train: EPOCH loop, shuffle, floor(n/BATCH_SIZE)
     // optimiser steps, loss prints and log/azr-nn-training-log.txt columns
     void train(const std::vector<NNTrainData>& trainData, int epochs);
+    // AlphaZeroNN::trainCrossValidation (alphazero_nn.cpp:412-575): k folds, each a fresh net trained epoch by epoch
+    // (azr_nn_train, one epoch per call) and validated after every epoch (azr_nn_validate: inference-mode BN, no update)
+    void trainCrossValidation(const std::vector<NNTrainData>& trainData, int k);
 };
 
 class AlphaZeroNNGroup {  // alphazero_gpu_cluster.h:76-95: the same net on every GPU

@@ -1,7 +1,9 @@
 // AlphaZero_Risk_hip — CLI of the MI355X-native build; flags and modes as src/alphazero_risk.cpp:160-199 /
 // src/settings.h:91-137 (`-m learn` = `-m train`).
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <filesystem>
 
 #include "azr_host.hpp"
 
@@ -96,6 +98,25 @@ static void executeTrainWithout(bool script)
     else trainer.trainOnGeneratedData(trainGroup, generateGroup);
 }
 
+// `-m analysis` (src/alphazero_risk.cpp:64-82): k-fold cross-validation on one sample file of data/.  The reference takes whatever
+// std::filesystem::directory_iterator yields first (an unspecified order); here it is the first regular file in name order.  No file:
+// a loud failure before any device is opened.
+static void executeAnalysis()
+{
+    std::vector<std::string> files;
+    std::error_code ec;
+    for (const auto& entry : std::filesystem::directory_iterator(SETTINGS.DEFAULT_DATA, ec))
+        if (entry.is_regular_file()) files.push_back(entry.path().string());
+    if (files.empty())
+        throw std::runtime_error("-m analysis: no training sample file in '" + SETTINGS.DEFAULT_DATA + "/' (write one with -m train-script / "
+                                 "train-data, or learn.save_training_samples)");
+    std::sort(files.begin(), files.end());
+    NNTrainDataStorage storage;
+    storage.loadTrainingSamples(files[0]);
+    AlphaZeroNNId nn(std::make_shared<Engine>(SETTINGS, SETTINGS.deviceOf(0), SETTINGS.NUMBER_OF_CONCURENT_GAMES_PER_GPU), 0);
+    nn.trainCrossValidation(storage.data, SETTINGS.CV_K);
+}
+
 int main(int argc, char* argv[])
 {
     SETTINGS.init(argc, argv);
@@ -105,6 +126,7 @@ int main(int argc, char* argv[])
         else if (SETTINGS.MODE == "play") executePlay();
         else if (SETTINGS.MODE == "train-script") executeTrainWithout(true);
         else if (SETTINGS.MODE == "train-data") executeTrainWithout(false);
+        else if (SETTINGS.MODE == "analysis") executeAnalysis();
         else printf("Mode '%s' is outside this round's hot-path scope (SURVEY §8f)\n", SETTINGS.MODE.c_str());
     } catch (const std::exception& ex) {
         fprintf(stderr, "fatal: %s\n", ex.what());

@@ -126,6 +126,15 @@ int azr_nn_predict(azr_engine* h, const void* in88_host, int n, float* pi_host, 
  * state is dropped (the reference's TensorFlow step would carry the NaNs on silently). */
 int azr_nn_train(azr_engine* h, const void* rec265_host, size_t n, int epochs, int batch_size,
                  uint32_t* shuffle_rng_state, float* loss_pi_host, float* loss_v_host);
+/* the validation phase of AlphaZeroNN::trainCrossValidation (alphazero_nn.cpp:512-548): floor(n / batch_size) batches of
+ * records in the given order, forward in inference mode (BN on the moving statistics), no update.  *loss_*_out = the float
+ * sum of the batch means divided by the batch count (NaN when n < batch_size, as the reference's 0 / 0); rec_*_host
+ * (optional) = per-record cross-entropy / squared error of the batches * batch_size evaluated records.
+ * The pass runs at the training step's precision whatever the handle's inference dtype, and changes nothing on the handle:
+ * weights, moving statistics, Adam moments and step count stay as they are.  Errors as azr_nn_train (AZR_E_STATE without
+ * weights, AZR_E_INVALID_ARGUMENT for batch_size < 2, NULL records with n > 0, or a conv weight outside the fp16-pair range). */
+int azr_nn_validate(azr_engine* h, const void* rec265_host, size_t n, int batch_size,
+                    float* loss_pi_out, float* loss_v_out, float* rec_loss_pi_host, float* rec_loss_v_host);
 /* Data-parallel AlphaZeroNN::train: the same epochs / shuffles / minibatches, every minibatch split over `world` ranks
  * (one process per GPU; the reference trains on GPU 0 only and hands the weights over through checkpoints/temp.bin,
  * alphazero_gpu_cluster.cpp:221-231).  Every rank passes ALL n records and the same *shuffle_rng_state and takes slice
