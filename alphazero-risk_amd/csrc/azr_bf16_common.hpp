@@ -1,5 +1,6 @@
-// azr_bf16_common.hpp — constants, packed-weight layout and small device helpers shared by the bf16 MFMA tower kernels
-// (azr_net_bf16.hip: 1..3 boards per workgroup, double-buffered; azr_tower_sb.hip: 4 boards, single LDS buffer).
+// azr_bf16_common.hpp — constants, packed-weight layout and device helpers shared by the LDS-resident tower kernels (azr_net_bf16.hip:
+// one board per workgroup, two LDS images; azr_tower_sb.hip: 2..4 boards, one image; azr_tower_sc.hip: split channels; azr_tower_fx.hip:
+// NET_F32X), among them the fused heads all four end with.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -99,6 +100,95 @@ __device__ __forceinline__ float plane_value(const uint8_t* in88, int pos, int c
     }
 }
 
+
+typedef __attribute__((ext_vector_type(8))) float f32x8;
+
+// Both heads (build_graph.py:76-90), fused onto the end of a tower kernel whose output stays in LDS: one arithmetic, the fma chains of
+// k_heads (azr_net.hip) in the same order, shared by every LDS-resident tower.  NB boards from board0 (of n), THREADS threads; `hp` = the
+// head section of the AZRW vector; `rowof[b * 42 + pos]` = LDS row of cell pos of board b; act(row, q) = the 8 activations of channels
+// 8q .. 8q+7 of that row as floats (exact: the tower's element type widened, or NET_F32X's hi + lo).  LDS the caller provides:
+// wl [3][256] floats (16-byte aligned) for the 1x1-conv weight columns, feat [NB][128 + 256 + 64] floats for the features, the value
+// hidden layer and the logits.  The 256-term 1x1 convs read the activations 8 channels at a time from the tower image and the weight
+// columns from wl — the same fma chain over ci = 0..255 as k_heads, so the same bits.  47 k MAC per board: VALU work.
+template <int NB, int THREADS, class Act>
+__device__ __forceinline__ void fused_heads(int tid, const float* __restrict__ hp, float* wl, float* feat, const uint8_t* __restrict__ rowof,
+                                            Act act, int board0, int n, const int* __restrict__ slot_map, float* __restrict__ pi_out,
+                                            float* __restrict__ v_out)
+{
+    const int lane = tid & 63, wave = tid >> 6;
+    float* hid = feat + NB * 128;     // [NB][256]
+    float* logit = hid + NB * 256;    // [NB][64]
+    for (int i = tid; i < 3 * NF; i += THREADS) wl[i] = i < 2 * NF ? hp[H_PI_W + (i & (NF - 1)) * 2 + (i >> 8)] : hp[H_V_W + i - 2 * NF];
+    __syncthreads();
+    for (int idx = tid; idx < NB * 126; idx += THREADS) {  // 42 cells x {pi0, pi1, v} per board
+        const int bb = idx / 126, t = idx % 126, pos = t / 3, ch = t % 3;
+        const int row = rowof[bb * 42 + pos];
+        const float4* w4 = reinterpret_cast<const float4*>(wl + ch * NF);
+        float sacc = 0.0f;
+        for (int q = 0; q < NF / 8; q++) {
+            const f32x8 x = act(row, q);
+            const float4 wa = w4[2 * q], wb = w4[2 * q + 1];
+            sacc = fmaf(x[0], wa.x, sacc); sacc = fmaf(x[1], wa.y, sacc); sacc = fmaf(x[2], wa.z, sacc); sacc = fmaf(x[3], wa.w, sacc);
+            sacc = fmaf(x[4], wb.x, sacc); sacc = fmaf(x[5], wb.y, sacc); sacc = fmaf(x[6], wb.z, sacc); sacc = fmaf(x[7], wb.w, sacc);
+        }
+        const float* bnp = hp + (ch < 2 ? H_PI_BN : H_V_BN);   // g b m v, 2 or 1 channels each
+        const int nc = ch < 2 ? 2 : 1, kk = ch < 2 ? ch : 0;
+        float y = (sacc - bnp[2 * nc + kk]) * (bnp[kk] / sqrtf(bnp[3 * nc + kk] + 1e-3f)) + bnp[nc + kk];
+        y = y > 0.0f ? y : 0.0f;
+        if (ch < 2) feat[bb * 128 + pos * 2 + ch] = y;  // NHWC flatten: (y*6+x)*2 + c
+        else feat[bb * 128 + 84 + pos] = y;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < NB * 43; idx += THREADS) {
+        const int bb = idx / 43, t = idx % 43;
+        float sacc = 0.0f;
+        for (int i = 0; i < 84; i++) sacc = fmaf(feat[bb * 128 + i], hp[H_PD_W + i * 43 + t], sacc);
+        logit[bb * 64 + t] = sacc + hp[H_PD_B + t];
+    }
+    for (int idx = tid; idx < NB * 256; idx += THREADS) {
+        const int bb = idx >> 8, t = idx & 255;
+        float sacc = 0.0f;
+        for (int i = 0; i < 42; i++) sacc = fmaf(feat[bb * 128 + 84 + i], hp[H_V1_W + i * 256 + t], sacc);
+        sacc += hp[H_V1_B + t];
+        hid[idx] = (sacc > 0.0f ? sacc : 0.0f) * hp[H_V2_W + t];
+    }
+    __syncthreads();
+    // one wave per (board, head): softmax over the 43 logits / tanh of the 256-term value sum
+    for (int job = wave; job < NB * 2; job += THREADS / 64) {
+        const int bb = job >> 1;
+        if (board0 + bb >= n) continue;
+        const int slot = slot_map ? slot_map[board0 + bb] : board0 + bb;
+        if ((job & 1) == 0) {
+            const float lv = lane < 43 ? logit[bb * 64 + lane] : -INFINITY;
+            float mx = lv;
+            for (int sft = 32; sft >= 1; sft >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sft));
+            const float e = lane < 43 ? expf(lv - mx) : 0.0f;
+            float se = e;
+            for (int sft = 32; sft >= 1; sft >>= 1) se += __shfl_xor(se, sft);
+            if (lane < 43) pi_out[(size_t)slot * PI_STRIDE + lane] = e / se;
+            if (lane == 43) pi_out[(size_t)slot * PI_STRIDE + 43] = 0.0f;
+        } else {
+            const float* hb = hid + bb * 256;
+            float sacc = hb[lane] + hb[lane + 64] + hb[lane + 128] + hb[lane + 192];
+            for (int sft = 32; sft >= 1; sft >>= 1) sacc += __shfl_xor(sacc, sft);
+            if (lane == 0) v_out[slot] = tanhf(sacc + hp[H_V2_B]);
+        }
+    }
+}
+
+// act() of fused_heads for a bf16 / fp16 tower image (rows of ROWB bytes)
+template <bool F16>
+struct ImageAct {
+    const uint8_t* img;
+    __device__ __forceinline__ f32x8 operator()(int row, int q) const
+    {
+        const s16x8 x = reinterpret_cast<const s16x8*>(img + row * ROWB)[q];
+        f32x8 f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) f[e] = El<F16>::tof((uint16_t)x[e]);
+        return f;
+    }
+};
 
 constexpr size_t KSTRIDE = FRAGS_PER_KSTEP * 64;   // s16x8 units between consecutive k-steps
 constexpr size_t KBYTES = KSTRIDE * 16;            // bytes per k-step of packed weights (all 16 column tiles)

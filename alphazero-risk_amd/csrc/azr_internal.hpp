@@ -33,6 +33,14 @@ constexpr int STAGE_BYTES = 264;   // staged record: in88 @0 | pi[43] @88 | play
 constexpr int NF = 256;            // FILTERS (python/src/build_graph.py:32)
 constexpr int NPOS = 42;
 
+// head section of the AZRW vector, in floats from its start: policy 1x1 conv [256][2], its BN g[2] b[2] m[2] v[2],
+// policy dense [84][43] + bias [43]; value 1x1 conv [256], its BN g b m v, dense [42][256] + bias [256], output [256] + bias [1]
+constexpr int H_PI_W = 0, H_PI_BN = 512, H_PD_W = 520, H_PD_B = 4132, H_V_W = 4175, H_V_BN = 4431, H_V1_W = 4435,
+              H_V1_B = 15187, H_V2_W = 15443, H_V2_B = 15699, HEAD_FLOATS = 15700;
+static_assert(H_PI_BN == H_PI_W + NF * 2 && H_PD_W == H_PI_BN + 8 && H_PD_B == H_PD_W + 84 * 43 && H_V_W == H_PD_B + 43 &&
+              H_V_BN == H_V_W + NF && H_V1_W == H_V_BN + 4 && H_V1_B == H_V1_W + 42 * 256 && H_V2_W == H_V1_B + 256 &&
+              H_V2_B == H_V2_W + 256 && HEAD_FLOATS == H_V2_B + 1, "the head section's parts tile it without gaps");
+
 // device view handed to kernels by value
 struct Dev {
     int G, C, H, DMAX, SCAP;

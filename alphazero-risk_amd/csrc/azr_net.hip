@@ -44,7 +44,6 @@ static size_t off_stem_w() { return 0; }
 static size_t off_stem_bn() { return 9 * NIN * NF; }
 static size_t off_block(int i) { return off_stem_bn() + 28 + (size_t)i * 2 * (9 * NF * NF + 4 * NF); }
 static size_t off_heads(int blocks) { return off_block(blocks); }
-constexpr size_t HEAD_FLOATS = NF * 2 + 8 + 84 * 43 + 43 + NF + 4 + 42 * 256 + 256 + 256 + 1;
 
 size_t azr::net_param_count(int blocks) { return off_heads(blocks) + HEAD_FLOATS; }
 
@@ -205,23 +204,13 @@ __global__ __launch_bounds__(256) void k_heads(const XT* X, const float* hp, flo
     __shared__ float hid[256];
     __shared__ float logit[44];
     const int b = blockIdx.x, t = threadIdx.x;
-    const float* wpi = hp;              // [256][2]
-    const float* bnpi = wpi + NF * 2;   // g[2] b[2] m[2] v[2]
-    const float* wd = bnpi + 8;         // [84][43]
-    const float* bd = wd + 84 * 43;     // [43]
-    const float* wv = bd + 43;          // [256]
-    const float* bnv = wv + NF;         // g b m v
-    const float* w1 = bnv + 4;          // [42][256]
-    const float* b1 = w1 + 42 * 256;    // [256]
-    const float* w2 = b1 + 256;         // [256]
-    const float* b2 = w2 + 256;         // [1]
     const XT* x = X + (size_t)b * NPOS * NF;
     if (t < 126) {  // 42 positions x {pi0, pi1, v}
         const int pos = t / 3, c = t % 3;
         float s = 0.0f;
-        if (c < 2) for (int ci = 0; ci < NF; ci++) s = fmaf(load_act<XT>(x + pos * NF + ci), wpi[ci * 2 + c], s);
-        else for (int ci = 0; ci < NF; ci++) s = fmaf(load_act<XT>(x + pos * NF + ci), wv[ci], s);
-        const float* bn = c < 2 ? bnpi : bnv;
+        if (c < 2) for (int ci = 0; ci < NF; ci++) s = fmaf(load_act<XT>(x + pos * NF + ci), hp[H_PI_W + ci * 2 + c], s);
+        else for (int ci = 0; ci < NF; ci++) s = fmaf(load_act<XT>(x + pos * NF + ci), hp[H_V_W + ci], s);
+        const float* bn = hp + (c < 2 ? H_PI_BN : H_V_BN);
         const int nc = c < 2 ? 2 : 1, k = c < 2 ? c : 0;
         float y = (s - bn[2 * nc + k]) * (bn[k] / sqrtf(bn[3 * nc + k] + BN_EPS)) + bn[nc + k];
         y = y > 0.0f ? y : 0.0f;
@@ -231,14 +220,14 @@ __global__ __launch_bounds__(256) void k_heads(const XT* X, const float* hp, flo
     __syncthreads();
     if (t < 43) {
         float s = 0.0f;
-        for (int i = 0; i < 84; i++) s = fmaf(feat[i], wd[i * 43 + t], s);
-        logit[t] = s + bd[t];
+        for (int i = 0; i < 84; i++) s = fmaf(feat[i], hp[H_PD_W + i * 43 + t], s);
+        logit[t] = s + hp[H_PD_B + t];
     }
     {
         float s = 0.0f;
-        for (int i = 0; i < 42; i++) s = fmaf(feat[84 + i], w1[i * 256 + t], s);
-        s += b1[t];
-        hid[t] = (s > 0.0f ? s : 0.0f) * w2[t];
+        for (int i = 0; i < 42; i++) s = fmaf(feat[84 + i], hp[H_V1_W + i * 256 + t], s);
+        s += hp[H_V1_B + t];
+        hid[t] = (s > 0.0f ? s : 0.0f) * hp[H_V2_W + t];
     }
     __syncthreads();
     if (t < 64) {  // softmax over 43 logits by one wave
@@ -255,7 +244,7 @@ __global__ __launch_bounds__(256) void k_heads(const XT* X, const float* hp, flo
         const int l = t - 64;
         float s = hid[l] + hid[l + 64] + hid[l + 128] + hid[l + 192];
         for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-        if (l == 0) v_out[slot_map ? slot_map[b] : b] = tanhf(s + b2[0]);
+        if (l == 0) v_out[slot_map ? slot_map[b] : b] = tanhf(s + hp[H_V2_B]);
     }
 }
 

@@ -387,86 +387,21 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_fx(const uint8_t* __restri
         __syncthreads();        // the new planes are complete
     }
 
-    // ---- both heads (build_graph.py:76-90) on the reconstructed fp32 activations: the fma chains of k_heads (azr_net.hip)
+    // ---- both heads on the reconstructed fp32 activations (hi + lo is exact in fp32); featF is free and holds the 1x1-conv weights
     // (The thread index goes through an opaque move first: left alone, the compiler computes the heads' thread-dependent addresses
     //  ahead of the layer loop and carries them across it in registers the loop needs — three of them ended in scratch, written once
     //  and read once per thread: 1.5 MB of the launch's 1.7 MB of HBM writes.)
-    {
-        int tid_h = threadIdx.x;
-        asm volatile("" : "+v"(tid_h));
-        const int tid = tid_h, lane = tid & 63, wave = tid >> 6;
-        const float* wpi = hp;              // [256][2]
-        const float* bnpi = wpi + NF * 2;   // g[2] b[2] m[2] v[2]
-        const float* wd = bnpi + 8;         // [84][43]
-        const float* bd = wd + 84 * 43;     // [43]
-        const float* wv = bd + 43;          // [256]
-        const float* bnv = wv + NF;         // g b m v
-        const float* w1 = bnv + 4;          // [42][256]
-        const float* b1 = w1 + 42 * 256;    // [256]
-        const float* w2 = b1 + 256;         // [256]
-        const float* b2 = w2 + 256;         // [1]
-        float* feat = reinterpret_cast<float*>(lds + G::HEAD_OFF);   // [NB][128]: 84 policy features, then 42 value features
-        float* hid = feat + NB * 128;                             // [NB][256]
-        float* logit = hid + NB * 256;                            // [NB][64]
-        float* wl3 = featF;                                       // [3][256]: the three 1x1-conv weight columns
-        for (int i = tid; i < 3 * NF; i += THREADS) wl3[i] = i < 2 * NF ? wpi[(i & (NF - 1)) * 2 + (i >> 8)] : wv[i - 2 * NF];
-        __syncthreads();
-        for (int idx = tid; idx < NB * 126; idx += THREADS) {  // 42 cells x {pi0, pi1, v} per board
-            const int bb = idx / 126, t = idx % 126, pos = t / 3, ch = t % 3;
-            const uint32_t ro = (uint32_t)rowof[bb * 42 + pos] * ROWB;
-            const f16x8* h8 = reinterpret_cast<const f16x8*>(bufH + ro);
-            const f16x8* l8 = reinterpret_cast<const f16x8*>(bufL + ro);
-            const float* w = wl3 + ch * NF;
-            float sacc = 0.0f;
-            for (int q = 0; q < NF / 8; q++) {
-                const f16x8 hh = h8[q], ll = l8[q];
+    int tid_h = threadIdx.x;
+    asm volatile("" : "+v"(tid_h));
+    auto act = [&](int row, int q) {
+        const uint32_t ro = (uint32_t)row * ROWB;
+        const f16x8 hh = reinterpret_cast<const f16x8*>(bufH + ro)[q], ll = reinterpret_cast<const f16x8*>(bufL + ro)[q];
+        f32x8 x;
 #pragma unroll
-                for (int e = 0; e < 8; e++) sacc = fmaf((float)hh[e] + (float)ll[e], w[8 * q + e], sacc);
-            }
-            const float* bnp = ch < 2 ? bnpi : bnv;
-            const int nc = ch < 2 ? 2 : 1, kk = ch < 2 ? ch : 0;
-            float y = (sacc - bnp[2 * nc + kk]) * (bnp[kk] / sqrtf(bnp[3 * nc + kk] + 1e-3f)) + bnp[nc + kk];
-            y = y > 0.0f ? y : 0.0f;
-            if (ch < 2) feat[bb * 128 + pos * 2 + ch] = y;  // NHWC flatten: (y*6+x)*2 + c
-            else feat[bb * 128 + 84 + pos] = y;
-        }
-        __syncthreads();
-        for (int idx = tid; idx < NB * 43; idx += THREADS) {
-            const int bb = idx / 43, t = idx % 43;
-            float sacc = 0.0f;
-            for (int i = 0; i < 84; i++) sacc = fmaf(feat[bb * 128 + i], wd[i * 43 + t], sacc);
-            logit[bb * 64 + t] = sacc + bd[t];
-        }
-        for (int idx = tid; idx < NB * 256; idx += THREADS) {
-            const int bb = idx >> 8, t = idx & 255;
-            float sacc = 0.0f;
-            for (int i = 0; i < 42; i++) sacc = fmaf(feat[bb * 128 + 84 + i], w1[i * 256 + t], sacc);
-            sacc += b1[t];
-            hid[idx] = (sacc > 0.0f ? sacc : 0.0f) * w2[t];
-        }
-        __syncthreads();
-        // one wave per (board, head): softmax over the 43 logits / tanh of the 256-term value sum
-        for (int job = wave; job < NB * 2; job += WAVES) {
-            const int bb = job >> 1;
-            if (board0 + bb >= n) continue;
-            const int slot = slot_map ? slot_map[board0 + bb] : board0 + bb;
-            if ((job & 1) == 0) {
-                const float lv = lane < 43 ? logit[bb * 64 + lane] : -INFINITY;
-                float mx = lv;
-                for (int sft = 32; sft >= 1; sft >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sft));
-                const float e = lane < 43 ? expf(lv - mx) : 0.0f;
-                float se = e;
-                for (int sft = 32; sft >= 1; sft >>= 1) se += __shfl_xor(se, sft);
-                if (lane < 43) pi_out[(size_t)slot * PI_STRIDE + lane] = e / se;
-                if (lane == 43) pi_out[(size_t)slot * PI_STRIDE + 43] = 0.0f;
-            } else {
-                const float* hb = hid + bb * 256;
-                float sacc = hb[lane] + hb[lane + 64] + hb[lane + 128] + hb[lane + 192];
-                for (int sft = 32; sft >= 1; sft >>= 1) sacc += __shfl_xor(sacc, sft);
-                if (lane == 0) v_out[slot] = tanhf(sacc + b2[0]);
-            }
-        }
-    }
+        for (int e = 0; e < 8; e++) x[e] = (float)hh[e] + (float)ll[e];
+        return x;
+    };
+    fused_heads<NB, THREADS>(tid_h, hp, featF, reinterpret_cast<float*>(lds + G::HEAD_OFF), rowof, act, board0, n, slot_map, pi_out, v_out);
 }
 
 struct FxNet {

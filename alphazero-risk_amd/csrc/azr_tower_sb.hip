@@ -359,84 +359,9 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_sb(const uint8_t* __restri
 
     if (diag && blockIdx.x == 0 && tid == 0) { diag[2] = __builtin_amdgcn_s_memtime(); diag[3] = __builtin_amdgcn_s_memrealtime(); }
     if (diag && tid == 0) { diag[8 + 8 * (size_t)blockIdx.x + 2] = __builtin_amdgcn_s_memrealtime(); diag[8 + 8 * (size_t)blockIdx.x + 6] = __builtin_amdgcn_s_memtime(); }
-    // ---- both heads (build_graph.py:76-90; the arithmetic of k_tower_bf16's fused heads, same order)
-    {
-        const float* wpi = hp;              // [256][2]
-        const float* bnpi = wpi + NF * 2;   // g[2] b[2] m[2] v[2]
-        const float* wd = bnpi + 8;         // [84][43]
-        const float* bd = wd + 84 * 43;     // [43]
-        const float* wv = bd + 43;          // [256]
-        const float* bnv = wv + NF;         // g b m v
-        const float* w1 = bnv + 4;          // [42][256]
-        const float* b1 = w1 + 42 * 256;    // [256]
-        const float* w2 = b1 + 256;         // [256]
-        const float* b2 = w2 + 256;         // [1]
-        float* feat = reinterpret_cast<float*>(lds + G::HEAD_OFF);   // [NB][128]: 84 policy features, then 42 value features
-        float* hid = feat + NB * 128;                             // [NB][256]
-        float* logit = hid + NB * 256;                            // [NB][64]
-        // 1x1 convs (256 -> 2 policy + 1 value channel per cell): the three weight columns are staged in LDS (the stem's
-        // feature image is free by now) and the activations are read 8 channels at a time — the same fma chain over
-        // ci = 0..255 as before, so the same bits, without 512 two-byte LDS reads and 512 global loads per output
-        float* wl = reinterpret_cast<float*>(bufF);              // [3][256]
-        for (int i = tid; i < 3 * NF; i += THREADS) wl[i] = i < 2 * NF ? wpi[(i & (NF - 1)) * 2 + (i >> 8)] : wv[i - 2 * NF];
-        __syncthreads();
-        for (int idx = tid; idx < NB * 126; idx += THREADS) {  // 42 cells x {pi0, pi1, v} per board
-            const int bb = idx / 126, t = idx % 126, pos = t / 3, ch = t % 3;
-            const s16x8* x8 = reinterpret_cast<const s16x8*>(bufX + rowof[bb * 42 + pos] * ROWB);
-            const float4* w4 = reinterpret_cast<const float4*>(wl + ch * NF);
-            float sacc = 0.0f;
-            for (int q = 0; q < NF / 8; q++) {
-                const s16x8 xx = x8[q];
-                const float4 wa = w4[2 * q], wb = w4[2 * q + 1];
-                sacc = fmaf(El<F16>::tof((uint16_t)xx[0]), wa.x, sacc); sacc = fmaf(El<F16>::tof((uint16_t)xx[1]), wa.y, sacc);
-                sacc = fmaf(El<F16>::tof((uint16_t)xx[2]), wa.z, sacc); sacc = fmaf(El<F16>::tof((uint16_t)xx[3]), wa.w, sacc);
-                sacc = fmaf(El<F16>::tof((uint16_t)xx[4]), wb.x, sacc); sacc = fmaf(El<F16>::tof((uint16_t)xx[5]), wb.y, sacc);
-                sacc = fmaf(El<F16>::tof((uint16_t)xx[6]), wb.z, sacc); sacc = fmaf(El<F16>::tof((uint16_t)xx[7]), wb.w, sacc);
-            }
-            const float* bnp = ch < 2 ? bnpi : bnv;
-            const int nc = ch < 2 ? 2 : 1, kk = ch < 2 ? ch : 0;
-            float y = (sacc - bnp[2 * nc + kk]) * (bnp[kk] / sqrtf(bnp[3 * nc + kk] + 1e-3f)) + bnp[nc + kk];
-            y = y > 0.0f ? y : 0.0f;
-            if (ch < 2) feat[bb * 128 + pos * 2 + ch] = y;  // NHWC flatten: (y*6+x)*2 + c
-            else feat[bb * 128 + 84 + pos] = y;
-        }
-        __syncthreads();
-        for (int idx = tid; idx < NB * 43; idx += THREADS) {
-            const int bb = idx / 43, t = idx % 43;
-            float sacc = 0.0f;
-            for (int i = 0; i < 84; i++) sacc = fmaf(feat[bb * 128 + i], wd[i * 43 + t], sacc);
-            logit[bb * 64 + t] = sacc + bd[t];
-        }
-        for (int idx = tid; idx < NB * 256; idx += THREADS) {
-            const int bb = idx >> 8, t = idx & 255;
-            float sacc = 0.0f;
-            for (int i = 0; i < 42; i++) sacc = fmaf(feat[bb * 128 + 84 + i], w1[i * 256 + t], sacc);
-            sacc += b1[t];
-            hid[idx] = (sacc > 0.0f ? sacc : 0.0f) * w2[t];
-        }
-        __syncthreads();
-        // one wave per (board, head): softmax over the 43 logits / tanh of the 256-term value sum
-        for (int job = wave; job < NB * 2; job += WAVES) {
-            const int bb = job >> 1;
-            if (board0 + bb >= n) continue;
-            const int slot = slot_map ? slot_map[board0 + bb] : board0 + bb;
-            if ((job & 1) == 0) {
-                const float lv = lane < 43 ? logit[bb * 64 + lane] : -INFINITY;
-                float mx = lv;
-                for (int sft = 32; sft >= 1; sft >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sft));
-                const float e = lane < 43 ? expf(lv - mx) : 0.0f;
-                float se = e;
-                for (int sft = 32; sft >= 1; sft >>= 1) se += __shfl_xor(se, sft);
-                if (lane < 43) pi_out[(size_t)slot * PI_STRIDE + lane] = e / se;
-                if (lane == 43) pi_out[(size_t)slot * PI_STRIDE + 43] = 0.0f;
-            } else {
-                const float* hb = hid + bb * 256;
-                float sacc = hb[lane] + hb[lane + 64] + hb[lane + 128] + hb[lane + 192];
-                for (int sft = 32; sft >= 1; sft >>= 1) sacc += __shfl_xor(sacc, sft);
-                if (lane == 0) v_out[slot] = tanhf(sacc + b2[0]);
-            }
-        }
-    }
+    // ---- both heads; the stem's feature image is free by now and holds the 1x1-conv weight columns
+    fused_heads<NB, THREADS>(tid, hp, reinterpret_cast<float*>(bufF), reinterpret_cast<float*>(lds + G::HEAD_OFF), rowof, ImageAct<F16>{bufX},
+                             board0, n, slot_map, pi_out, v_out);
     if (diag && tid == 0) diag[8 + 8 * (size_t)blockIdx.x + 3] = __builtin_amdgcn_s_memrealtime();
 }
 }  // namespace

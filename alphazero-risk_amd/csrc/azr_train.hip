@@ -64,9 +64,6 @@ constexpr int RB = 64;            // rows per block in the two-stage reductions
 constexpr size_t LAYER = (size_t)9 * NF * NF + 4 * NF;
 constexpr size_t OFF_STEM_BN = 9 * 13 * NF;
 constexpr size_t OFF_BLOCK0 = OFF_STEM_BN + 28;
-// head section
-constexpr int H_PI_W = 0, H_PI_BN = 512, H_PD_W = 520, H_PD_B = 4132, H_V_W = 4175, H_V_BN = 4431, H_V1_W = 4435,
-              H_V1_B = 15187, H_V2_W = 15443, H_V2_B = 15699, HEAD_FLOATS = 15700;
 // per-board dense-gradient partials (t_head_bwd): pd_w | pd_b | v1_w | v1_b | v2_w | v2_b
 constexpr int HP_PD_W = 0, HP_PD_B = 3612, HP_V1_W = 3655, HP_V1_B = 14407, HP_V2_W = 14663, HP_V2_B = 14919, HP_FLOATS = 14920;
 
