@@ -467,7 +467,10 @@ class Engine:
         self._chk(self.L.azr_arena_start(self.h, player1, player2, games, per_slot_cap, int(mirror), base_seed))
 
     def arena_set_opponent(self, other):
-        """the network of PLAYER_ALPHAZERO_B = `other`'s (an Engine on the same device, or None to detach)"""
+        """the network of PLAYER_ALPHAZERO_B = `other`'s: an Engine on the same device with at least this one's leaf slots (games x
+        threads), or None to detach.  Its blocks and dtype may differ from this Engine's (a 5-block net against a 20-block one, bf16
+        against f32x).  Pairings of NET_BF16 / NET_F16 / NET_F32X run without a host read-back per pass up to 256 leaf slots; an arena
+        with a NET_F32 side reads the leaf counts back every pass."""
         self._chk(self.L.azr_arena_set_opponent_net(self.h, other.h if other is not None else None))
         self._opponent = other   # keep it alive
 

@@ -221,6 +221,8 @@ int tower_sb_launch(azr_engine* h, int nb, int wgs, const uint8_t* d_in88, int i
 int tower_sc_init(azr_engine* h);
 void tower_sc_free(azr_engine* h);
 int tower_sc_launch(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st,
-                    const int* n_dev = nullptr, const int* n_other = nullptr);
+                    const int* n_dev = nullptr, const int* n_other = nullptr, int other_wgpp = 0);
+int tower_sc_wgs_per_pair();   // workgroups a counted k_tower_sc launch spends on a board pair
+int tower_sc_whole_chip();
 int tower_sc_fallbacks(azr_engine* h, unsigned long long* out);
 }  // namespace azr

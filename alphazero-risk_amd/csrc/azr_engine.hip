@@ -1668,13 +1668,16 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
     if (h->mode != 3) { h->err = "azr_arena_run: call azr_arena_start first"; return AZR_E_STATE; }
     const bool needs_net = h->d.kind0 == AZR_PLAYER_ALPHAZERO || h->d.kind1 == AZR_PLAYER_ALPHAZERO;
     const int GT = h->d.G * h->d.T;
-    // Up to 256 waiting leaves on the 16-bit towers: the net launches read the tree step's leaf counts from device memory themselves
-    // (net_forward_counted), so a pass is queued without a read-back and the host looks at the slots' states once per CHUNK passes —
-    // the passes of a slot that went idle meanwhile end at their first instruction.  (AZR_ARENA_COUNTED=0, test build: the read-back form.)
+    // Up to 256 waiting leaves on the 16-bit towers and the NET_F32X tower, in any pairing of them: the net launches read the tree step's
+    // leaf counts from device memory themselves (net_forward_counted), so a pass is queued without a read-back and the host looks at the
+    // slots' states once per CHUNK passes — the passes of a slot that went idle meanwhile end at their first instruction.  An arena with a
+    // NET_F32 side reads back.  (Test build, AZR_ARENA_COUNTED=0: the read-back form; =2: AZR_E_STATE where the read-back form would run.)
     // (At most min(slots, games) slots ever play: an engine of 512 slots that plays 100 compare games has at most 200 leaves waiting.)
     const int NB_MAX = std::min(h->d.G, std::max(1, h->d.arena_total)) * h->d.T;
-    const bool counted = hook_env_int("AZR_ARENA_COUNTED", 1) != 0 && net_forward_counted_ok(h, NB_MAX) &&
-                         (!h->d.nodes2 || net_forward_counted_ok(h->opponent, NB_MAX));
+    const int form = hook_env_int("AZR_ARENA_COUNTED", 1);
+    const bool can_count = net_forward_counted_ok(h, NB_MAX) && (!h->d.nodes2 || net_forward_counted_ok(h->opponent, NB_MAX));
+    const bool counted = form != 0 && can_count;
+    if (form == 2 && !can_count && (needs_net || h->d.nodes2)) { h->err = "azr_arena_run: AZR_ARENA_COUNTED=2 and this arena reads back"; return AZR_E_STATE; }
     if (counted && (needs_net || h->d.nodes2)) {
         constexpr int CHUNK = 16;
         if (!h->arena_ev) HIPCHK(h, hipEventCreateWithFlags(&h->arena_ev, hipEventDisableTiming));
@@ -1689,14 +1692,20 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
             ARENA_STEP(h, e);
             const int* cnt_dev = h->d.leaf_count + row;
             const bool beside = h->d.nodes2 && h->opponent != h;   // two launches on two streams (one handle on both sides: one stream, one after the other)
+            // what each launch has to know of the one beside it: its count word and the charge per board pair of its batch, from that
+            // handle's plan (test build, AZR_ARENA_BESIDE_WGPP=N: N instead — 1 = the workgroups k_tower_fx<2> really spends on a pair,
+            // 256 = the whole chip; tests and measurements of the side-by-side rule)
+            const int wgpp_hook = hook_env_int("AZR_ARENA_BESIDE_WGPP", 0);
+            const int wgpp_opp = !beside ? 0 : wgpp_hook > 0 ? wgpp_hook : net_counted_wgs_per_pair(h->opponent);
+            const int wgpp_own = !beside ? 0 : wgpp_hook > 0 ? wgpp_hook : net_counted_wgs_per_pair(h);
             if (h->d.nodes2) {   // the opponent's net on the opponent's stream, side by side with this one's: after the tree step, before the next
                 HIPCHK(h, hipEventRecord(h->arena_ev2, h->stream));
                 HIPCHK(h, hipStreamWaitEvent(h->opponent->stream, h->arena_ev2, 0));
-                int rc = net_forward_counted(h->opponent, h->d.leaf_in, LEAF_STRIDE, NB_MAX, cnt_dev + 1, beside ? cnt_dev : nullptr, h->d.net_pi, h->d.net_v, h->d.leaf_list + GT, h->opponent->stream);
+                int rc = net_forward_counted(h->opponent, h->d.leaf_in, LEAF_STRIDE, NB_MAX, cnt_dev + 1, beside ? cnt_dev : nullptr, wgpp_own, h->d.net_pi, h->d.net_v, h->d.leaf_list + GT, h->opponent->stream);
                 if (rc) { h->err = h->opponent->err; return rc; }
                 HIPCHK(h, hipEventRecord(h->arena_ev, h->opponent->stream));
             }
-            int rc = net_forward_counted(h, h->d.leaf_in, LEAF_STRIDE, NB_MAX, cnt_dev, beside ? cnt_dev + 1 : nullptr, h->d.net_pi, h->d.net_v, h->d.leaf_list, h->stream);
+            int rc = net_forward_counted(h, h->d.leaf_in, LEAF_STRIDE, NB_MAX, cnt_dev, beside ? cnt_dev + 1 : nullptr, wgpp_opp, h->d.net_pi, h->d.net_v, h->d.leaf_list, h->stream);
             if (rc) return rc;
             if (h->d.nodes2) HIPCHK(h, hipStreamWaitEvent(h->stream, h->arena_ev, 0));
             if (p % CHUNK == CHUNK - 1 && p + 1 < passes) {
@@ -1765,9 +1774,10 @@ extern "C" int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other)
 {
     ENTER(h);
     if (!other) { h->opponent = nullptr; return AZR_OK; }
-    if (other->cfg.device != h->cfg.device || other->net.blocks != h->net.blocks || other->cfg.net_dtype != h->cfg.net_dtype ||
-        other->d.G * other->d.T < h->d.G * h->d.T) {
-        h->err = "azr_arena_set_opponent_net: the opponent handle must be on the same device with the same net shape and >= leaf slots";
+    // Depth and element type are the opponent's own business: its launches run with its own weights, context and activation buffers on
+    // this handle's leaves (96-byte NNInputData in, fp32 pi / v out — the same for every tower).  Its buffers must hold this handle's batch.
+    if (other->cfg.device != h->cfg.device || other->d.G * other->d.T < h->d.G * h->d.T) {
+        h->err = "azr_arena_set_opponent_net: the opponent handle must be on the same device and have >= leaf slots";
         return AZR_E_INVALID_ARGUMENT;
     }
     Dev& d = h->d;

@@ -161,7 +161,8 @@ int net_upload(azr_engine* h);  // fold BN, pack, copy h->flat to the device
 int net_forward(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v);
 int net_forward_ex(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
 bool net_forward_counted_ok(azr_engine* h, int n_max);
-int net_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
+int net_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, int other_wgpp, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
+int net_counted_wgs_per_pair(azr_engine* h);   // what a split-channel launch beside h's counted launch charges a board pair of h's with
 size_t net_param_count(int blocks);
 void net_init_random(float* flat, int blocks, uint64_t seed);
 int net_fallbacks(azr_engine* h, unsigned long long* out);   // split-channel tower launches recomputed after a hand-off gave up
@@ -170,6 +171,8 @@ int net_fx_alloc(azr_engine* h);
 void net_fx_free(azr_engine* h);
 int net_fx_upload(azr_engine* h, const float* fold_host);
 int net_fx_forward(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
+bool net_fx_counted_ok(azr_engine* h, int n_max);
+int net_fx_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
 // train (azr_train.hip)
 void train_free(azr_engine* h);
 void dp_free(azr_engine* h);

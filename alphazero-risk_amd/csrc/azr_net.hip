@@ -34,7 +34,9 @@ void net_bf16_free(azr_engine* h);
 int net_bf16_upload(azr_engine* h, const float* fold_host);
 int net_bf16_forward(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
 bool net_bf16_counted_ok(azr_engine* h, int n_max);
-int net_bf16_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
+int net_bf16_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, int other_wgpp, float* d_pi, float* d_v, const int* d_map, hipStream_t st);
+int tower_sc_wgs_per_pair();
+int tower_sc_whole_chip();
 }  // namespace azr
 
 constexpr float BN_EPS = 1e-3f;  // tf.layers.batch_normalization default epsilon
@@ -394,16 +396,30 @@ int azr::net_forward_ex(azr_engine* h, const uint8_t* d_in88, int in_stride, int
     return net_bf16_forward(h, d_in88, in_stride, n, d_pi, d_v, d_map, st);
 }
 
-// forward of a batch whose size is the device word *n_dev (at most n_max boards), without a read-back: the 16-bit split-channel tower only
+// forward of a batch whose size is the device word *n_dev (at most n_max boards), without a read-back: the 16-bit split-channel tower
+// and the NET_F32X tower.  NET_F32 (the fp32 vector path, the tests' tolerance anchor) has one launch per layer and stays read-back only.
 bool azr::net_forward_counted_ok(azr_engine* h, int n_max)
 {
-    return (h->cfg.net_dtype == AZR_NET_BF16 || h->cfg.net_dtype == AZR_NET_F16) && h->net.bf16ctx && net_bf16_counted_ok(h, n_max);
+    if (h->cfg.net_dtype == AZR_NET_BF16 || h->cfg.net_dtype == AZR_NET_F16) return h->net.bf16ctx && net_bf16_counted_ok(h, n_max);
+    if (h->cfg.net_dtype == AZR_NET_F32X) return h->net.fxctx && net_fx_counted_ok(h, n_max);
+    return false;
 }
 
-int azr::net_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
+// what a split-channel launch BESIDE h's counted launch charges a board pair of h's batch with in its side-by-side rule (k_tower_sc):
+// the pair's workgroups for a split-channel launch.  k_tower_fx<2> spends one workgroup on a pair, but the split-channel form does not
+// pay beside it whatever the counts (measured both ways, see the rule in k_tower_sc): it is charged with the whole chip.
+int azr::net_counted_wgs_per_pair(azr_engine* h)
+{
+    return h->cfg.net_dtype == AZR_NET_F32X ? tower_sc_whole_chip() : tower_sc_wgs_per_pair();
+}
+
+// n_other (optional) = the count word of another handle's counted launch running beside this one, other_wgpp = net_counted_wgs_per_pair of
+// that handle
+int azr::net_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, int other_wgpp, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
 {
     if (!net_forward_counted_ok(h, n_max)) { h->err = "net_forward_counted: not available for this net / batch"; return AZR_E_STATE; }
-    return net_bf16_forward_counted(h, d_in88, in_stride, n_max, n_dev, n_other, d_pi, d_v, d_map, st);
+    if (h->cfg.net_dtype == AZR_NET_F32X) return net_fx_forward_counted(h, d_in88, in_stride, n_max, n_dev, d_pi, d_v, d_map, st);
+    return net_bf16_forward_counted(h, d_in88, in_stride, n_max, n_dev, n_other, other_wgpp, d_pi, d_v, d_map, st);
 }
 
 namespace azr { int tower_sc_fallbacks(azr_engine* h, unsigned long long* out); }   // azr_tower_sc.hip
@@ -493,13 +509,19 @@ extern "C" int azr_nn_predict(azr_engine* h, const void* in88, int n, float* pi,
     // batches of up to G boards through staging buffers that live as long as the handle (pinned host side: the copies are
     // real async DMA, no allocation in the call path — the reference's predict() is timed per call, alphazero_gpu_cluster.cpp:54-65)
     const int G = h->d.G;
-    const size_t in_b = (size_t)G * LEAF_STRIDE, pi_b = (size_t)G * PI_STRIDE * 4, v_b = (size_t)G * 4;
+    const size_t in_b = (size_t)G * LEAF_STRIDE, pi_b = (size_t)G * PI_STRIDE * 4, v_b = (size_t)G * 4, all_b = in_b + pi_b + v_b + 16;   // + one count word
     if (!h->net.pred_dev) {
-        HIPCHK(h, hipMalloc((void**)&h->net.pred_dev, in_b + pi_b + v_b));
-        HIPCHK(h, hipMemsetAsync(h->net.pred_dev, 0, in_b + pi_b + v_b, h->stream));
-        HIPCHK(h, hipHostMalloc((void**)&h->net.pred_host, in_b + pi_b + v_b, hipHostMallocDefault));
-        memset(h->net.pred_host, 0, in_b + pi_b + v_b);
+        HIPCHK(h, hipMalloc((void**)&h->net.pred_dev, all_b));
+        HIPCHK(h, hipMemsetAsync(h->net.pred_dev, 0, all_b, h->stream));
+        HIPCHK(h, hipHostMalloc((void**)&h->net.pred_host, all_b, hipHostMallocDefault));
+        memset(h->net.pred_host, 0, all_b);
     }
+    // test hook (libazr_hip_test.so only) AZR_PREDICT_COUNTED=N, N > 0: the batch goes through net_forward_counted — its size, capped at N,
+    // in a device word, the launch sized for the handle's leaf slots.  The copies stay those of the whole batch, so a call with N below
+    // its batch returns, for the boards from N on, what the device outputs held before it.
+    const int hook_n = hook_env_int("AZR_PREDICT_COUNTED", 0);
+    int* d_cnt = reinterpret_cast<int*>(h->net.pred_dev + in_b + pi_b + v_b);
+    int* s_cnt = reinterpret_cast<int*>(h->net.pred_host + in_b + pi_b + v_b);
     uint8_t* d_in = h->net.pred_dev;
     float* d_pi = reinterpret_cast<float*>(h->net.pred_dev + in_b);
     float* d_v = reinterpret_cast<float*>(h->net.pred_dev + in_b + pi_b);
@@ -511,6 +533,11 @@ extern "C" int azr_nn_predict(azr_engine* h, const void* in88, int n, float* pi,
         const int m = n - base < G ? n - base : G;
         for (int i = 0; i < m; i++) memcpy(s_in + (size_t)i * LEAF_STRIDE, (const uint8_t*)in88 + (size_t)(base + i) * 88, 88);
         HIPCHK(h, hipMemcpyAsync(d_in, s_in, (size_t)m * LEAF_STRIDE, hipMemcpyHostToDevice, h->stream));
+        if (hook_n > 0) {
+            *s_cnt = m < hook_n ? m : hook_n;
+            HIPCHK(h, hipMemcpyAsync(d_cnt, s_cnt, sizeof(int), hipMemcpyHostToDevice, h->stream));
+            rc = net_forward_counted(h, d_in, LEAF_STRIDE, G * h->d.T, d_cnt, nullptr, 0, d_pi, d_v, nullptr, h->stream);
+        } else
         rc = net_forward(h, d_in, LEAF_STRIDE, m, d_pi, d_v);
         if (rc) break;
         if (pi) HIPCHK(h, hipMemcpyAsync(s_pi, d_pi, (size_t)m * PI_STRIDE * 4, hipMemcpyDeviceToHost, h->stream));

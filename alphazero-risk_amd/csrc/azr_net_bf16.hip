@@ -493,7 +493,7 @@ int net_bf16_forward(azr_engine* h, const uint8_t* d_in88, int in_stride, int n,
 // Small batches whose size only the device knows (the arena's and the emptying self-play tail's waiting leaves, counted by the tree step
 // into *n_dev ahead of this call in stream order): no read-back, no host synchronisation per pass.  Both launches are sized for n_max
 // (<= 256) boards and read the count themselves: the split-channel tower takes up to 128 boards, above that — or when the launch of another
-// network beside it (n_other: that one's count) leaves it no CU per workgroup — it raises the give-up word with the value 2 and the guarded
+// network beside it (n_other: that one's count, other_wgpp: its workgroups per board pair) leaves it no CU per workgroup — it raises the give-up word with the value 2 and the guarded
 // one-board-per-workgroup launch computes the batch; a count of 0 ends every workgroup at once.
 bool net_bf16_counted_ok(azr_engine* h, int n_max)
 {
@@ -501,14 +501,14 @@ bool net_bf16_counted_ok(azr_engine* h, int n_max)
     return x && x->sb_mode == 1 && x->sc_mode != 0 && n_max >= 1 && n_max <= 256;   // the product's plan (no forced tile of the test build)
 }
 
-int net_bf16_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, float* d_pi, float* d_v,
-                             const int* d_map, hipStream_t st)
+int net_bf16_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, const int* n_other, int other_wgpp,
+                             float* d_pi, float* d_v, const int* d_map, hipStream_t st)
 {
     if (!net_bf16_counted_ok(h, n_max) || !n_dev) { h->err = "net_bf16_forward_counted: 1..256 boards on the split-channel tower"; return AZR_E_INVALID_ARGUMENT; }
     Bf16Net* x = bn(h);
     const int B = h->net.blocks;
     if (h->pe_tower0) hipEventRecord(h->pe_tower0, st);
-    int rc = tower_sc_launch(h, d_in88, in_stride, n_max, d_pi, d_v, d_map, st, n_dev, n_other);
+    int rc = tower_sc_launch(h, d_in88, in_stride, n_max, d_pi, d_v, d_map, st, n_dev, n_other, other_wgpp);
     if (h->pe_tower1) hipEventRecord(h->pe_tower1, st);
     if (rc) return rc;
     if (x->f16)

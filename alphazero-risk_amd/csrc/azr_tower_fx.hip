@@ -206,8 +206,16 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_fx(const uint8_t* __restri
                                                           const float* __restrict__ stem_w, const uint16_t* __restrict__ tower_wp,
                                                           const float* __restrict__ fold, int blocks, const float* __restrict__ hp,
                                                           float* __restrict__ pi_out, float* __restrict__ v_out,
-                                                          const int* __restrict__ slot_map)
+                                                          const int* __restrict__ slot_map, const int* __restrict__ n_dev)
 {
+    // n_dev != null: the batch size is a word in device memory (written by the tree step ahead of this launch in stream order; the grid
+    // was sized for the largest batch, `n` is only that bound).  The word is read, never written; workgroups past the count end here,
+    // before they request a weight fragment or touch an output, and the last partly filled workgroup masks its missing board as ever.
+    // This tower has one form and no give-up path, so the count of a launch beside it (k_tower_sc's n_other) is nothing it looks at.
+    if (n_dev) {
+        n = __builtin_amdgcn_readfirstlane(*n_dev);
+        if ((int)blockIdx.x * NB >= n) return;
+    }
     using G = FX<NB>;
     constexpr int ROWS = G::ROWS, MT = G::MT, ZR = G::ZR, RING = G::RING;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -498,16 +506,32 @@ int net_fx_upload(azr_engine* h, const float* fold_host)
     return AZR_OK;
 }
 
-int net_fx_forward(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
+// n_dev (optional): the batch size is read from that word of device memory by the launch itself and n is only its upper bound (the grid)
+static int fx_launch(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, const int* n_dev, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
 {
     FxNet* x = fx(h);
     const int wgs = (n + 1) / 2;
     if (h->pe_tower0) hipEventRecord(h->pe_tower0, st);
     hipLaunchKernelGGL(k_tower_fx<2>, dim3(wgs), dim3(THREADS), FX<2>::LDS_BYTES, st, d_in88, in_stride, n, h->net.stem_w, x->tower_wp, x->fold,
-                       h->net.blocks, net_head_params(h), d_pi, d_v, d_map);
+                       h->net.blocks, net_head_params(h), d_pi, d_v, d_map, n_dev);
     if (h->pe_tower1) hipEventRecord(h->pe_tower1, st);
     HIPCHK(h, hipGetLastError());
     return AZR_OK;
+}
+
+int net_fx_forward(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
+{
+    return fx_launch(h, d_in88, in_stride, n, nullptr, d_pi, d_v, d_map, st);
+}
+
+// A batch whose size only the device knows (net_forward_counted): one launch sized for n_max boards, no read-back.  The same bound as the
+// 16-bit towers' counted form (256 boards = 128 workgroups, all resident), so an arena's choice of form does not depend on the pairing.
+bool net_fx_counted_ok(azr_engine* h, int n_max) { return fx(h) && n_max >= 1 && n_max <= 256; }
+
+int net_fx_forward_counted(azr_engine* h, const uint8_t* d_in88, int in_stride, int n_max, const int* n_dev, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
+{
+    if (!net_fx_counted_ok(h, n_max) || !n_dev) { h->err = "net_fx_forward_counted: 1..256 boards and a device count"; return AZR_E_INVALID_ARGUMENT; }
+    return fx_launch(h, d_in88, in_stride, n_max, n_dev, d_pi, d_v, d_map, st);
 }
 
 }  // namespace azr

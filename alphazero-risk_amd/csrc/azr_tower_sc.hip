@@ -393,7 +393,8 @@ __global__ __launch_bounds__(THREADS) void k_tower_sc(const uint8_t* __restrict_
                                                        const float* __restrict__ fold, int blocks, const float* __restrict__ hp,
                                                        float* __restrict__ pi_out, float* __restrict__ v_out, const int* __restrict__ slot_map,
                                                        uint8_t* __restrict__ ex_base, uint32_t ex_bytes_total, unsigned* __restrict__ counters,
-                                                       unsigned spin_limit, int force_wt, const int* __restrict__ n_dev, unsigned tag, const int* __restrict__ n_other)
+                                                       unsigned spin_limit, int force_wt, const int* __restrict__ n_dev, unsigned tag, const int* __restrict__ n_other,
+                                                       int other_wgpp)
 {
     // n_dev != null: the batch size is a word in device memory (written by the tree step ahead of this launch in stream order; the grid
     // was sized for the largest batch).  More boards than this kernel takes: the give-up word is raised with the value 2 — the guarded
@@ -403,14 +404,21 @@ __global__ __launch_bounds__(THREADS) void k_tower_sc(const uint8_t* __restrict_
     // measured again in the arena's trace, profiles/r04_arena_passes.txt: 0.66 ms for the second of two 100-board launches).  So both
     // launches take this kernel only if their workgroups fit the 256 CUs together; else both go one board per workgroup (letting the
     // smaller batch keep this kernel beside the larger one's one-board workgroups measured slower: it slows the larger, which the pass
-    // waits for).  Both launches evaluate the same rule on the same two words.
+    // waits for).  The other launch need not be this kernel: other_wgpp = what a board pair of ITS batch is charged with (the host takes it
+    // from the other handle's plan, net_counted_wgs_per_pair: CGN for k_tower_sc), so two launches of this kernel still evaluate one rule
+    // on the same two words and come to the same answer, and beside a tower that has one form only this launch decides for itself alone.
+    // Beside k_tower_fx<2> (NET_F32X: ONE workgroup per board pair) both choices were measured — 100 games bf16 against f32x, 20 blocks,
+    // 100 simulations, T = 2, two runs each in one visit (profiles/mixed_arena.txt): charged with its 1 workgroup per pair, i.e. split
+    // channels while 4 * pairs_n + 1 * pairs_m <= 256: 16.74 / 16.74 s; charged with the whole chip (CUS), i.e. one board per workgroup
+    // whenever the F32X net has a leaf in the pass: 15.88 / 15.92 s.  The pass waits for the F32X launch, which runs about 3.5 times as
+    // long, so the shorter launch gains nothing from its faster form and the arena measures slower with it: the plan charges CUS.
     if (n_dev) {
         n = __builtin_amdgcn_readfirstlane(*n_dev);
         pairs = (n + 1) / 2;
         bool here = n <= 2 * MAX_PAIRS;
         if (here && n_other) {
             const int m = __builtin_amdgcn_readfirstlane(*n_other);
-            const int wg_n = CGN * ((n + 1) / 2), wg_m = CGN * ((m + 1) / 2);
+            const int wg_n = CGN * ((n + 1) / 2), wg_m = other_wgpp * ((m + 1) / 2);
             if (m > 0 && wg_n + wg_m > CUS) here = false;
         }
         if (!here) {
@@ -513,9 +521,14 @@ void tower_sc_free(azr_engine* h)
 // the whole net for n <= 128 boards in one persistent launch of 4 workgroups per board pair.  The caller queues the guarded
 // one-board-per-workgroup launch right behind it (net_bf16_forward): if a hand-off of this launch gave up, that one recomputes the batch.
 // n_dev != null: the batch size is read from that word of device memory by the launch itself and n is only its upper bound (the grid);
-// n_other (optional): the batch-size word of another network's launch running beside this one (see the kernel).
+// n_other (optional): the batch-size word of another network's launch running beside this one, other_wgpp = that launch's workgroups per
+// board pair (see the kernel).
+int tower_sc_wgs_per_pair() { return CGN; }
+// ... and the charge under which any leaf of the other launch sends this tower to one board per workgroup (see the kernel)
+int tower_sc_whole_chip() { return CUS; }
+
 int tower_sc_launch(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st,
-                    const int* n_dev, const int* n_other)
+                    const int* n_dev, const int* n_other, int other_wgpp)
 {
     if (n_dev && n > 2 * MAX_PAIRS) n = 2 * MAX_PAIRS;
     if (n < 1 || n > 2 * MAX_PAIRS) { h->err = "tower_sc_launch: 1..128 boards"; return AZR_E_INVALID_ARGUMENT; }
@@ -531,10 +544,10 @@ int tower_sc_launch(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, 
     const unsigned tag = x->sc_tag;
     if (x->f16)
         hipLaunchKernelGGL(k_tower_sc<true>, dim3(wgs), dim3(THREADS), LDS_BYTES, st, d_in88, in_stride, n, pairs, x->stem_wp, x->tower_wp, tower_bytes, (const float*)x->fold16, B,
-                           net_head_params(h), d_pi, d_v, d_map, reinterpret_cast<uint8_t*>(x->sc_ex), ex_bytes, x->sc_counters, x->sc_spin_limit, x->sc_force_wt, n_dev, tag, n_other);
+                           net_head_params(h), d_pi, d_v, d_map, reinterpret_cast<uint8_t*>(x->sc_ex), ex_bytes, x->sc_counters, x->sc_spin_limit, x->sc_force_wt, n_dev, tag, n_other, other_wgpp);
     else
         hipLaunchKernelGGL(k_tower_sc<false>, dim3(wgs), dim3(THREADS), LDS_BYTES, st, d_in88, in_stride, n, pairs, x->stem_wp, x->tower_wp, tower_bytes, net_fold(h), B,
-                           net_head_params(h), d_pi, d_v, d_map, reinterpret_cast<uint8_t*>(x->sc_ex), ex_bytes, x->sc_counters, x->sc_spin_limit, x->sc_force_wt, n_dev, tag, n_other);
+                           net_head_params(h), d_pi, d_v, d_map, reinterpret_cast<uint8_t*>(x->sc_ex), ex_bytes, x->sc_counters, x->sc_spin_limit, x->sc_force_wt, n_dev, tag, n_other, other_wgpp);
     HIPCHK(h, hipGetLastError());
     return AZR_OK;
 }

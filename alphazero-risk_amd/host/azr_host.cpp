@@ -91,6 +91,8 @@ void Settings::init(int argc, char* argv[])
         {"s", "Number of stored samples", std::to_string(SAMPLES_STORAGE_MIN), false},
         {"blocks", "[this build] residual blocks of the net (reference: compile-time BLOCKS)", std::to_string(BLOCKS), false},
         {"dtype", "[this build] net arithmetic bf16|f16|f32x|f32 (f32x = fp32-equivalent on the MFMA)", NET_DTYPE, false},
+        {"blocks2", "[this build] residual blocks of player 2's net in -m play --p1 az --p2 az (if not --blocks, --c2 defaults to checkpoints/latest-checkpoint-N-blocks.bin)", "--blocks", false},
+        {"dtype2", "[this build] arithmetic of player 2's net in -m play --p1 az --p2 az", "--dtype", false},
         {"seed", "[this build] base seed of the per-game RNG streams", std::to_string(BASE_SEED), false},
         {"devices", "[this build] HIP device of every logical gpu, comma separated (default 0,1,..; \"0,0\" rehearses --gpus 2 on one card)", "", false},
         {"pair-halves", "[this build] mirrored pairs: 1 = both games of a pair at the same time on two slots, 0 = one after the other on one slot", std::to_string(CONCURRENT_PAIR_HALVES), true},
@@ -168,6 +170,21 @@ void Settings::init(int argc, char* argv[])
     SAMPLES_STORAGE_MIN = atoi(get("s").c_str());
     BLOCKS = atoi(get("blocks").c_str());
     NET_DTYPE = get("dtype");
+    // player 2's net: what --blocks / --dtype say unless given (the settings file then carries the value in force, not the word "--blocks")
+    if (!given.count("blocks2")) val["blocks2"] = get("blocks");
+    if (!given.count("dtype2")) val["dtype2"] = get("dtype");
+    BLOCKS2 = atoi(val["blocks2"].c_str());
+    NET_DTYPE2 = val["dtype2"];
+    // A checkpoint holds the fp32 parameters of ONE depth, and --c1 / --c2 default to the same file: a player 2 of another depth whose
+    // checkpoint was not named gets a default of its own (a missing checkpoint is initialised and saved, as for every net)
+    if (BLOCKS2 != BLOCKS && !given.count("c2")) {
+        CHECKPOINT_2 = DEFAULT_CHECKPOINT_DIR + "/latest-checkpoint-" + std::to_string(BLOCKS2) + "-blocks.bin";
+        val["c2"] = CHECKPOINT_2;
+    }
+    if (NET_DTYPE2 != "bf16" && NET_DTYPE2 != "f16" && NET_DTYPE2 != "f32x" && NET_DTYPE2 != "f32") {
+        fprintf(stderr, "--dtype2: unknown net arithmetic '%s' (bf16|f16|f32x|f32)\n", NET_DTYPE2.c_str());
+        exit(2);
+    }
     BASE_SEED = (uint32_t)strtoul(get("seed").c_str(), nullptr, 10);
     CONCURRENT_PAIR_HALVES = parse_bool(get("pair-halves"));
     CV_K = atoi(get("cvk").c_str());
@@ -185,7 +202,7 @@ void Settings::init(int argc, char* argv[])
     // `--lnt` and `--apbs` are parsed and never applied in the reference either
     mkdirs("log");
     std::ofstream out("log/settings.txt", std::ofstream::out);
-    for (auto& o : opts) out << o.name << "(" << o.desc << ")=" << (given.count(o.name) ? val[o.name] : o.def) << std::endl;
+    for (auto& o : opts) out << o.name << "(" << o.desc << ")=" << (val.count(o.name) ? val[o.name] : o.def) << std::endl;
 }
 
 void Settings::toEngine(azr_settings& s, int device) const
@@ -194,7 +211,7 @@ void Settings::toEngine(azr_settings& s, int device) const
     s.device = device;
     s.games = NUMBER_OF_CONCURENT_GAMES_PER_GPU;
     s.blocks = BLOCKS;
-    s.net_dtype = NET_DTYPE == "f32" ? AZR_NET_F32 : NET_DTYPE == "f32x" ? AZR_NET_F32X : NET_DTYPE == "f16" ? AZR_NET_F16 : AZR_NET_BF16;
+    s.net_dtype = netDtype(NET_DTYPE);
     s.mcts_simulations = MCTS_SIMULATIONS;
     s.mcts_threads = std::max(1, std::min(8, THREADS_PER_MCTS));
     s.allow_yield = ALLOW_YIELD;
@@ -206,6 +223,11 @@ void Settings::toEngine(azr_settings& s, int device) const
     s.hp_exploration = HP_EXPLORATION;
     s.dir_noise_value = DIR_NOISE_VALUE;
     s.dir_noise_epsi = DIR_NOISE_EPSI;
+}
+
+int Settings::netDtype(const std::string& name)
+{
+    return name == "f32" ? AZR_NET_F32 : name == "f32x" ? AZR_NET_F32X : name == "f16" ? AZR_NET_F16 : AZR_NET_BF16;
 }
 
 std::string Settings::describe() const
@@ -314,6 +336,20 @@ Engine::Engine(const Settings& s, int device, int g) : games(g)
     int rc = azr_engine_create(&es, &h);
     if (rc) {
         std::string msg = azr_last_error(nullptr);   // *out is NULL on failure; the reason is kept per thread
+        h = nullptr;
+        throw std::runtime_error("engine: " + msg);
+    }
+}
+Engine::Engine(const Settings& s, int device, int g, int blocks, const std::string& dtype) : games(g)
+{
+    azr_settings es;
+    s.toEngine(es, device);
+    es.games = g;
+    es.blocks = blocks;
+    es.net_dtype = Settings::netDtype(dtype);
+    int rc = azr_engine_create(&es, &h);
+    if (rc) {
+        std::string msg = azr_last_error(nullptr);
         h = nullptr;
         throw std::runtime_error("engine: " + msg);
     }
@@ -492,15 +528,15 @@ void AlphaZeroNNGroup::train(const std::vector<NNTrainData>& trainData, int epoc
     for (size_t i = 1; i < neuralNetworkIds.size(); i++) neuralNetworkIds[i]->loadCheckpoint(SETTINGS.DEFAULT_CHECKPOINT_TEMP);
 }
 
-std::shared_ptr<AlphaZeroNNGroup> AlphaZeroCluster::initPlayerGroup(const std::string& name, const std::string& graphPath)
+std::shared_ptr<AlphaZeroNNGroup> AlphaZeroCluster::initPlayerGroup(const std::string& name, const std::string& graphPath, int blocks, const std::string& dtype)
 {
     for (auto& g : groups)
         if (g->name == name) throw std::invalid_argument("Duplicated player group");  // alphazero_gpu_cluster.cpp:160-163
-    (void)graphPath;  // the TF graph-def is not used: the net is built into the HIP library (blocks = --blocks)
+    (void)graphPath;  // the TF graph-def is not used: the net is built into the HIP library, its shape is `blocks` / `dtype`
     auto grp = std::make_shared<AlphaZeroNNGroup>();
     grp->name = name;
     for (int gpu = 0; gpu < gpus; gpu++) {
-        auto eng = std::make_shared<Engine>(SETTINGS, SETTINGS.deviceOf(gpu), SETTINGS.NUMBER_OF_CONCURENT_GAMES_PER_GPU);
+        auto eng = std::make_shared<Engine>(SETTINGS, SETTINGS.deviceOf(gpu), SETTINGS.NUMBER_OF_CONCURENT_GAMES_PER_GPU, blocks, dtype);
         grp->neuralNetworkIds.push_back(std::make_shared<AlphaZeroNNId>(eng, gpu));
     }
     groups.push_back(grp);

@@ -24,7 +24,8 @@ namespace azrhost {
 
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
-// `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype.
+// `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2 for
+// player 2's net in `-m play --p1 az --p2 az`), the others marked "[this build]" in --help.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:
@@ -65,6 +66,8 @@ public:
     // this build
     int BLOCKS = 20;              // CMakeLists.txt:15 `set(BLOCKS 20)` is compile-time in the reference
     std::string NET_DTYPE = "bf16";
+    int BLOCKS2 = 20;             // --blocks2 / --dtype2: the net of player 2's group in `-m play --p1 az --p2 az` (default: --blocks / --dtype)
+    std::string NET_DTYPE2 = "bf16";
     uint32_t BASE_SEED = 20260001;
     std::vector<int> DEVICE_MAP;         // --devices: HIP device of logical gpu i (empty = i); "0,0" rehearses --gpus 2 on one card
     bool CONCURRENT_PAIR_HALVES = true;  // --pair-halves: the two games of a mirrored pair on two slots at the same time (AZR_MIRROR_CONCURRENT)
@@ -77,6 +80,7 @@ public:
     int getNumberOfPlayers() const { return NUMBER_OF_GPUS * NUMBER_OF_CONCURENT_GAMES_PER_GPU; }
     void init(int argc, char* argv[]);   // parses every flag of SURVEY App-G; exits on -h/--help
     void toEngine(azr_settings& s, int device) const;
+    static int netDtype(const std::string& name);   // bf16|f16|f32x|f32 -> AZR_NET_*; anything else is an error
     std::string describe() const;
 };
 extern Settings SETTINGS;
@@ -141,6 +145,7 @@ public:
     azr_engine* h = nullptr;
     int games = 0;
     Engine(const Settings& s, int device, int games);
+    Engine(const Settings& s, int device, int games, int blocks, const std::string& dtype);   // a net shape other than s.BLOCKS / s.NET_DTYPE
     ~Engine();
     void check(int rc, const char* what) const;
 };
@@ -179,7 +184,8 @@ public:
     int gpus = 0;
     std::vector<std::shared_ptr<AlphaZeroNNGroup>> groups;
     void initGpus(int n) { gpus = n; }
-    std::shared_ptr<AlphaZeroNNGroup> initPlayerGroup(const std::string& name, const std::string& graphPath);
+    // blocks / dtype: the shape of the group's net (the reference names a graph file per group; here the net is built in)
+    std::shared_ptr<AlphaZeroNNGroup> initPlayerGroup(const std::string& name, const std::string& graphPath, int blocks, const std::string& dtype);
 };
 
 // ------------------------------------------------------------------------------------------------------------------

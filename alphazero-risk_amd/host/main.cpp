@@ -13,9 +13,9 @@ static void executeTrain()
 {
     auto cluster = std::make_shared<AlphaZeroCluster>();
     cluster->initGpus(SETTINGS.NUMBER_OF_GPUS);
-    auto trainGroup = cluster->initPlayerGroup("az_train", SETTINGS.GRAPH_DEF_PB_1);
+    auto trainGroup = cluster->initPlayerGroup("az_train", SETTINGS.GRAPH_DEF_PB_1, SETTINGS.BLOCKS, SETTINGS.NET_DTYPE);
     trainGroup->loadCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
-    auto generateGroup = cluster->initPlayerGroup("az_generate", SETTINGS.GRAPH_DEF_PB_1);
+    auto generateGroup = cluster->initPlayerGroup("az_generate", SETTINGS.GRAPH_DEF_PB_1, SETTINGS.BLOCKS, SETTINGS.NET_DTYPE);
     generateGroup->loadCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
     AlphaZeroTrainer trainer;
     trainer.train(trainGroup, generateGroup);
@@ -44,11 +44,11 @@ static void executePlay()
     const int k1 = playerKind(SETTINGS.PLAYER_1), k2 = playerKind(SETTINGS.PLAYER_2);
     auto cluster = std::make_shared<AlphaZeroCluster>();
     cluster->initGpus(SETTINGS.NUMBER_OF_GPUS);
-    auto group = cluster->initPlayerGroup("az1", SETTINGS.GRAPH_DEF_PB_1);
+    auto group = cluster->initPlayerGroup("az1", SETTINGS.GRAPH_DEF_PB_1, SETTINGS.BLOCKS, SETTINGS.NET_DTYPE);
     if (k1 == AZR_PLAYER_ALPHAZERO) group->loadCheckpoint(SETTINGS.CHECKPOINT_1);
     else if (k2 == AZR_PLAYER_ALPHAZERO) group->loadCheckpoint(SETTINGS.CHECKPOINT_2);
     if (k1 == AZR_PLAYER_ALPHAZERO && k2 == AZR_PLAYER_ALPHAZERO) {  // two AlphaZeroPlayers, each with its checkpoint
-        auto group2 = cluster->initPlayerGroup("az2", SETTINGS.GRAPH_DEF_PB_2);
+        auto group2 = cluster->initPlayerGroup("az2", SETTINGS.GRAPH_DEF_PB_2, SETTINGS.BLOCKS2, SETTINGS.NET_DTYPE2);
         group2->loadCheckpoint(SETTINGS.CHECKPOINT_2);
         executePlayAzVsAz(group, group2);
         return;
@@ -89,9 +89,9 @@ static void executeTrainWithout(bool script)
 {
     auto cluster = std::make_shared<AlphaZeroCluster>();
     cluster->initGpus(SETTINGS.NUMBER_OF_GPUS);
-    auto trainGroup = cluster->initPlayerGroup("az_train", SETTINGS.GRAPH_DEF_PB_1);
+    auto trainGroup = cluster->initPlayerGroup("az_train", SETTINGS.GRAPH_DEF_PB_1, SETTINGS.BLOCKS, SETTINGS.NET_DTYPE);
     trainGroup->loadCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
-    auto generateGroup = cluster->initPlayerGroup("az_generate", SETTINGS.GRAPH_DEF_PB_1);
+    auto generateGroup = cluster->initPlayerGroup("az_generate", SETTINGS.GRAPH_DEF_PB_1, SETTINGS.BLOCKS, SETTINGS.NET_DTYPE);
     generateGroup->loadCheckpoint(SETTINGS.DEFAULT_LATEST_CHECKPOINT);
     AlphaZeroTrainer trainer;
     if (script) trainer.trainOnScript(trainGroup, generateGroup);

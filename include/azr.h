@@ -259,9 +259,9 @@ int azr_arena_start(azr_engine* h, int player1, int player2, int games, int game
 int azr_arena_run(azr_engine* h, int passes, int* finished_out);
 /* New-vs-old arena (GameGroup::playGames(trainAZPG, generateAZPG, ...), alphazero_trainer.cpp:147-152): player
  * AZR_PLAYER_ALPHAZERO_B searches a tree of its own in every slot (every AlphaZeroPlayer owns an AlphaZeroMCTS) and is
- * evaluated by `other`'s network (same device, same net shape; `other` may be h itself; its weights are used in place,
- * so keep `other` alive and pass NULL here before destroying it).  Each pass runs the two networks on the leaves of
- * their own players only. */
+ * evaluated by `other`'s network (same device, at least h's leaf slots; its blocks and net_dtype may differ from h's;
+ * `other` may be h itself; its weights are used in place, so keep `other` alive and pass NULL here before destroying
+ * it).  Each pass runs the two networks on the leaves of their own players only. */
 int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other);
 /* INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES (alphazero_trainer.cpp:143-146): AlphaZero players push (s, pi) at every decision
  * (alphazero_player.cpp:15-18); a finished game's records get their z and go to the record ring (azr_samples_drain),

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Time the new-vs-old arena of the learn loop (GameGroup::playGames with two AlphaZero players, two networks) on the
-device: `games` mirrored games on `slots` engine slots, S simulations per move, THREADS_PER_MCTS T, B blocks, bf16.
-    python tools/arena_bench.py [--games 100] [--slots 128] [--sims 100] [--threads 2] [--blocks 20]"""
+device: `games` mirrored games on `slots` engine slots, S simulations per move, THREADS_PER_MCTS T, B blocks, bf16 — or, with
+--blocks-b / --dtype-b, an opponent net of another depth and / or arithmetic (random-init nets: a timing, not a strength).
+    python tools/arena_bench.py [--games 100] [--slots 128] [--sims 100] [--threads 2] [--blocks 20] [--dtype bf16]
+                                [--blocks-b N] [--dtype-b bf16|f16|f32x|f32]
+AZR_EXP_LIB=<library>: time that build of the same sources instead (e.g. libazr_hip_test.so with one of its environment hooks)."""
 import argparse
 import importlib
 import os
@@ -12,6 +15,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 P = importlib.import_module("alphazero-risk_amd")
 if os.environ.get("AZR_EXP_LIB"):   # a timing-experiment build of the same sources (never the product library)
     P.binding.lib_path = lambda test_hooks=False: os.environ["AZR_EXP_LIB"]
+DTYPES = {"bf16": P.NET_BF16, "f16": P.NET_F16, "f32x": P.NET_F32X, "f32": P.NET_F32}
 
 
 def main():
@@ -21,10 +25,15 @@ def main():
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--threads", type=int, default=2)
     ap.add_argument("--blocks", type=int, default=20)
+    ap.add_argument("--dtype", default="bf16", choices=sorted(DTYPES))
+    ap.add_argument("--blocks-b", type=int, default=None, help="residual blocks of the opponent handle's net (default: --blocks)")
+    ap.add_argument("--dtype-b", default=None, choices=sorted(DTYPES), help="arithmetic of the opponent handle's net (default: --dtype)")
     ap.add_argument("--pair-halves", type=int, default=1, help="1: a mirrored pair's two games at the same time on two slots; 0: one after the other on one slot")
     a = ap.parse_args()
-    new = P.Engine(a.slots, blocks=a.blocks, sims=a.sims, dtype=P.NET_BF16, threads=a.threads)
-    old = P.Engine(a.slots, blocks=a.blocks, sims=a.sims, dtype=P.NET_BF16, threads=a.threads)
+    blocks_b = a.blocks if a.blocks_b is None else a.blocks_b
+    dtype_b = a.dtype if a.dtype_b is None else a.dtype_b
+    new = P.Engine(a.slots, blocks=a.blocks, sims=a.sims, dtype=DTYPES[a.dtype], threads=a.threads)
+    old = P.Engine(a.slots, blocks=blocks_b, sims=a.sims, dtype=DTYPES[dtype_b], threads=a.threads)
     new.init_random(1)
     old.init_random(2)
     new.arena_set_opponent(old)
@@ -34,7 +43,8 @@ def main():
         pass
     dt = time.time() - t0
     r = new.arena_results()
-    print(f"{a.games} games on {a.slots} slots, S={a.sims} T={a.threads} B={a.blocks}: {dt:.1f} s, results {r}", flush=True)
+    print(f"{a.games} games on {a.slots} slots, S={a.sims} T={a.threads} {a.dtype} B={a.blocks} vs {dtype_b} B={blocks_b}: {dt:.2f} s, results {r}, "
+          f"tower_fallbacks {new.counters()['tower_fallbacks']}", flush=True)
 
 
 if __name__ == "__main__":
