@@ -82,7 +82,7 @@ EXPORTS = [
     "azr_mcts_apply", "azr_mcts_root_stats", "azr_mcts_policy", "azr_mcts_pick", "azr_selfplay_start", "azr_selfplay_start_games", "azr_selfplay_start_from_states",
     "azr_selfplay_run", "azr_selfplay_counters", "azr_samples_drain", "azr_samples_device_view", "azr_samples_copy_device", "azr_profile_last_run",
     "azr_device_synchronize", "azr_debug_tower_clock", "azr_debug_tower_trace", "azr_debug_tower_plan", "azr_arena_start", "azr_arena_run", "azr_arena_results", "azr_arena_log",
-    "azr_arena_set_opponent_net", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
+    "azr_arena_set_opponent_net", "azr_arena_set_opponent_search", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
 ]
 
 
@@ -144,6 +144,7 @@ def load_library(test_hooks=False):
         L.azr_arena_start.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         L.azr_arena_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.azr_arena_set_opponent_net.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_arena_set_opponent_search.argtypes = [C.c_void_p, C.c_int, C.c_float]
         L.azr_arena_collect_samples.argtypes = [C.c_void_p, C.c_int]
         L.azr_arena_collect_scripted_samples.argtypes = [C.c_void_p, C.c_int]
         L.azr_arena_results.argtypes = [C.c_void_p, C.c_void_p]
@@ -473,6 +474,12 @@ class Engine:
         with a NET_F32 side reads the leaf counts back every pass."""
         self._chk(self.L.azr_arena_set_opponent_net(self.h, other.h if other is not None else None))
         self._opponent = other   # keep it alive
+
+    def arena_set_opponent_search(self, sims=None, hp=None):
+        """the search budget of PLAYER_ALPHAZERO_B: its simulations per decision and its PUCT constant (None = this Engine's own).  Holds
+        until it is set again or arena_set_opponent(None); refused while an arena runs, below `threads`, and above what the node pool
+        holds (16 * (sims + 1) nodes: create the Engine with node_capacity for the larger of the two budgets)."""
+        self._chk(self.L.azr_arena_set_opponent_search(self.h, -1 if sims is None else int(sims), -1.0 if hp is None else float(hp)))
 
     def arena_collect_samples(self, on=True):
         self._chk(self.L.azr_arena_collect_samples(self.h, int(on)))

@@ -361,11 +361,11 @@ enum : int { RD_DONE = 0, RD_LEAF = 1, RD_FAIL = 2 };
 // AlphaZeroMCTS::threadSimulateJob + search (alphazero_mcts.cpp:310-377) for search thread `th`, iteratively: claim the
 // next simulation from the counter and descend from the root, repeated until the counter is exhausted (RD_DONE), a leaf
 // needs the net (RD_LEAF: leaf record written to slot g * T + th, pending bit set) or a rule error (RD_FAIL).
-__device__ __forceinline__ int run_descents(const Dev& E, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
+// `S`: the settings of the tree that is searching (the arena's player B may carry its own budget and PUCT constant).
+__device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
                                             StepCount& k, uint32_t& err_out)
 {
     const Rules R = E.rules;
-    const Search S = E.search;
     const Tree t = thread_tree(t0, th);
     const size_t slot = (size_t)g * E.T + th;
     while ((int)c.sims_started < S.simulations) {
@@ -440,12 +440,12 @@ __device__ __forceinline__ int run_descents(const Dev& E, int g, const Tree& t0,
 // One round of AlphaZeroMCTS::simulate for all T search threads of the game, in thread order: every thread without a
 // pending leaf runs descents until it blocks on the net.  RD_LEAF = at least one leaf is waiting; RD_DONE = the counter
 // is exhausted and every claimed simulation is backed up.
-__device__ __forceinline__ int search_round(const Dev& E, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
+__device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
                                             StepCount& k, uint32_t& err_out)
 {
     for (int th = 0; th < E.T; th++) {
         if ((c.pending >> th) & 1u) continue;
-        int r = run_descents(E, g, t, th, c, root, scratch, k, err_out);
+        int r = run_descents(E, S, g, t, th, c, root, scratch, k, err_out);
         if (r == RD_FAIL) { c.pending = 0; return RD_FAIL; }
         if (r == RD_LEAF && plen_get(c, th) == 0) break;  // root expansion: the threads start after setRootState
     }
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             TP(14);
         }
         uint32_t err = 0;
-        int r = search_round(E, g, t, c, root, scratch, k, err);
+        int r = search_round(E, S, g, t, c, root, scratch, k, err);
         if (r == RD_LEAF) break;
         if (r == RD_FAIL) {
             k.err++;
@@ -632,7 +632,6 @@ __device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
     const unsigned long long cnt0 = counters_begin(E, g);
     Tree t = tree_of(E, g);
     const Rules R = E.rules;
-    const Search S = E.search;
     WS root;
     ws_load(root, E.state + (size_t)g * GREC);
     root.rng = c.rng;
@@ -774,7 +773,11 @@ __device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
             c.search_tree = w;
             c.rng = root.rng;
             uint32_t err = 0;
-            int r = search_round(E, g, tt, c, root, scratch, k, err);
+            // every AlphaZeroPlayer owns an AlphaZeroMCTS with its own Settings: player B's simulation count and PUCT constant
+            // (azr_arena_set_opponent_search); the noise term is shared
+            Search Sw = E.search;
+            if (w) { Sw.simulations = E.search2_simulations; Sw.hp = E.search2_hp; }
+            int r = search_round(E, Sw, g, tt, c, root, scratch, k, err);
             root.rng = c.rng;
             if (r == RD_LEAF) { if (w) swap_tree_ctl(c, x2); break; }
             if (r == RD_FAIL) { fail = true; root.err = err; }
@@ -1048,6 +1051,8 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     d.search.c2 = s->dir_noise_epsi * s->dir_noise_value;
     d.search.hp = s->hp_exploration;
     d.search.temperature_threshold = s->temperature_threshold;
+    d.search2_simulations = d.search.simulations;   // player B of a two-net arena: this handle's own until azr_arena_set_opponent_search
+    d.search2_hp = d.search.hp;
     const size_t G = d.G, GT = G * d.T;
     HIPCHK(h, dmalloc(&d.state, G * GREC));
     HIPCHK(h, dmalloc(&d.ctl, G));
@@ -1645,6 +1650,9 @@ extern "C" int azr_arena_start(azr_engine* h, int player1, int player2, int game
         return AZR_E_STATE;
     }
     Dev& d = h->d;
+    // player B's search settings as they stand now: a running arena never sees a later change
+    d.search2_simulations = h->opp_simulations >= 0 ? h->opp_simulations : d.search.simulations;
+    d.search2_hp = h->opp_hp >= 0 ? h->opp_hp : d.search.hp;
     d.nodes2 = usesB ? h->tree2[0] ? (uint8_t*)h->tree2[0] : nullptr : nullptr;
     h->arena_rec = h->arena_script;
     if (d.arena_collect || h->arena_rec) HIPCHK(h, hipMemsetAsync(d.ring_count, 0, 2 * sizeof(unsigned long long), h->stream));
@@ -1659,6 +1667,7 @@ extern "C" int azr_arena_start(azr_engine* h, int player1, int player2, int game
     HIPCHK(h, hipMemsetAsync(d.alog_status, 0, (size_t)d.G * ALOG, h->stream));
     LAUNCH(h, k_arena_start, d);
     SYNC(h);
+    h->arena_open = true;
     return AZR_OK;
 }
 
@@ -1766,6 +1775,7 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
     SYNC(h);
     int idle = 0;
     for (uint32_t v : st) idle += v == 2;
+    if (idle == h->d.G) h->arena_open = false;
     if (finished_out) *finished_out = idle == h->d.G;
     return AZR_OK;
 }
@@ -1773,7 +1783,12 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
 extern "C" int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other)
 {
     ENTER(h);
-    if (!other) { h->opponent = nullptr; return AZR_OK; }
+    if (!other) {
+        h->opponent = nullptr;
+        h->opp_simulations = -1;   // azr_arena_set_opponent_search's setting goes with the opponent (read by the next azr_arena_start)
+        h->opp_hp = -1.0f;
+        return AZR_OK;
+    }
     // Depth and element type are the opponent's own business: its launches run with its own weights, context and activation buffers on
     // this handle's leaves (96-byte NNInputData in, fp32 pi / v out — the same for every tower).  Its buffers must hold this handle's batch.
     if (other->cfg.device != h->cfg.device || other->d.G * other->d.T < h->d.G * h->d.T) {
@@ -1797,6 +1812,38 @@ extern "C" int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other)
         SYNC(h);
     }
     h->opponent = other;
+    return AZR_OK;
+}
+
+extern "C" int azr_arena_set_opponent_search(azr_engine* h, int mcts_simulations, float hp_exploration)
+{
+    ENTER(h);
+    if (h->mode == 3 && h->arena_open) {
+        h->err = "azr_arena_set_opponent_search: an arena is running (set it before azr_arena_start or after the arena has finished)";
+        return AZR_E_STATE;
+    }
+    if (hp_exploration != hp_exploration) { h->err = "azr_arena_set_opponent_search: hp_exploration is not a number"; return AZR_E_INVALID_ARGUMENT; }
+    const int T = h->d.T;
+    int sims = -1;
+    if (mcts_simulations >= 0) {
+        if (mcts_simulations < T) {   // count = S - S % T would be 0, as at azr_engine_create
+            h->err = "azr_arena_set_opponent_search: mcts_simulations = " + std::to_string(mcts_simulations) + " < mcts_threads = " +
+                     std::to_string(T) + " (S - S % T simulations would be none)";
+            return AZR_E_INVALID_ARGUMENT;
+        }
+        // player B's tree lives in this handle's second node pool, sized like the first: a budget the pool was not made for would
+        // drop expansions.  Refused, not clamped.
+        const long long want_nodes = 16ll * ((long long)mcts_simulations + 1);
+        if (want_nodes > (long long)h->d.C) {
+            h->err = "azr_arena_set_opponent_search: mcts_simulations = " + std::to_string(mcts_simulations) + " needs a node pool of 16 * (" +
+                     std::to_string(mcts_simulations) + " + 1) = " + std::to_string(want_nodes) + " nodes per game, this handle's holds " +
+                     std::to_string(h->d.C) + ": create the handle with a larger node_capacity";
+            return AZR_E_INVALID_ARGUMENT;
+        }
+        sims = mcts_simulations - mcts_simulations % T;   // alphazero_mcts.cpp:265, per player
+    }
+    h->opp_simulations = sims;   // azr_arena_start hands them to the kernels
+    h->opp_hp = hp_exploration < 0 ? -1.0f : hp_exploration;
     return AZR_OK;
 }
 

@@ -47,6 +47,8 @@ struct Dev {
     int T;                 // THREADS_PER_MCTS: search threads (= leaf slots) per game; slot = g * T + k
     Rules rules;
     Search search;
+    int search2_simulations;   // two-net arena: player AZR_PLAYER_ALPHAZERO_B's simulations per decision and PUCT constant
+    float search2_hp;          // (azr_arena_set_opponent_search; the handle's own unless set).  Read by the arena step only.
     uint8_t* state;        // [G][64] game records
     Ctl* ctl;              // [G]
     uint8_t* nodes;        // [G][C][NODE_BYTES]
@@ -147,6 +149,9 @@ struct azr_engine {
     hipEvent_t arena_ev = nullptr;   // two-net arena: the opponent's net launch (on ITS stream) done -> this stream may go on
     bool arena_script = false;    // azr_arena_collect_scripted_samples
     bool arena_rec = false;       // ... as azr_arena_start found it: this arena's steps run k_arena_step_rec
+    bool arena_open = false;      // between azr_arena_start and the azr_arena_run that found every slot idle
+    int opp_simulations = -1;     // azr_arena_set_opponent_search: player B's count per decision and PUCT constant (< 0 = the handle's own);
+    float opp_hp = -1.0f;         // copied into d.search2_* by azr_arena_start
     bool sp_tail = false;         // quota self-play: no game is left to start, slots go idle -> compacted net batches
     void* train = nullptr;        // azr_train.hip: optimiser state + activation slabs, created by the first azr_nn_train*
     void* dp_comm = nullptr;      // azr_dp_init: this handle's RCCL communicator (ncclComm_t), rank and world

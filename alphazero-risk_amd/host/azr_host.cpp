@@ -93,6 +93,8 @@ void Settings::init(int argc, char* argv[])
         {"dtype", "[this build] net arithmetic bf16|f16|f32x|f32 (f32x = fp32-equivalent on the MFMA)", NET_DTYPE, false},
         {"blocks2", "[this build] residual blocks of player 2's net in -m play --p1 az --p2 az (if not --blocks, --c2 defaults to checkpoints/latest-checkpoint-N-blocks.bin)", "--blocks", false},
         {"dtype2", "[this build] arithmetic of player 2's net in -m play --p1 az --p2 az", "--dtype", false},
+        {"mcts2", "[this build] MCTS simulations of player 2 in -m play --p1 az --p2 az (a search budget per side)", "--mcts", false},
+        {"hp2", "[this build] exploration factor of player 2 in -m play --p1 az --p2 az", "--hp", false},
         {"seed", "[this build] base seed of the per-game RNG streams", std::to_string(BASE_SEED), false},
         {"devices", "[this build] HIP device of every logical gpu, comma separated (default 0,1,..; \"0,0\" rehearses --gpus 2 on one card)", "", false},
         {"pair-halves", "[this build] mirrored pairs: 1 = both games of a pair at the same time on two slots, 0 = one after the other on one slot", std::to_string(CONCURRENT_PAIR_HALVES), true},
@@ -185,6 +187,30 @@ void Settings::init(int argc, char* argv[])
         fprintf(stderr, "--dtype2: unknown net arithmetic '%s' (bf16|f16|f32x|f32)\n", NET_DTYPE2.c_str());
         exit(2);
     }
+    // player 2's search: what --mcts / --hp say unless given
+    SEARCH2_GIVEN = given.count("mcts2") || given.count("hp2");
+    if (!given.count("mcts2")) val["mcts2"] = get("mcts");
+    if (!given.count("hp2")) val["hp2"] = get("hp");
+    {
+        char* end = nullptr;
+        const long m2 = strtol(val["mcts2"].c_str(), &end, 10);
+        if (given.count("mcts2") && (val["mcts2"].empty() || *end != '\0' || m2 < 1 || m2 > 4094)) {
+            fprintf(stderr, "--mcts2: '%s' is not a simulation count (1..4094)\n", val["mcts2"].c_str());
+            exit(2);
+        }
+        MCTS_SIMULATIONS2 = (int)m2;
+        const int threads = std::max(1, std::min(8, THREADS_PER_MCTS));
+        if (given.count("mcts2") && MCTS_SIMULATIONS2 < threads) {   // S - S % T simulations would be none
+            fprintf(stderr, "--mcts2: %d simulations are fewer than the %d search threads (-t)\n", MCTS_SIMULATIONS2, threads);
+            exit(2);
+        }
+        const double h2 = strtod(val["hp2"].c_str(), &end);
+        if (given.count("hp2") && (val["hp2"].empty() || *end != '\0' || !(h2 >= 0.0))) {
+            fprintf(stderr, "--hp2: '%s' is not an exploration factor (a number >= 0)\n", val["hp2"].c_str());
+            exit(2);
+        }
+        HP_EXPLORATION2 = (float)h2;
+    }
     BASE_SEED = (uint32_t)strtoul(get("seed").c_str(), nullptr, 10);
     CONCURRENT_PAIR_HALVES = parse_bool(get("pair-halves"));
     CV_K = atoi(get("cvk").c_str());
@@ -223,6 +249,9 @@ void Settings::toEngine(azr_settings& s, int device) const
     s.hp_exploration = HP_EXPLORATION;
     s.dir_noise_value = DIR_NOISE_VALUE;
     s.dir_noise_epsi = DIR_NOISE_EPSI;
+    // player 2's tree lives in a pool of the same size as player 1's: make room for the larger of the two budgets
+    // (only where player 2 searches: -m play --p1 az --p2 az)
+    if (MODE == "play" && PLAYER_1 == "az" && PLAYER_2 == "az" && MCTS_SIMULATIONS2 > MCTS_SIMULATIONS) s.node_capacity = 16 * (MCTS_SIMULATIONS2 + 1);
 }
 
 int Settings::netDtype(const std::string& name)
@@ -721,7 +750,7 @@ std::ostream& operator<<(std::ostream& os, const GameResults& gr)  // game.cpp:2
 // moves the base seed (a compare / benchmark round must not replay the previous iteration's deals)
 static std::atomic<uint32_t> arenaCallCounter{0};
 
-GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup& pg2, int games, NNTrainDataStorage* tds)
+GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup& pg2, int games, NNTrainDataStorage* tds, int mcts2, float hp2)
 {
     const uint32_t arenaCallsBase = ++arenaCallCounter;
     // Device-resident arena: pg1's engine of GPU i runs the G slots, pg2's network of the same GPU plays
@@ -740,13 +769,15 @@ GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup
         const int share = 2 * (pairs / P + (i < pairs % P ? 1 : 0));
         if (share == 0) return;
         e.check(azr_arena_set_opponent_net(e.h, o.h), "arena_set_opponent_net");
+        if (mcts2 >= 0 || hp2 >= 0) e.check(azr_arena_set_opponent_search(e.h, mcts2, hp2), "arena_set_opponent_search");
         e.check(azr_arena_collect_samples(e.h, tds ? 1 : 0), "arena_collect_samples");
+        const int passes = 4 * (std::max(SETTINGS.MCTS_SIMULATIONS, mcts2) + 2);   // the larger of the two budgets
         e.check(azr_arena_start(e.h, AZR_PLAYER_ALPHAZERO, AZR_PLAYER_ALPHAZERO_B, share, 0, mirror,
                                 SETTINGS.BASE_SEED + 7919u * arenaCallsBase + (uint32_t)i * (1u << 24)), "arena_start");
         int fin = 0;
         std::vector<uint8_t> buf;
         while (!fin) {
-            e.check(azr_arena_run(e.h, 4 * (SETTINGS.MCTS_SIMULATIONS + 2), &fin), "arena_run");
+            e.check(azr_arena_run(e.h, passes, &fin), "arena_run");
             e.check(azr_arena_results(e.h, &res[i]), "arena_results");
             if (tds) {
                 buf.resize((size_t)e.games * 512 * AZR_RECORD_BYTES);

@@ -24,8 +24,8 @@ namespace azrhost {
 
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
-// `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2 for
-// player 2's net in `-m play --p1 az --p2 az`), the others marked "[this build]" in --help.
+// `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2,
+// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`), the others marked "[this build]" in --help.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:
@@ -68,6 +68,9 @@ public:
     std::string NET_DTYPE = "bf16";
     int BLOCKS2 = 20;             // --blocks2 / --dtype2: the net of player 2's group in `-m play --p1 az --p2 az` (default: --blocks / --dtype)
     std::string NET_DTYPE2 = "bf16";
+    int MCTS_SIMULATIONS2 = 32;   // --mcts2 / --hp2: the search of player 2 in `-m play --p1 az --p2 az` (default: --mcts / --hp)
+    float HP_EXPLORATION2 = 1.1f;
+    bool SEARCH2_GIVEN = false;   // one of the two was on the command line: executePlayAzVsAz sets player 2's search
     uint32_t BASE_SEED = 20260001;
     std::vector<int> DEVICE_MAP;         // --devices: HIP device of logical gpu i (empty = i); "0,0" rehearses --gpus 2 on one card
     bool CONCURRENT_PAIR_HALVES = true;  // --pair-halves: the two games of a mirrored pair on two slots at the same time (AZR_MIRROR_CONCURRENT)
@@ -250,7 +253,9 @@ std::ostream& operator<<(std::ostream& os, const GameResults& gr);
 // (alphazero_player.cpp:15-18,24-29), game by game.
 class GameGroup {
 public:
-    static GameResults playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup& pg2, int games, NNTrainDataStorage* tds = nullptr);
+    // mcts2 / hp2: player group 2's own simulations per decision and PUCT constant (azr_arena_set_opponent_search; < 0 = group 1's)
+    static GameResults playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup& pg2, int games, NNTrainDataStorage* tds = nullptr,
+                                 int mcts2 = -1, float hp2 = -1.0f);
     // `tds` (optional, train-script): both sides' records — the AlphaZero player's (s, pi) and the ScriptPlayer's / RandomPlayer's
     // one-hot moves (player.cpp:9-17) — game by game in move order (GameGroup::playGames(.., tds), game.cpp:256-275)
     static GameResults playGames(AlphaZeroPlayerGroup& pg1, int otherKind /* AZR_PLAYER_SCRIPT | RANDOM */, int games,

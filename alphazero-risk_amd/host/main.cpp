@@ -35,7 +35,10 @@ static int playerKind(const std::string& p)
 static void executePlayAzVsAz(std::shared_ptr<AlphaZeroNNGroup> group1, std::shared_ptr<AlphaZeroNNGroup> group2)
 {
     AlphaZeroPlayerGroup p1(group1), p2(group2);
-    GameResults gr = GameGroup::playGames(p1, p2, SETTINGS.COMPARE_GAMES);
+    // --mcts2 / --hp2: player 2's own search budget and PUCT constant; absent, both players search with --mcts / --hp
+    GameResults gr = SETTINGS.SEARCH2_GIVEN
+                         ? GameGroup::playGames(p1, p2, SETTINGS.COMPARE_GAMES, nullptr, SETTINGS.MCTS_SIMULATIONS2, SETTINGS.HP_EXPLORATION2)
+                         : GameGroup::playGames(p1, p2, SETTINGS.COMPARE_GAMES);
     printf("Games: %d\nDraws:%d\nPlayer 1:%d\nPlayer 2:%d\n", gr.count, gr.draw, gr.players[0].win, gr.players[1].win);
 }
 

@@ -263,6 +263,17 @@ int azr_arena_run(azr_engine* h, int passes, int* finished_out);
  * `other` may be h itself; its weights are used in place, so keep `other` alive and pass NULL here before destroying
  * it).  Each pass runs the two networks on the leaves of their own players only. */
 int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other);
+/* Search settings of player AZR_PLAYER_ALPHAZERO_B in this handle's arena: its simulations per decision and its PUCT
+ * constant (every AlphaZeroPlayer's AlphaZeroMCTS reads its own Settings).  mcts_simulations < 0 / hp_exploration < 0 = this
+ * handle's own (the state after azr_engine_create and after azr_arena_set_opponent_net(h, NULL)).  mcts_threads stays the
+ * handle's (leaf slot = g * T + k for both trees), so mcts_simulations >= mcts_threads and the count per decision is
+ * S - S % T.  Player B's tree lives in this handle's second node pool, which has the first one's size: a budget whose default
+ * pool 16 * (mcts_simulations + 1) exceeds it is AZR_E_INVALID_ARGUMENT (create the handle with a larger node_capacity).
+ * AZR_E_STATE between azr_arena_start and the arena's finish, i.e. the azr_arena_run that reports *finished_out = 1 (starting
+ * self-play or a host-stepped search ends an arena too).  azr_arena_start reads the setting: a running arena never sees a change,
+ * the reset through azr_arena_set_opponent_net(h, NULL) included.  The setting holds over later azr_arena_start calls until it is
+ * set again.  Player AZR_PLAYER_ALPHAZERO, self-play, the one-net arenas and azr_mcts_* keep the handle's settings. */
+int azr_arena_set_opponent_search(azr_engine* h, int mcts_simulations, float hp_exploration);
 /* INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES (alphazero_trainer.cpp:143-146): AlphaZero players push (s, pi) at every decision
  * (alphazero_player.cpp:15-18); a finished game's records get their z and go to the record ring (azr_samples_drain),
  * game by game in decision order (the reference appends player by player).  Set before azr_arena_start.  Its sibling
