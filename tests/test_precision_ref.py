@@ -187,3 +187,158 @@ def test_f16_edge_nets_pass_the_certificate():
     sub = (h > 0) & (h < 2.0 ** -14)
     print("subnormal: share of fp16 subnormals among the non-zero tower outputs %.2f" % (sub.sum() / (h > 0).sum()))
     assert sub.sum() >= 0.5 * (h > 0).sum()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# NET_F32X: the fp16-pair element (precision_ref.forward_fx, lattice_net_fx)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_pair_split_properties():
+    """hi = rne16(x), lo = rne16(x - hi) on random fp32 values over the fp16 range: hi + lo is exact in fp32; the pair is within
+    2^-22 |x| of x where lo is a normal fp16 number and within 2^-25 absolute where it is subnormal (or zero)"""
+    rng = np.random.default_rng(2)
+    x = (rng.standard_normal(400000) * np.exp2(rng.integers(-30, 15, 400000))).astype(np.float32)
+    x = x[np.abs(x) < 65504]
+    hi, lo = M.split_pair(x)
+    s64 = hi.astype(np.float64) + lo.astype(np.float64)
+    assert ((hi + lo).astype(np.float64) == s64).all()
+    err = np.abs(x.astype(np.float64) - s64)
+    normal = np.abs(lo) >= 2.0 ** -14
+    assert normal.sum() > 50000 and (~normal).sum() > 50000
+    assert (err[normal] <= 2.0 ** -22 * np.abs(x[normal]).astype(np.float64)).all()
+    assert (err[~normal] <= 2.0 ** -25).all()
+    assert (M.h2f(M.f2h(hi)) == hi).all() and (M.h2f(M.f2h(lo)) == lo).all()
+    sub = (lo != 0) & ~normal
+    assert sub.sum() > 10000 and (np.abs(lo[sub]) >= 2.0 ** -24).all()      # subnormal low parts keep their value
+
+
+@pytest.mark.parametrize("blocks", [1, 2])
+def test_pair_model_without_rounding_is_the_float64_graph(blocks):
+    flat = T.make_net_flat(blocks, seed=3, perturb_bn=True)
+    net = R.AzrNet(blocks, flat).double().eval()
+    x = golden_boards(16)
+    with torch.no_grad():
+        lg, rv = net(torch.from_numpy(R.planes_from_in88(x)).double())
+    rpi = torch.softmax(lg, 1).numpy()
+    pi, v, _ = M.forward_fx(flat, blocks, x, rounding=False)
+    assert np.abs(pi - rpi).max() <= 1e-12 and np.abs(v - rv.numpy()).max() <= 1e-12, np.abs(pi - rpi).max()
+
+
+def test_pair_model_on_a_dense_net():
+    """an ordinary dense net (Glorot weights, perturbed BN) at B = 2: the pair model is within 1e-5 of the plain float64 graph (a
+    sanity bound, not a claim: the kernel's own figure is 3e-6 at B = 20)"""
+    flat = T.make_net_flat(2, seed=3, perturb_bn=True)
+    x = golden_boards(16)
+    rpi, rv, _ = M.forward_fx(flat, 2, x, rounding=False)
+    pi, v, st = M.forward_fx(flat, 2, x)
+    d = max(np.abs(pi - rpi).max(), np.abs(v - rv).max())
+    print(f"pair model vs float64 graph, dense B=2: {d:.2e}; layer exponents {st['exps']}")
+    assert d <= 1e-5, d
+    p2, v2, _ = M.forward_fx(flat, 2, x, variant=dict(kind="with_al_wl"))
+    assert max(np.abs(p2 - rpi).max(), np.abs(v2 - rv).max()) <= 1e-5
+
+
+@pytest.mark.parametrize("blocks", [1, 2, 20])
+def test_fx_lattice_net_passes_the_certificate(blocks):
+    """lattice_net_fx on the whole pool of the GPU test: every output's terms (ah wh, al wh, ah wl) on one quantum with
+    sum |term| < 2^24 of it, every fma and shortcut add exact in float64"""
+    flat, x, pi, v, st = M.fx_pool(blocks)
+    r = max(l["ratio"] for l in st["layers"])
+    print(f"f32x B={blocks}: largest sum |term| / (2^24 quantum) {r:.2f}, largest activation {max(st['vmax']):.4g}, "
+          f"layer exponents {sorted(set(st['exps']))}")
+    assert len(st["layers"]) == 2 * blocks + 1 and 0 < r < 1.0
+    assert set(st["exps"]) == {13}
+    assert np.isfinite(pi).all() and np.isfinite(v).all()
+    assert v.std() > 0.005 and pi.max(1).min() < 0.95, (v.std(), pi.max(1).min())
+
+
+def test_fx_certificate_refuses_inexact_nets():
+    """one rich weight reading a rich channel (both low parts non-zero: 12 + 12 significand bits and a sum) breaks the certificate;
+    so does a dense Glorot net"""
+    blocks = 2
+    x = M.fx_boards(16, 9)
+    p = M.from_flat(blocks, M.lattice_net_fx(blocks, 5))
+    M.forward_fx(M.to_flat(blocks, p), blocks, x, certify=True)
+    W = p["b1a_w"]
+    ci, co = 33, 37                                            # rich input channel, rich output channel
+    rich_w = W[W != np.round(W)].ravel()[0]
+    ky, kx = [(a, b) for a in range(3) for b in range(3) if W[a, b, ci, co] == 0][0]
+    W[ky, kx, ci, co] = rich_w
+    with pytest.raises(M.NotExact):
+        M.forward_fx(M.to_flat(blocks, p), blocks, x, certify=True)
+    with pytest.raises(M.NotExact):
+        M.forward_fx(T.make_net_flat(1, seed=3, perturb_bn=True), 1, golden_boards(2), certify=True)
+
+
+def test_fx_lattice_net_is_not_vacuous():
+    """the B = 20 net on the pool of the GPU test: every fragment position (tap, k-slice, column tile) of the layer loop meets, in
+    some layer, a rich weight (wl != 0) on a non-zero ah and a ternary weight on an activation with al != 0 — for every tap both in a
+    border cell and in an interior cell of the board; in every layer at least 10 % of the non-zero activations entering the
+    rich-reading weights have al != 0, at least 25 % of the outputs are non-zero and at least 10 % are zero"""
+    blocks = 20
+    flat, x, pi, v, st = M.fx_pool(blocks)
+    cov = st["coverage"]
+    assert len(x) == 256 and len(cov) == 2 * blocks
+    for kind in ("rich", "tern"):
+        live = np.any([c[kind] for c in cov], 0)
+        assert live.shape == (9, 8, 16) and live.all(), (kind, np.argwhere(~live))
+        cells = np.any([c["cell_" + kind] for c in cov], 0)
+        assert cells.shape == (9, 2) and cells.all(), (kind, cells)
+    share = np.array([c["enter_lo"] / c["enter"] for c in cov])
+    d = np.array(st["density"])
+    print(f"f32x B=20: al != 0 on {share.min():.2f} .. {share.max():.2f} of the activations entering rich-reading weights, "
+          f"non-zero outputs per layer {d.min():.2f} .. {d.max():.2f}")
+    assert share.min() >= 0.10 and d.min() >= 0.25 and d.max() <= 0.90, (share.min(), d.min(), d.max())
+    # the term the kernel leaves out is identically zero on this net: no weight with wl != 0 reads an activation with al != 0
+    p2, v2, _ = M.forward_fx(flat, blocks, x[:8], variant=dict(kind="with_al_wl"))
+    assert (p2 == pi[:8]).all() and (v2 == v[:8]).all()
+
+
+def test_fx_model_variants_are_visible():
+    """what the GPU test would see: each mistake of the layer loop, confined to ONE layer, tap, k-slice and column tile — in the first,
+    a middle and the last conv layer, at the busiest live position of the coverage table — moves pi or v of some board of the pool
+    by 4 x GPU_TOL or more; so does a shortcut taken from the pair instead of the fp32 registers (anywhere).  (al wl included is
+    not among them: on the lattice net that term is zero — test_fx_lattice_net_is_not_vacuous.)"""
+    blocks = 20
+    flat, x, pi, v, st = M.fx_pool(blocks)
+    cov = st["coverage"]
+    sub = slice(0, 96)
+    for L in (0, blocks, 2 * blocks - 1):
+        rich_pos = np.unravel_index(np.argmax(cov[L]["rich_n"]), (9, 8, 16))
+        tern_pos = np.unravel_index(np.argmax(cov[L]["tern_n"] * (np.arange(8) >= 1)[None, :, None]), (9, 8, 16))   # stale_al: ks >= 1
+        for kind, pos in (("drop_wh_al", tern_pos), ("drop_wl_ah", rich_pos), ("wl_ah_next_tile", rich_pos), ("stale_al", tern_pos)):
+            assert cov[L]["rich" if pos is rich_pos else "tern"][pos]
+            var = dict(kind=kind, layer=L, tap=int(pos[0]), ks=int(pos[1]), ct=int(pos[2]))
+            p2, v2, _ = M.forward_fx(flat, blocks, x[sub], variant=var)
+            d = max(np.abs(p2 - pi[sub]).max(), np.abs(v2 - v[sub]).max())
+            print(f"f32x B=20 layer {L:2d} {kind:16s} at (tap, ks, ct) = {tuple(int(i) for i in pos)}: {d:.2e} = {d / M.GPU_TOL:.0f} x GPU_TOL")
+            assert d >= 4 * M.GPU_TOL, (var, d)
+    p2, v2, _ = M.forward_fx(flat, blocks, x[sub], variant=dict(kind="shortcut_pair"))
+    d = max(np.abs(p2 - pi[sub]).max(), np.abs(v2 - v[sub]).max())
+    print(f"f32x B=20 shortcut taken from hi + lo: {d:.2e} = {d / M.GPU_TOL:.0f} x GPU_TOL")
+    assert d >= 4 * M.GPU_TOL, d
+
+
+def test_fx_edge_and_stem_nets_pass_the_certificate():
+    """the nets of the GPU tests at the edges of the layer scale reach them, exactly; and the stem keeps planes that fp16 cannot
+    represent: the certificate holds on them in fp32, and rounding them to fp16 first would move the outputs"""
+    x = M.fx_boards(64, 11)
+    _, _, st = M.forward_fx(M.fx_edge_net("scale_clamps", 5), 2, x, certify=True)
+    assert st["exps"] == [24, -2, 0, 13], st["exps"]
+    flat = M.fx_edge_net("subnormal_wl", 5)
+    _, _, st = M.forward_fx(flat, 2, x, certify=True, coverage=True)
+    assert st["exps"] == [13] * 4
+    _, wl = M.split_pair(M.from_flat(2, flat)["b1b_w"] * np.float32(2.0 ** 13))
+    sub = (wl != 0) & (np.abs(wl) < 2.0 ** -14)
+    assert sub.sum() == 21 and st["coverage"][3]["rich"][:, :, 5].any()      # 7 rich channels x 3 rich weights, live
+    xs = M.fx_boards(96, 10, exact_planes=False)
+    planes = R.planes_from_in88(xs)
+    assert (M.F16.rne(planes) != planes).mean() > 0.05
+    flat = M.lattice_net_fx(2, 6, stem_fine=0)
+    pi, v, _ = M.forward_fx(flat, 2, xs, certify=True)
+    f = xs[:, 48:88].copy().view(np.float32).reshape(-1, 10)
+    xr = xs.copy()
+    xr[:, 48:88] = M.F16.rne(f).view(np.uint8).reshape(-1, 40)
+    p2, v2, _ = M.forward_fx(flat, 2, xr)
+    d = max(np.abs(p2 - pi).max(), np.abs(v2 - v).max())
+    print(f"stem planes rounded to fp16 first: {d:.2e} = {d / M.GPU_TOL:.0f} x GPU_TOL")
+    assert d >= 4 * M.GPU_TOL
