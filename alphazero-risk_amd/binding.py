@@ -83,6 +83,7 @@ EXPORTS = [
     "azr_selfplay_run", "azr_selfplay_counters", "azr_samples_drain", "azr_samples_device_view", "azr_samples_copy_device", "azr_profile_last_run",
     "azr_device_synchronize", "azr_debug_tower_clock", "azr_debug_tower_trace", "azr_debug_tower_plan", "azr_arena_start", "azr_arena_run", "azr_arena_results", "azr_arena_log",
     "azr_arena_set_opponent_net", "azr_arena_set_opponent_search", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
+    "azr_mcts_set_root_noise", "azr_selfplay_set_dirichlet", "azr_mcts_root_noise", "azr_debug_root_noise",
 ]
 
 
@@ -149,6 +150,10 @@ def load_library(test_hooks=False):
         L.azr_arena_collect_scripted_samples.argtypes = [C.c_void_p, C.c_int]
         L.azr_arena_results.argtypes = [C.c_void_p, C.c_void_p]
         L.azr_arena_log.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_mcts_set_root_noise.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_selfplay_set_dirichlet.argtypes = [C.c_void_p, C.c_float, C.c_uint32]
+        L.azr_mcts_root_noise.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_debug_root_noise.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _libs[test_hooks] = L
         if not test_hooks:
             _lib = L
@@ -405,6 +410,37 @@ class Engine:
         m = np.zeros(self.G, np.uint8)
         self._chk(self.L.azr_mcts_pick(self.h, int(sample), _p(m)))
         return m
+
+    # ---- root noise (this engine's own; off = the reference's constant)
+    def set_root_noise(self, eta):
+        """host-stepped searches: eta [G, 43] replaces DIR_NOISE_VALUE in the first selection of every descent, used as given;
+        None = off"""
+        if eta is None:
+            self._chk(self.L.azr_mcts_set_root_noise(self.h, None))
+            return
+        e = np.ascontiguousarray(eta, np.float32)
+        assert e.shape == (self.G, MOVES)
+        self._chk(self.L.azr_mcts_set_root_noise(self.h, _p(e)))
+
+    def selfplay_set_dirichlet(self, alpha, noise_seed=0):
+        """device self-play: Dirichlet(alpha) over every new root's legal moves (alpha <= 0 = off); read by selfplay_start*"""
+        self._chk(self.L.azr_selfplay_set_dirichlet(self.h, float(alpha), int(noise_seed)))
+
+    def root_noise(self):
+        """the vector in force at each game's current root, [G, 43]; zeros where none"""
+        e = np.zeros((self.G, MOVES), np.float32)
+        self._chk(self.L.azr_mcts_root_noise(self.h, _p(e)))
+        return e
+
+    def debug_root_noise(self, alpha, noise_seed, game_seed, decision, valid):
+        """the sampler alone: one vector per (game_seed[i], decision[i], valid[i]) -> [n, 43]"""
+        s = np.ascontiguousarray(game_seed, np.uint32)
+        d = np.ascontiguousarray(decision, np.uint32)
+        v = np.ascontiguousarray(valid, np.uint64)
+        assert s.ndim == 1 and s.shape == d.shape == v.shape
+        e = np.zeros((len(s), MOVES), np.float32)
+        self._chk(self.L.azr_debug_root_noise(self.h, float(alpha), int(noise_seed), _p(s), _p(d), _p(v), len(s), _p(e)))
+        return e
 
     # ---- self-play
     def selfplay_start(self, base_seed=20260001):

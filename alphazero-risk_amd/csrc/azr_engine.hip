@@ -7,6 +7,7 @@
 #include <new>
 
 #include "azr_internal.hpp"
+#include "azr_noise.hpp"
 #include "azr_players.hpp"
 
 using namespace azr;
@@ -362,8 +363,10 @@ enum : int { RD_DONE = 0, RD_LEAF = 1, RD_FAIL = 2 };
 // next simulation from the counter and descend from the root, repeated until the counter is exhausted (RD_DONE), a leaf
 // needs the net (RD_LEAF: leaf record written to slot g * T + th, pending bit set) or a rule error (RD_FAIL).
 // `S`: the settings of the tree that is searching (the arena's player B may carry its own budget and PUCT constant).
+// NOISE: the game's root noise vector `eta` (lane i <-> move i) enters the first selection of every descent (tree_select).
+template <bool NOISE>
 __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out)
+                                            StepCount& k, uint32_t& err_out, float eta)
 {
     const Rules R = E.rules;
     const Tree t = thread_tree(t0, th);
@@ -409,7 +412,7 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
                 break;
             }
             k.levels++;
-            uint32_t mv = tree_select(t, idx, nr, S, c.search_id, scratch);
+            uint32_t mv = tree_select<NOISE>(t, idx, nr, S, c.search_id, scratch, plen == 0, E.noise_eps, eta);
             TP(12);
             if (mv == NONE) { fail = true; s.err = E_LOGIC; break; }
             uint32_t before = s.cur;
@@ -440,12 +443,13 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
 // One round of AlphaZeroMCTS::simulate for all T search threads of the game, in thread order: every thread without a
 // pending leaf runs descents until it blocks on the net.  RD_LEAF = at least one leaf is waiting; RD_DONE = the counter
 // is exhausted and every claimed simulation is backed up.
+template <bool NOISE>
 __device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out)
+                                            StepCount& k, uint32_t& err_out, float eta)
 {
     for (int th = 0; th < E.T; th++) {
         if ((c.pending >> th) & 1u) continue;
-        int r = run_descents(E, S, g, t, th, c, root, scratch, k, err_out);
+        int r = run_descents<NOISE>(E, S, g, t, th, c, root, scratch, k, err_out, eta);
         if (r == RD_FAIL) { c.pending = 0; return RD_FAIL; }
         if (r == RD_LEAF && plen_get(c, th) == 0) break;  // root expansion: the threads start after setRootState
     }
@@ -491,9 +495,21 @@ __device__ __forceinline__ void selfplay_next_game(const Dev& E, int g, const Tr
     tree_clear(t, c);
 }
 
+// the noise vector of game g's NEW root (device self-play with azr_selfplay_set_dirichlet): drawn for (seed, decision) of the running
+// game over the root's legal moves, stored for azr_mcts_root_noise and handed to the descents; zeros for a slot that went idle
+__device__ __forceinline__ float new_root_noise(const Dev& E, int g, const Ctl& c, const WS& root)
+{
+    float eta = 0.0f;
+    if (c.mode != 0) eta = dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules));
+    if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
+    return eta;
+}
+
 // One tree step for game g: consume the pending leaf's (pi, v) [expand + backup], then run searches — and in
 // self-play mode decisions, moves and game restarts — until the next leaf that needs the net.
-template <bool SELFPLAY>
+// NOISE: root noise is in force (host-stepped: azr_mcts_set_root_noise's vector; self-play: a Dirichlet draw per new root).  The
+// default instantiations carry none of it.
+template <bool SELFPLAY, bool NOISE>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
     __shared__ int8_t scratch[128];
@@ -510,6 +526,8 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
     ws_load(root, E.state + (size_t)g * GREC);
     StepCount k;
     bool root_dirty = false;
+    float eta = 0.0f;
+    if (NOISE) eta = E.root_eta[(size_t)g * MOVES + (lane_id() < MOVES ? lane_id() : 0)];
     TP(0);
     consume_pending(E, g, t, c, k);
     for (;;) {
@@ -553,13 +571,14 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             }
             root_dirty = true;
             TP(18);
+            if (NOISE) eta = new_root_noise(E, g, c, root);   // the next decision's root, or the next game's first
             if (c.mode == 0) break;  // quota exhausted: the slot idles
             tree_trim(t, c);
             c.sims_done = 0; c.sims_started = 0;
             TP(14);
         }
         uint32_t err = 0;
-        int r = search_round(E, S, g, t, c, root, scratch, k, err);
+        int r = search_round<NOISE>(E, S, g, t, c, root, scratch, k, err, eta);
         if (r == RD_LEAF) break;
         if (r == RD_FAIL) {
             k.err++;
@@ -567,6 +586,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             if (SELFPLAY) {  // abandon the game (the reference would have thrown): restart the slot
                 selfplay_next_game(E, g, t, c, root);
                 root_dirty = true;
+                if (NOISE) eta = new_root_noise(E, g, c, root);
                 if (c.mode == 0) break;
                 tree_trim(t, c);
                 continue;
@@ -774,10 +794,11 @@ __device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
             c.rng = root.rng;
             uint32_t err = 0;
             // every AlphaZeroPlayer owns an AlphaZeroMCTS with its own Settings: player B's simulation count and PUCT constant
-            // (azr_arena_set_opponent_search); the noise term is shared
+            // (azr_arena_set_opponent_search); the noise term is shared, and it is the constant one: evaluation games are played
+            // without root noise, whatever azr_mcts_set_root_noise / azr_selfplay_set_dirichlet say
             Search Sw = E.search;
             if (w) { Sw.simulations = E.search2_simulations; Sw.hp = E.search2_hp; }
-            int r = search_round(E, Sw, g, tt, c, root, scratch, k, err);
+            int r = search_round<false>(E, Sw, g, tt, c, root, scratch, k, err, 0.0f);
             root.rng = c.rng;
             if (r == RD_LEAF) { if (w) swap_tree_ctl(c, x2); break; }
             if (r == RD_FAIL) { fail = true; root.err = err; }
@@ -955,6 +976,26 @@ __global__ __launch_bounds__(64) void k_selfplay_start(Dev E, int keep)
     ctl_store(c, &E.ctl[g]);
 }
 
+// the first root's noise vector of every slot (azr_selfplay_start* with azr_selfplay_set_dirichlet in force)
+__global__ __launch_bounds__(64) void k_selfplay_noise(Dev E)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    WS root;
+    ws_load(root, E.state + (size_t)g * GREC);
+    new_root_noise(E, g, c, root);
+}
+
+// azr_debug_root_noise: the sampler alone, one wave per vector
+__global__ __launch_bounds__(64) void k_debug_root_noise(float alpha, uint32_t noise_seed, const uint32_t* game_seed, const uint32_t* decision,
+                                                         const uint64_t* valid, float* out)
+{
+    const size_t i = blockIdx.x;
+    const float eta = dirichlet_draw(alpha, noise_seed, rfl(game_seed[i]), rfl(decision[i]), rfl64(valid[i]));
+    if (lane_id() < MOVES) out[i * MOVES + lane_id()] = eta;
+}
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -1051,6 +1092,7 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     d.search.c2 = s->dir_noise_epsi * s->dir_noise_value;
     d.search.hp = s->hp_exploration;
     d.search.temperature_threshold = s->temperature_threshold;
+    d.noise_eps = s->dir_noise_epsi;
     d.search2_simulations = d.search.simulations;   // player B of a two-net arena: this handle's own until azr_arena_set_opponent_search
     d.search2_hp = d.search.hp;
     const size_t G = d.G, GT = G * d.T;
@@ -1085,6 +1127,8 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     HIPCHK(h, dmalloc(&d.alog_status, G * ALOG));
     HIPCHK(h, dmalloc(&d.alog_rounds, G * ALOG));
     HIPCHK(h, dmalloc(&d.alog_final, G * ALOG * GREC));
+    HIPCHK(h, dmalloc(&d.root_eta, G * MOVES));
+    HIPCHK(h, hipMemsetAsync(d.root_eta, 0, G * MOVES * sizeof(float), h->stream));
     HIPCHK(h, hipMemsetAsync(d.state, 0, G * GREC, h->stream));
     HIPCHK(h, hipMemsetAsync(d.ctl, 0, G * sizeof(Ctl), h->stream));
     HIPCHK(h, hipMemsetAsync(d.touch, 0, G * C * sizeof(uint32_t), h->stream));
@@ -1111,7 +1155,7 @@ extern "C" int azr_engine_destroy(azr_engine* h)
     Dev& d = h->d;
     void* ptrs[] = {d.sp_started, d.state, d.ctl, d.nodes, d.touch, d.nhash, d.table, d.freel, d.path, d.leaf_in, d.leaf_key,
                     d.leaf_valid, d.leaf_hash, d.net_pi, d.net_v, d.stage, d.ring, d.ring_count, d.counters, d.active,
-                    d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final};
+                    d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final, d.root_eta};
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : h->tree2) if (p) hipFree(p);
     if (d.leaf_list) hipFree(d.leaf_list);
@@ -1318,7 +1362,8 @@ extern "C" int azr_mcts_begin(azr_engine* h)
 static int tree_step_host(azr_engine* h, uint32_t* active)
 {
     HIPCHK(h, hipMemsetAsync(h->d.active, 0, 4, h->stream));
-    LAUNCH(h, k_tree_step<false>, h->d);
+    if (h->noise_host) LAUNCH(h, (k_tree_step<false, true>), h->d);
+    else LAUNCH(h, (k_tree_step<false, false>), h->d);
     D2H(h, active, h->d.active, 4);
     SYNC(h);
     return AZR_OK;
@@ -1430,6 +1475,75 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
     HIPCHK(h, hipMemsetAsync(h->d.counters, 0, (size_t)h->d.G * sizeof(Counters), h->stream));
     HIPCHK(h, hipMemsetAsync(h->d.ring_count, 0, sizeof(unsigned long long), h->stream));
     LAUNCH(h, k_selfplay_start, h->d, keep);
+    // root noise as azr_selfplay_set_dirichlet stands now: a running self-play never sees a change.  A vector set for host-stepped
+    // searches ends here (the array is this self-play's from now on).
+    h->noise_host = false;
+    h->sp_noise = h->sp_alpha > 0.0f;
+    h->d.noise_alpha = h->sp_alpha;
+    h->d.noise_seed = h->sp_noise_seed;
+    if (h->sp_noise) LAUNCH(h, k_selfplay_noise, h->d);
+    else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, (size_t)h->d.G * MOVES * sizeof(float), h->stream));
+    SYNC(h);
+    return AZR_OK;
+}
+
+// ---- root noise -----------------------------------------------------------------------------------------
+extern "C" int azr_mcts_set_root_noise(azr_engine* h, const float* eta)
+{
+    ENTER(h);
+    const size_t sz = (size_t)h->d.G * MOVES * sizeof(float);
+    if (eta) H2D(h, h->d.root_eta, eta, sz);
+    else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, sz, h->stream));
+    SYNC(h);
+    h->noise_host = eta != nullptr;
+    if (h->mode == 2) h->mode = 0;   // the array was a running self-play's: that self-play is over (azr_selfplay_start* begins the next)
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_set_dirichlet(azr_engine* h, float alpha, uint32_t noise_seed)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (alpha != alpha || alpha > DIR_ALPHA_MAX) {
+        h->err = "azr_selfplay_set_dirichlet: alpha must be a number <= 10 (<= 0 = off)";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    h->sp_alpha = alpha > 0.0f ? alpha : 0.0f;
+    h->sp_noise_seed = noise_seed;
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_root_noise(azr_engine* h, float* eta)
+{
+    ENTER(h);
+    if (!eta) return AZR_E_INVALID_ARGUMENT;
+    const size_t sz = (size_t)h->d.G * MOVES * sizeof(float);
+    const bool in_force = h->mode == 2 ? h->sp_noise : h->mode == 3 ? false : h->noise_host;
+    if (!in_force) { memset(eta, 0, sz); return AZR_OK; }
+    D2H(h, eta, h->d.root_eta, sz);
+    SYNC(h);
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_root_noise(azr_engine* h, float alpha, uint32_t noise_seed, const uint32_t* game_seed, const uint32_t* decision,
+                                    const uint64_t* valid, int n, float* eta_out)
+{
+    ENTER(h);
+    if (alpha != alpha || alpha > DIR_ALPHA_MAX || !(alpha > 0.0f)) {
+        h->err = "azr_debug_root_noise: alpha must be a number in (0, 10]";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    if (n < 0 || (n > 0 && (!game_seed || !decision || !valid || !eta_out))) return AZR_E_INVALID_ARGUMENT;
+    if (n == 0) return AZR_OK;
+    DevBuf bs, bd, bv, bo;
+    HIPCHK(h, bs.alloc((size_t)n * 4)); HIPCHK(h, bd.alloc((size_t)n * 4)); HIPCHK(h, bv.alloc((size_t)n * 8));
+    HIPCHK(h, bo.alloc((size_t)n * MOVES * sizeof(float)));
+    H2D(h, bs.p, game_seed, (size_t)n * 4);
+    H2D(h, bd.p, decision, (size_t)n * 4);
+    H2D(h, bv.p, valid, (size_t)n * 8);
+    hipLaunchKernelGGL(k_debug_root_noise, dim3(n), dim3(64), 0, h->stream, alpha, noise_seed, (const uint32_t*)bs.p, (const uint32_t*)bd.p,
+                       (const uint64_t*)bv.p, (float*)bo.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, eta_out, bo.p, (size_t)n * MOVES * sizeof(float));
     SYNC(h);
     return AZR_OK;
 }
@@ -1486,7 +1600,8 @@ extern "C" int azr_selfplay_run(azr_engine* h, int passes)
         const bool prof = (p % stride == 0) && k < nprof;
         if (h->sp_tail) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, sizeof(int), h->stream));
         if (prof) HIPCHK(h, hipEventRecord(h->ev[3 * k + 0], h->stream));
-        LAUNCH(h, k_tree_step<true>, h->d);
+        if (h->sp_noise) LAUNCH(h, (k_tree_step<true, true>), h->d);
+        else LAUNCH(h, (k_tree_step<true, false>), h->d);
         if (prof) HIPCHK(h, hipEventRecord(h->ev[3 * k + 1], h->stream));
         if (h->sp_tail) {
             D2H(h, &n_eval, h->d.leaf_count, sizeof(int));

@@ -99,6 +99,11 @@ struct Dev {
     int lc_base;               // ... row (x 2) the arena step counts into
     int lc_zero;               // ... row (x 2) the arena step zeroes for the next pass (nobody reads it any more), or -1
     int arena_collect;         // stage (s, pi, player) per AlphaZero decision and flush finished games to the record ring
+    // root noise (this engine's own; read by k_tree_step<.., true> only, never by the arena)
+    float* root_eta;           // [G][43]  the vector in force at each game's root (lane i <-> move i)
+    float noise_eps;           // DIR_NOISE_EPSI: noiseP = c1 * P + noise_eps * eta at path depth 0
+    float noise_alpha;         // device self-play: Dirichlet(alpha) per new root ...
+    uint32_t noise_seed;       // ... keyed by (noise_seed, game seed, decision, move)
 };
 constexpr int ALOG = 16;
 
@@ -152,6 +157,10 @@ struct azr_engine {
     bool arena_open = false;      // between azr_arena_start and the azr_arena_run that found every slot idle
     int opp_simulations = -1;     // azr_arena_set_opponent_search: player B's count per decision and PUCT constant (< 0 = the handle's own);
     float opp_hp = -1.0f;         // copied into d.search2_* by azr_arena_start
+    bool noise_host = false;      // azr_mcts_set_root_noise: host-stepped searches run k_tree_step<false, true> on d.root_eta
+    float sp_alpha = 0.0f;        // azr_selfplay_set_dirichlet, as set ...
+    uint32_t sp_noise_seed = 0;
+    bool sp_noise = false;        // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, true>
     bool sp_tail = false;         // quota self-play: no game is left to start, slots go idle -> compacted net batches
     void* train = nullptr;        // azr_train.hip: optimiser state + activation slabs, created by the first azr_nn_train*
     void* dp_comm = nullptr;      // azr_dp_init: this handle's RCCL communicator (ncclComm_t), rank and world

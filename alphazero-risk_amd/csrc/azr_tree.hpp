@@ -354,7 +354,12 @@ __device__ __forceinline__ uint32_t tree_lookup_node(const Tree& t, uint32_t kd,
 // FMA.  The reference's loop keeps the first strict maximum in unordered_map iteration order over the moves that are
 // not "skipped" (N == 0 && active_N == 1: another thread is already exploring that unobserved move); only when every
 // candidate is skipped does it fall back to the best skipped one.  active_N++ on the chosen move.
-__device__ __forceinline__ uint32_t tree_select(const Tree& t, uint32_t idx, const NodeRegs& nr, const Search& S, uint32_t stamp, int8_t* scratch)
+// NOISE (this engine's own, off by default): at path depth 0 of a descent — `root_level`, the first selection of a search thread's
+// descent — the constant second term c2 = eps * DIR_NOISE_VALUE becomes eps * eta[move], eta the game's root noise vector (lane i <->
+// move i); every other level keeps c2.  The stored P stays the clean prior.  Without NOISE the parameters are dead.
+template <bool NOISE = false>
+__device__ __forceinline__ uint32_t tree_select(const Tree& t, uint32_t idx, const NodeRegs& nr, const Search& S, uint32_t stamp, int8_t* scratch,
+                                                bool root_level = false, float eps = 0.0f, float eta = 0.0f)
 {
     const uint8_t* n = node_ptr(t, idx);
     const uint32_t l = lane_id();
@@ -365,7 +370,7 @@ __device__ __forceinline__ uint32_t tree_select(const Tree& t, uint32_t idx, con
     const uint32_t W = nr.W;
     const uint32_t N = W & N_MASK, act = W >> 24;
     if (l == 0) t.touch[idx] = stamp;  // visited = true
-    const float noiseP = __fadd_rn(__fmul_rn(S.c1, P), S.c2);
+    const float noiseP = (NOISE && root_level) ? __fadd_rn(__fmul_rn(S.c1, P), __fmul_rn(eps, eta)) : __fadd_rn(__fmul_rn(S.c1, P), S.c2);
     const float v = __fmul_rn(__fmul_rn(noiseP, S.hp), __fsqrt_rn(__fadd_rn(1.0f, (float)sumN)));
     const float nn = __fadd_rn(1.0f, (float)N);
     float u = __fadd_rn(Q, __fdiv_rn(v, nn));

@@ -98,6 +98,8 @@ void Settings::init(int argc, char* argv[])
         {"seed", "[this build] base seed of the per-game RNG streams", std::to_string(BASE_SEED), false},
         {"devices", "[this build] HIP device of every logical gpu, comma separated (default 0,1,..; \"0,0\" rehearses --gpus 2 on one card)", "", false},
         {"pair-halves", "[this build] mirrored pairs: 1 = both games of a pair at the same time on two slots, 0 = one after the other on one slot", std::to_string(CONCURRENT_PAIR_HALVES), true},
+        {"dir-alpha", "[this build] self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision (0 = the reference's constant --dnv; at most 10)", "0", false},
+        {"dir-seed", "[this build] seed of the self-play root noise (independent of --seed: the games' dice and deals do not move)", std::to_string(DIR_SEED), false},
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -213,6 +215,17 @@ void Settings::init(int argc, char* argv[])
     }
     BASE_SEED = (uint32_t)strtoul(get("seed").c_str(), nullptr, 10);
     CONCURRENT_PAIR_HALVES = parse_bool(get("pair-halves"));
+    {
+        char* end = nullptr;
+        const std::string av = get("dir-alpha");
+        const double al = strtod(av.c_str(), &end);
+        if (av.empty() || *end != '\0' || !(al >= 0.0) || al > 10.0) {
+            fprintf(stderr, "--dir-alpha: '%s' is not a Dirichlet parameter (0 = off, at most 10)\n", av.c_str());
+            exit(2);
+        }
+        DIR_ALPHA = (float)al;
+    }
+    DIR_SEED = (uint32_t)strtoul(get("dir-seed").c_str(), nullptr, 10);
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
     DEVICE_MAP.clear();
@@ -680,6 +693,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         Engine& e = *generate->getNN(i)->engine;
         // exactly `share` games are started and every one is played to its end (Counter::hasNext over
         // TRAIN_ITERATION_GAMES, alphazero_trainer.cpp:83)
+        // root noise of the generated games: --dir-alpha 0 (default) keeps the reference's constant
+        e.check(azr_selfplay_set_dirichlet(e.h, SETTINGS.DIR_ALPHA, SETTINGS.DIR_SEED), "selfplay_set_dirichlet");
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);

@@ -25,7 +25,7 @@ namespace azrhost {
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
 // `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2,
-// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`), the others marked "[this build]" in --help.
+// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play), the others marked "[this build]" in --help.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:
@@ -74,6 +74,8 @@ public:
     uint32_t BASE_SEED = 20260001;
     std::vector<int> DEVICE_MAP;         // --devices: HIP device of logical gpu i (empty = i); "0,0" rehearses --gpus 2 on one card
     bool CONCURRENT_PAIR_HALVES = true;  // --pair-halves: the two games of a mirrored pair on two slots at the same time (AZR_MIRROR_CONCURRENT)
+    float DIR_ALPHA = 0.0f;              // --dir-alpha: self-play root noise ~ Dirichlet(alpha) per decision (0 = the reference's constant DIR_NOISE_VALUE)
+    uint32_t DIR_SEED = 0;               // --dir-seed: seed of that noise (self-play generation of -m train only: compare, benchmark and -m play games have none)
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 

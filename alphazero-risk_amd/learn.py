@@ -203,6 +203,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         if share > 0:
             # exactly `share` games, each played to its end (Counter::hasNext, alphazero_trainer.cpp:83); this rank's seed
             # stream continues where its previous iteration stopped, so no (iteration, rank) pair ever replays a game
+            gen.selfplay_set_dirichlet(getattr(a, "dir_alpha", 0.0), getattr(a, "dir_seed", 0))   # root noise of the generated games only (0 = the reference's constant)
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -332,6 +333,10 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32x", "f32"])
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--include-compare-samples", type=int, default=1)   # INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES
+    ap.add_argument("--dir-alpha", type=float, default=0.0,
+                    help="self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision on the device "
+                         "(0 = the reference's constant DIR_NOISE_VALUE; at most 10); compare and benchmark games have none")
+    ap.add_argument("--dir-seed", type=int, default=0, help="seed of the self-play root noise (the games' dice and deals do not move)")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")

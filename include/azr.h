@@ -188,6 +188,33 @@ int azr_mcts_policy(azr_engine* h, float* pi_host);
  * sample != 0 draws with the game's own RNG stream (one rFloat). */
 int azr_mcts_pick(azr_engine* h, int sample, uint8_t* moves_host);
 
+/* ---- root noise (this engine's own; the default is the reference's constant) ----------------------------------------
+ * The reference mixes the constant DIR_NOISE_EPSI * DIR_NOISE_VALUE into every prior at every node (alphazero_mcts.cpp:81) and
+ * samples nothing; that is the state after azr_engine_create.  With a noise vector eta in force for a game, the FIRST selection of
+ * every descent of that game's search threads (path depth 0) scores move m with
+ *     noiseP = (1 - DIR_NOISE_EPSI) * P[m] + DIR_NOISE_EPSI * eta[m]
+ * in place of ... + DIR_NOISE_EPSI * DIR_NOISE_VALUE; every deeper level keeps the constant.  eta[m] = DIR_NOISE_VALUE for all m is
+ * the constant form bit for bit.  The stored priors, azr_mcts_root_stats, the policies and the records do not change meaning.
+ * The arena (azr_arena_*, both trees) never uses root noise: evaluation games are played without it.
+ *
+ * host-stepped searches (azr_mcts_simulate / azr_mcts_begin..apply): eta_host [G][43] used as given (no masking, no
+ * normalising) at path depth 0; NULL = off (the state after create).  Holds until set again; azr_selfplay_start* ends it (the
+ * vector array is then the self-play's), and setting it ends a running self-play. */
+int azr_mcts_set_root_noise(azr_engine* h, const float* eta_host);
+/* device self-play (azr_selfplay_start*): alpha > 0 draws Dirichlet(alpha) over each new root's legal moves;
+ * alpha <= 0 = off (default).  Read by azr_selfplay_start*; a running self-play never sees a change.  Every decision's root — the
+ * first of a game, the next after a move with the tree's N / Q carried over — gets a new vector, shared by the game's search
+ * threads.  The vector for decision d of the game with seed s is a function of (noise_seed, s, d, move, alpha) alone: not of the
+ * slot, the number of games or threads, or the pass schedule; nothing is drawn from the game's own RNG stream, so dice, deals
+ * and sampled moves are the ones the same search results give without noise.  AZR_E_INVALID_ARGUMENT for a NaN alpha or alpha > 10. */
+int azr_selfplay_set_dirichlet(azr_engine* h, float alpha, uint32_t noise_seed);
+/* the vector in force at each game's current root, [G][43], zeros where none */
+int azr_mcts_root_noise(azr_engine* h, float* eta_host);
+/* the sampler alone: n vectors for (game_seed[i], decision[i], valid[i]) -> eta_out [n][43]; valid = legal-move mask as
+ * azr_engine_valid_moves; alpha in (0, 10] */
+int azr_debug_root_noise(azr_engine* h, float alpha, uint32_t noise_seed, const uint32_t* game_seed,
+                         const uint32_t* decision, const uint64_t* valid, int n, float* eta_out);
+
 /* ---- device-resident self-play (trainer move loop, alphazero_trainer.cpp:80-119) --------------------------- */
 /* (Re)start all G games: game g plays seeds base_seed + g, then base_seed + G + g, ... */
 int azr_selfplay_start(azr_engine* h, uint32_t base_seed);
