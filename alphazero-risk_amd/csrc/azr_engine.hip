@@ -1,14 +1,13 @@
 // azr_engine.hip — kernels and C-ABI (include/azr.h) of the batched Risk state-step + flattened MCTS.
 // One wavefront per game; grid = G workgroups of 64 threads.  gfx950 only.
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <new>
 
-#include "azr_internal.hpp"
-#include "azr_noise.hpp"
-#include "azr_players.hpp"
+#include "azr_arena.hpp"
 
 using namespace azr;
 
@@ -21,93 +20,6 @@ using namespace azr;
             return AZR_E_HIP;                                                                   \
         }                                                                                       \
     } while (0)
-
-// ================================================================================================
-// device helpers
-// ================================================================================================
-__device__ __forceinline__ Tree tree_of(const Dev& E, int g)
-{
-    Tree t;
-    t.C = E.C; t.H = E.H; t.DMAX = E.DMAX;
-    t.nodes = E.nodes + (size_t)g * E.C * NODE_BYTES;
-    t.touch = E.touch + (size_t)g * E.C;
-    t.nhash = E.nhash + (size_t)g * E.C;
-    t.table = E.table + (size_t)g * E.H;
-    t.freel = E.freel + (size_t)g * E.C;
-    t.path = E.path + (size_t)g * E.T * E.DMAX;  // thread 0's stack; thread_tree() selects thread k's
-    return t;
-}
-
-// the opponent AlphaZero player's tree of game g (two-net arena)
-__device__ __forceinline__ Tree tree2_of(const Dev& E, int g)
-{
-    Tree t = tree_of(E, g);
-    t.nodes = E.nodes2 + (size_t)g * E.C * NODE_BYTES;
-    t.touch = E.touch2 + (size_t)g * E.C;
-    t.nhash = E.nhash2 + (size_t)g * E.C;
-    t.table = E.table2 + (size_t)g * E.H;
-    t.freel = E.freel2 + (size_t)g * E.C;
-    return t;
-}
-// tree 2's allocator / trim state lives outside the (full) Ctl line; it is swapped into the Ctl fields the tree
-// functions use while that tree is being worked on
-struct TreeCtl { uint32_t search_id, nfree, hiwater; };
-__device__ __forceinline__ void swap_tree_ctl(Ctl& c, TreeCtl& x)
-{
-    uint32_t a = c.search_id, b = c.nfree, d = c.hiwater;
-    c.search_id = x.search_id; c.nfree = x.nfree; c.hiwater = x.hiwater;
-    x.search_id = a; x.nfree = b; x.hiwater = d;
-}
-
-__device__ __forceinline__ void ctl_load(Ctl& c, const Ctl* src)
-{
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(src);
-    uint32_t w = p[lane_id() & 31u];
-    c.mode = rdl(w, 0); c.search_id = rdl(w, 1); c.sims_done = rdl(w, 2); c.pending = rdl(w, 3);
-    c.sims_started = rdl(w, 4); c.nfree = rdl(w, 5); c.hiwater = rdl(w, 6); c.search_done = rdl(w, 7);
-    c.rng = rdl(w, 8); c.game_no = rdl(w, 9); c.nsamples = rdl(w, 10); c.status = (int32_t)rdl(w, 11);
-    c.error = rdl(w, 12); c.last_move = rdl(w, 13); c.decisions = rdl(w, 14); c.seed = rdl(w, 15);
-    c.arena_state = rdl(w, 16); c.player_start = rdl(w, 17); c.pair_phase = rdl(w, 18); c.turn_started = rdl(w, 19);
-    c.search_active = rdl(w, 20); c.slot_games = rdl(w, 21); c.dup_dropped = rdl(w, 22);
-#pragma unroll
-    for (int k = 0; k < MAX_THREADS; k++) c.plen[k] = rdl(w, 23 + k);
-    c.search_tree = rdl(w, 31);
-}
-// c.plen[k] with a wave-uniform runtime k, without indexing the register array
-__device__ __forceinline__ uint32_t plen_get(const Ctl& c, int k)
-{
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < MAX_THREADS; i++) v = k == i ? c.plen[i] : v;
-    return v;
-}
-__device__ __forceinline__ void plen_set(Ctl& c, int k, uint32_t v)
-{
-#pragma unroll
-    for (int i = 0; i < MAX_THREADS; i++) c.plen[i] = k == i ? v : c.plen[i];
-}
-__device__ __forceinline__ Tree thread_tree(const Tree& t, int k)
-{
-    Tree tk = t;
-    tk.path = t.path + (size_t)k * t.DMAX;
-    return tk;
-}
-__device__ __forceinline__ void ctl_store(const Ctl& c, Ctl* dst)
-{
-    uint32_t l = lane_id();
-    uint32_t w = 0;
-    w = l == 0 ? c.mode : w; w = l == 1 ? c.search_id : w; w = l == 2 ? c.sims_done : w; w = l == 3 ? c.pending : w;
-    w = l == 4 ? c.sims_started : w; w = l == 5 ? c.nfree : w; w = l == 6 ? c.hiwater : w; w = l == 7 ? c.search_done : w;
-    w = l == 8 ? c.rng : w; w = l == 9 ? c.game_no : w; w = l == 10 ? c.nsamples : w; w = l == 11 ? (uint32_t)c.status : w;
-    w = l == 12 ? c.error : w; w = l == 13 ? c.last_move : w; w = l == 14 ? c.decisions : w; w = l == 15 ? c.seed : w;
-    w = l == 16 ? c.arena_state : w; w = l == 17 ? c.player_start : w; w = l == 18 ? c.pair_phase : w;
-    w = l == 19 ? c.turn_started : w; w = l == 20 ? c.search_active : w; w = l == 21 ? c.slot_games : w;
-    w = l == 22 ? c.dup_dropped : w;
-#pragma unroll
-    for (int k = 0; k < MAX_THREADS; k++) w = l == 23u + k ? c.plen[k] : w;
-    w = l == 31 ? c.search_tree : w;
-    if (l < 32) reinterpret_cast<uint32_t*>(dst)[l] = w;
-}
 
 // ================================================================================================
 // rules kernels (UtilityNN / State seams)
@@ -264,247 +176,6 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
     ctl_store(c, &E.ctl[g]);
 }
 
-// packs one finished game's staged records into the 265-byte on-disk layout (alphazero_nn_data.cpp:123-130)
-__device__ __forceinline__ void flush_samples(const Dev& E, int g, uint32_t n, int status, unsigned long long& dropped)
-{
-    if (n == 0) return;
-    unsigned long long start = 0;
-    if (lane_id() == 0) start = atomicAdd(E.ring_count, (unsigned long long)n);
-    start = rfl64(start);
-    const uint8_t* st = E.stage + (size_t)g * E.SCAP * STAGE_BYTES;
-    for (uint32_t r = 0; r < n; r++) {
-        unsigned long long slot = start + r;
-        if (slot >= E.ring_cap) { dropped += 1; continue; }
-        const uint8_t* src = st + (size_t)r * STAGE_BYTES;
-        uint8_t* dst = E.ring + (size_t)slot * AZR_RECORD_BYTES;
-        uint32_t player = rfl((uint32_t)src[260]);
-        // NNTrainDataStorage::updateValues (alphazero_nn_data.cpp:51-65)
-        float z = status == ST_DRAW ? 0.0f : ((int)player == status ? 1.0f : -1.0f);
-        uint32_t zb = __float_as_uint(z);
-        for (uint32_t j = lane_id(); j < AZR_RECORD_BYTES; j += 64) {
-            uint8_t b;
-            if (j == 0) b = (uint8_t)player;
-            else if (j < 89) b = src[j - 1];
-            else if (j < 93) b = (uint8_t)(zb >> (8 * (j - 89)));
-            else b = src[88 + (j - 93)];
-            dst[j] = b;
-        }
-    }
-}
-
-struct StepCount {
-    unsigned long long sims = 0, evals = 0, levels = 0, dec = 0, games = 0, samples = 0, drop = 0, err = 0, ringdrop = 0;
-};
-
-// Counters are kept PER GAME (one 72-byte row each, written by the game's own wave: no atomics) and summed by the host
-// when somebody asks (azr_selfplay_counters).  One shared row bumped with atomics made every pass end with G x 4..9
-// same-address device atomics, which the L2 retires one by one (~12 ns each): 20 us of a 47-us tree step at 512 games.
-// `count_active`: host-stepped search only (azr_mcts_leaves reads the number of games that wait for the net).
-// The row is read-modify-write, and the read is issued when the wave STARTS (counters_begin): at the end of a step the wave's stores
-// are still draining, and a load issued behind them waits for every one of them (memory operations of a wave retire in order) —
-// 3.7 us of an average mid-game wave, 9 us of the slow ones the launch waits for (profiles/r03_tree_step_profile.txt).
-__device__ __forceinline__ unsigned long long counters_begin(const Dev& E, int g)
-{
-    const uint32_t l = lane_id();
-    return l < 9 ? reinterpret_cast<const unsigned long long*>(E.counters + g)[l] : 0ull;
-}
-__device__ __forceinline__ void flush_counters(const Dev& E, int g, const Ctl& c, const StepCount& k, bool count_active, unsigned long long base)
-{
-    if (count_active && lane_id() == 0 && c.pending) atomicAdd(E.active, 1u);
-    const uint32_t l = lane_id();
-    unsigned long long d = 0;
-    d = l == 0 ? k.sims : d; d = l == 1 ? k.evals : d; d = l == 2 ? k.levels : d; d = l == 3 ? k.dec : d; d = l == 4 ? k.games : d;
-    d = l == 5 ? k.samples : d; d = l == 6 ? k.drop : d; d = l == 7 ? k.err : d; d = l == 8 ? k.ringdrop : d;
-    if (l < 9 && d) {
-        unsigned long long* row = reinterpret_cast<unsigned long long*>(E.counters + g);
-        row[l] = base + d;
-    }
-}
-
-// AlphaZeroMCTS::search leaf branch, after the future resolved (alphazero_mcts.cpp:350-356): expand + backup, for every
-// search thread with a pending leaf, in thread order.  A state another thread has added meanwhile is dropped
-// (StateSimulationsStorage::add, alphazero_mcts.cpp:203-215) and its value still backed up.
-__device__ __forceinline__ void consume_pending(const Dev& E, int g, const Tree& t, Ctl& c, StepCount& k)
-{
-    if (!c.pending) return;
-    const uint32_t l = lane_id();
-    for (int th = 0; th < E.T; th++) {
-        if (!((c.pending >> th) & 1u)) continue;
-        const size_t slot = (size_t)g * E.T + th;
-        float pi = E.net_pi[slot * PI_STRIDE + (l < MOVES ? l : 0)];
-        float v = rdlf(E.net_v[slot], 0);
-        uint64_t valid = rfl64(E.leaf_valid[slot]);
-        uint32_t kd = reinterpret_cast<const uint32_t*>(E.leaf_key + slot * GREC)[l & 15u];
-        uint32_t h = rfl(E.leaf_hash[slot]);
-        TP(1);
-        if (E.T > 1 && tree_lookup(t, kd, h) != NO_NODE) c.dup_dropped++;
-        else {
-            TP(2);
-            float prior = normalize_prior(pi, valid);
-            TP(3);
-            if (tree_expand(t, c, kd, h, valid, prior) == NO_NODE) k.drop++;
-        }
-        TP(4);
-        k.evals++;
-        const uint32_t plen = plen_get(c, th);
-        if (plen > 0) {  // plen == 0: this was setRootState's root expansion (not a simulation)
-            tree_backup(thread_tree(t, th), plen, v, false);
-            c.sims_done++;
-            k.sims++;
-        }
-        TP(5);
-    }
-    c.pending = 0;
-}
-
-enum : int { RD_DONE = 0, RD_LEAF = 1, RD_FAIL = 2 };
-
-// AlphaZeroMCTS::threadSimulateJob + search (alphazero_mcts.cpp:310-377) for search thread `th`, iteratively: claim the
-// next simulation from the counter and descend from the root, repeated until the counter is exhausted (RD_DONE), a leaf
-// needs the net (RD_LEAF: leaf record written to slot g * T + th, pending bit set) or a rule error (RD_FAIL).
-// `S`: the settings of the tree that is searching (the arena's player B may carry its own budget and PUCT constant).
-// NOISE: the game's root noise vector `eta` (lane i <-> move i) enters the first selection of every descent (tree_select).
-template <bool NOISE>
-__device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out, float eta)
-{
-    const Rules R = E.rules;
-    const Tree t = thread_tree(t0, th);
-    const size_t slot = (size_t)g * E.T + th;
-    while ((int)c.sims_started < S.simulations) {
-        c.sims_started++;  // Counter::hasNext
-        WS s = root;
-        s.rng = c.rng;
-        s.err = 0;
-        uint32_t plen = 0;
-        bool leaf = false, fail = false;
-        TP(6);
-        for (;;) {
-            int gs = game_status(s, R);
-            TP(7);
-            if (gs != ST_NOT_ENDED) {
-                float v = gs == ST_DRAW ? 0.0f : (gs == (int)s.cur ? 1.0f : -1.0f);
-                tree_backup(t, plen, v);
-                c.sims_done++;
-                k.sims++;
-                TP(5);
-                break;
-            }
-            uint64_t valid = valid_moves(s, R);
-            TP(8);
-            if (valid == 0) { fail = true; s.err = E_INVALID_ARGUMENT; break; }
-            uint32_t kd = ws_record_dword(s);
-            uint32_t h = key_hash(kd);
-            TP(9);
-            NodeRegs nr;
-            uint32_t idx = tree_lookup_node(t, kd, h, nr);
-            TP(10);
-            if (idx == NO_NODE) {  // leaf: hand the position to the NN service
-                encode88(s, E.leaf_in + slot * LEAF_STRIDE);
-                const uint32_t l = lane_id();
-                if (l < 16) reinterpret_cast<uint32_t*>(E.leaf_key + slot * GREC)[l] = kd;
-                if (l == 0) { E.leaf_valid[slot] = valid; E.leaf_hash[slot] = h; }
-                leaf = true;
-#ifdef AZR_EXP_LATE_FENCE
-                wave_mem_sync();   // (experiment: one fence per descent instead of one per level)
-#endif
-                TP(11);
-                break;
-            }
-            k.levels++;
-            uint32_t mv = tree_select<NOISE>(t, idx, nr, S, c.search_id, scratch, plen == 0, E.noise_eps, eta);
-            TP(12);
-            if (mv == NONE) { fail = true; s.err = E_LOGIC; break; }
-            uint32_t before = s.cur;
-#ifdef AZR_TREE_PROF
-            const uint32_t ph0 = s.phase;
-#endif
-            make_move(s, mv, R);
-#ifdef AZR_TREE_PROF
-            TP(ph0 == PH_FORTIFY ? 22 : ph0 == PH_ATTACK ? 23 : 13);
-#endif
-            if (s.err) { fail = true; break; }
-            if ((int)plen >= t.DMAX) { fail = true; s.err = AZR_E_CAPACITY; break; }
-            if (lane_id() == 0) t.path[plen] = idx | (mv << 16) | ((s.cur != before ? 1u : 0u) << 24);
-            plen++;
-        }
-        c.rng = s.rng;
-        if (fail) { err_out = s.err; return RD_FAIL; }
-        if (leaf) {
-            if (plen == 0) c.sims_started--;  // setRootState's root expansion is not one of the S simulations
-            c.pending |= 1u << th;
-            plen_set(c, th, plen);
-            return RD_LEAF;
-        }
-    }
-    return RD_DONE;
-}
-
-// One round of AlphaZeroMCTS::simulate for all T search threads of the game, in thread order: every thread without a
-// pending leaf runs descents until it blocks on the net.  RD_LEAF = at least one leaf is waiting; RD_DONE = the counter
-// is exhausted and every claimed simulation is backed up.
-template <bool NOISE>
-__device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out, float eta)
-{
-    for (int th = 0; th < E.T; th++) {
-        if ((c.pending >> th) & 1u) continue;
-        int r = run_descents<NOISE>(E, S, g, t, th, c, root, scratch, k, err_out, eta);
-        if (r == RD_FAIL) { c.pending = 0; return RD_FAIL; }
-        if (r == RD_LEAF && plen_get(c, th) == 0) break;  // root expansion: the threads start after setRootState
-    }
-    return c.pending ? RD_LEAF : RD_DONE;
-}
-
-// N[lane] and the legal mask of the node of `root` (NO_NODE if the root is not in the tree)
-__device__ __forceinline__ uint32_t root_node(const Tree& t, const WS& root, uint32_t& N, uint64_t& valid)
-{
-    uint32_t rkd = ws_record_dword(root);
-    uint32_t ridx = tree_lookup(t, rkd, key_hash(rkd));
-    N = 0; valid = 0;
-    if (ridx != NO_NODE) {
-        const uint8_t* n = node_ptr(t, ridx);
-        const uint32_t l = lane_id();
-        N = reinterpret_cast<const uint32_t*>(n + ND_N)[l < MOVES ? l : 0] & N_MASK;
-        valid = (uint64_t)rfl(*reinterpret_cast<const uint32_t*>(n + ND_VALID_LO)) |
-                ((uint64_t)rfl(*reinterpret_cast<const uint32_t*>(n + ND_VALID_HI)) << 32);
-    }
-    return ridx;
-}
-
-// the slot's next self-play game.  Unlimited mode: seeds base + g, base + G + g, ...  Quota mode (azr_selfplay_start_games,
-// Counter::hasNext of alphazero_trainer.cpp:83): the next game index is a ticket from one atomic counter — exactly
-// sp_quota games are started, seeds base .. base + sp_quota - 1, each game a function of its seed alone; a slot that
-// draws no ticket goes idle (mode 0).
-__device__ __forceinline__ void selfplay_next_game(const Dev& E, int g, const Tree& t, Ctl& c, WS& root)
-{
-    c.game_no++;
-    c.seed = E.base_seed + c.game_no * (uint32_t)E.G + (uint32_t)g;
-    if (E.sp_quota) {
-        unsigned long long ticket = 0;
-        if (lane_id() == 0) ticket = atomicAdd(E.sp_started, 1ull);
-        ticket = rfl64(ticket);
-        if (ticket >= E.sp_quota) { c.mode = 0; c.pending = 0; c.nsamples = 0; return; }
-        c.seed = E.base_seed + (uint32_t)ticket;
-    }
-    ws_blank(root);
-    root.rng = rng_seed(c.seed);
-    new_game(root);
-    c.rng = root.rng;
-    c.nsamples = 0; c.decisions = 0; c.sims_done = 0; c.sims_started = 0; c.pending = 0;
-    tree_clear(t, c);
-}
-
-// the noise vector of game g's NEW root (device self-play with azr_selfplay_set_dirichlet): drawn for (seed, decision) of the running
-// game over the root's legal moves, stored for azr_mcts_root_noise and handed to the descents; zeros for a slot that went idle
-__device__ __forceinline__ float new_root_noise(const Dev& E, int g, const Ctl& c, const WS& root)
-{
-    float eta = 0.0f;
-    if (c.mode != 0) eta = dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules));
-    if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
-    return eta;
-}
-
 // One tree step for game g: consume the pending leaf's (pi, v) [expand + backup], then run searches — and in
 // self-play mode decisions, moves and game restarts — until the next leaf that needs the net.
 // NOISE: root noise is in force (host-stepped: azr_mcts_set_root_noise's vector; self-play: a Dirichlet draw per new root).  The
@@ -539,16 +210,9 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             uint32_t N; uint64_t valid;
             uint32_t mv = NONE;
             if (root_node(t, root, N, valid) != NO_NODE) {
-                const uint32_t l = lane_id();
                 float pi = root_policy(N, valid);
                 mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
-                if (c.nsamples < (uint32_t)E.SCAP) {
-                    uint8_t* rec = E.stage + ((size_t)g * E.SCAP + c.nsamples) * STAGE_BYTES;
-                    encode88(root, rec);
-                    if (l < MOVES) reinterpret_cast<float*>(rec + 88)[l] = pi;
-                    if (l == 0) rec[260] = (uint8_t)root.cur;
-                    c.nsamples++;
-                } else k.ringdrop++;
+                stage_sample(E, g, c, root, pi, k);
             }
             TP(16);
             if (mv != NONE) make_move(root, mv, R); else root.err = E_LOGIC;
@@ -603,260 +267,9 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
     flush_counters(E, g, c, k, !SELFPLAY, cnt0);
     TP(21);
     // self-play tail (quota mode, slots going idle): the net of this pass runs on the waiting leaf slots only
-    if (SELFPLAY && E.sp_compact && c.pending) {
-        int base = 0;
-        if (lane_id() == 0) base = atomicAdd(&E.leaf_count[0], (int)__builtin_popcount(c.pending));   // one atomic per game
-        base = (int)rfl((uint32_t)base);
-        const uint32_t l = lane_id();
-        if (l < (uint32_t)E.T && ((c.pending >> l) & 1u)) E.leaf_list[base + (int)__builtin_popcount(c.pending & ((1u << l) - 1u))] = g * E.T + (int)l;
-    }
+    if (SELFPLAY && E.sp_compact) list_pending(E, g, c, &E.leaf_count[0], E.leaf_list);
     TP(15);
     TP_END();
-}
-
-// ================================================================================================
-// arena: GameGroup::playGames on the device (game/game.cpp:101-312).  One slot = one player pair = one "thread" of
-// the reference: games in mirrored pairs with alternating starts, AlphaZeroPlayer::takeTurn (alphazero_player.cpp:3-21)
-// through the search above, ScriptPlayer / RandomPlayer as wave-resident code (azr_players.hpp).
-// ================================================================================================
-// ring room for scripted collection (azr_arena_collect_scripted_samples): ring_count[1] = records flushed and not yet drained +
-// SCAP per game in progress.  A game is dealt only once its SCAP records are claimed, so a flush always lands inside the ring.
-__device__ __forceinline__ bool ring_reserve(const Dev& E)
-{
-    uint32_t ok = 0;
-    if (lane_id() == 0) {
-        unsigned long long* claim = E.ring_count + 1;
-        unsigned long long cur = atomicAdd(claim, 0ULL);
-        while (cur + (unsigned long long)E.SCAP <= E.ring_cap) {
-            const unsigned long long prev = atomicCAS(claim, cur, cur + (unsigned long long)E.SCAP);
-            if (prev == cur) { ok = 1; break; }
-            cur = prev;
-        }
-    }
-    return rfl(ok) != 0;
-}
-__device__ __forceinline__ void ring_release(const Dev& E, uint32_t n)
-{
-    if (lane_id() == 0 && n) atomicAdd(E.ring_count + 1, (unsigned long long)(-(long long)n));
-}
-
-// SREC: ScriptPlayer / RandomPlayer record their moves (StageRec); without it they get NoRec and this is the arena as it was
-template <bool SREC>
-__device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
-{
-    const int g = blockIdx.x;
-    if (E.lc_zero >= 0 && g == 0 && threadIdx.x < 2) E.leaf_count[E.lc_zero + threadIdx.x] = 0;   // the next pass's counts (the last readers are done)
-    Ctl c;
-    ctl_load(c, &E.ctl[g]);
-    if (c.mode != 3 || c.arena_state == 2) return;
-    const unsigned long long cnt0 = counters_begin(E, g);
-    Tree t = tree_of(E, g);
-    const Rules R = E.rules;
-    WS root;
-    ws_load(root, E.state + (size_t)g * GREC);
-    root.rng = c.rng;
-    ScriptW sp[2];
-    {
-        const ScriptW* src = reinterpret_cast<const ScriptW*>(E.script) + (size_t)g * 2;
-        sp[0] = src[0]; sp[1] = src[1];
-        sp[0].order = rfl(sp[0].order); sp[0].attacking_set = rfl(sp[0].attacking_set); sp[0].land_to = rfl(sp[0].land_to);
-        sp[0].land_from = rfl(sp[0].land_from); sp[0].attack_from_army = rfl(sp[0].attack_from_army);
-        sp[1].order = rfl(sp[1].order); sp[1].attacking_set = rfl(sp[1].attacking_set); sp[1].land_to = rfl(sp[1].land_to);
-        sp[1].land_from = rfl(sp[1].land_from); sp[1].attack_from_army = rfl(sp[1].attack_from_army);
-    }
-    StepCount k;
-    // two-net arena: the opponent AlphaZero player's own tree and its allocator state
-    const bool two = E.nodes2 != nullptr;
-    const Tree t2 = two ? tree2_of(E, g) : t;
-    TreeCtl x2 = {0, 0, 0};
-    if (two) {
-        const uint32_t w = E.tctl2[(size_t)g * 4 + (lane_id() & 3u)];
-        x2.search_id = rdl(w, 0); x2.nfree = rdl(w, 1); x2.hiwater = rdl(w, 2);
-    }
-    if (c.search_tree) { swap_tree_ctl(c, x2); consume_pending(E, g, t2, c, k); swap_tree_ctl(c, x2); }
-    else consume_pending(E, g, t, c, k);
-    for (;;) {
-        if (c.arena_state == 0 && E.arena_mirror == AZR_MIRROR_CONCURRENT) {
-            // Both games of a mirrored pair at the same time: slot 2j plays half 0 of slot pair j's k-th pair, slot 2j + 1 the
-            // mirrored half (include/azr.h).  Nothing in Game orders the two games (game.cpp:238-254); what they share is the
-            // deal (game.cpp:170-191), and the deal is a function of the pair's seed, so each half deals for itself.
-            const int L = E.G >> 1, lane = g >> 1;
-            const uint32_t half = (uint32_t)g & 1u;
-            const long long pr = (long long)lane + (long long)c.slot_games * L;   // pairs are assigned statically
-            const bool capped = E.arena_slot_cap > 0 && (int)c.slot_games >= E.arena_slot_cap;
-            if (capped || g >= 2 * L || pr >= (long long)(E.arena_total / 2)) { c.arena_state = 2; break; }
-            if (SREC && !ring_reserve(E)) break;   // no ring room for this game: wait for the next drain, the pair stays this slot's
-            const uint32_t pseed = E.base_seed + (uint32_t)pr;
-            root.rng = rng_seed(pseed);
-            new_game(root);
-            if (half) {   // Game::newGame's mirrored branch: invertPlayers of the pair's deal, player 1 starts, own dice stream
-                invert_players(root);
-                root.rng = rng_seed(pseed + (1u << 30));
-            }
-            root.cur = half;
-            c.player_start = half;
-            c.seed = pseed;
-            tree_clear(t, c);  // AlphaZeroPlayer::newGame
-            if (two) { swap_tree_ctl(c, x2); tree_clear(t2, c); swap_tree_ctl(c, x2); }
-            c.nsamples = 0;
-            c.sims_done = 0; c.sims_started = 0; c.search_active = 0; c.turn_started = 0; c.pending = 0;
-            c.arena_state = 1;
-        }
-        if (c.arena_state == 0) {  // Game::newGame (game.cpp:170-191) for the next Game::playGames(1)
-            if (SREC) {   // ring room first: a slot that has to wait takes nothing from the quota
-                const bool capped = c.pair_phase == 0 && E.arena_slot_cap > 0 && (int)c.slot_games >= E.arena_slot_cap;
-                if (!capped && !ring_reserve(E)) break;
-            }
-            if (c.pair_phase == 0) {  // Counter::hasNext(2) (game.cpp:14-26)
-                int taken = 0;
-                const bool capped = E.arena_slot_cap > 0 && (int)c.slot_games >= E.arena_slot_cap;
-                if (!capped && lane_id() == 0) taken = atomicAdd(E.arena_taken, 2);
-                taken = (int)rfl((uint32_t)taken);
-                if (capped || taken + 2 > E.arena_total) {
-                    if (SREC && !capped) ring_release(E, (uint32_t)E.SCAP);
-                    c.arena_state = 2;
-                    break;
-                }
-            }
-            if (E.arena_mirror && c.player_start != 0) {
-                uint32_t keep = root.rng;
-                ws_load(root, E.prev_start + (size_t)g * GREC);
-                root.rng = keep;
-                invert_players(root);
-                root.cur = c.player_start;
-            } else {
-                new_game(root);
-                root.cur = c.player_start;
-                ws_store(root, E.prev_start + (size_t)g * GREC);
-            }
-            tree_clear(t, c);  // AlphaZeroPlayer::newGame
-            if (two) { swap_tree_ctl(c, x2); tree_clear(t2, c); swap_tree_ctl(c, x2); }
-            c.nsamples = 0;
-            c.sims_done = 0; c.sims_started = 0; c.search_active = 0; c.turn_started = 0; c.pending = 0;
-            c.arena_state = 1;
-        }
-        // ---- Game::playTurn (game.cpp:112-133)
-        int gs = game_status(root, R);
-        if (gs != ST_NOT_ENDED) {  // GameResults::addGame (game.cpp:193-213)
-            if (lane_id() == 0) {
-                atomicAdd(&E.arena_res[0], 1);
-                if (gs == ST_DRAW) atomicAdd(&E.arena_res[1], 1);
-                if (gs == 0 || gs == 1) {
-                    atomicAdd(&E.arena_res[2 + 2 * gs], 1);
-                    if ((int)c.player_start == gs) atomicAdd(&E.arena_res[3 + 2 * gs], 1);
-                }
-                if (c.slot_games < (uint32_t)ALOG) {
-                    E.alog_status[(size_t)g * ALOG + c.slot_games] = (int8_t)gs;
-                    E.alog_rounds[(size_t)g * ALOG + c.slot_games] = (uint16_t)root.round;
-                }
-            }
-            if (c.slot_games < (uint32_t)ALOG) ws_store(root, E.alog_final + ((size_t)g * ALOG + c.slot_games) * GREC);
-            if (SREC) ring_release(E, (uint32_t)E.SCAP - c.nsamples);   // the game's n records stay claimed until they are drained
-            if ((SREC || E.arena_collect) && c.nsamples) {  // Player::gameFinished -> NNTrainDataStorage::updateValues for both players
-                wave_mem_sync();
-                flush_samples(E, g, c.nsamples, gs, k.ringdrop);
-                k.samples += c.nsamples;
-                c.nsamples = 0;
-            }
-            c.slot_games++;
-            k.games++;
-            c.player_start ^= 1u;  // Game::incPlayerStart (the concurrent form sets it per game)
-            c.pair_phase ^= 1u;
-            c.arena_state = 0;
-            continue;
-        }
-        const uint32_t p = root.cur;
-        const int kind = p == 0 ? E.kind0 : E.kind1;
-        bool fail = false;
-        if (kind == 1) {
-            if (SREC) {
-                const StageRec rec{E.stage + (size_t)g * E.SCAP * STAGE_BYTES, (uint32_t)E.SCAP, c.nsamples, k.ringdrop};
-                if (p == 0) script_take_turn(sp[0], root, R, rec); else script_take_turn(sp[1], root, R, rec);
-            } else {
-                if (p == 0) script_take_turn(sp[0], root, R, NoRec{}); else script_take_turn(sp[1], root, R, NoRec{});
-            }
-            fail = root.err != 0 || (root.cur == p && game_status(root, R) == ST_NOT_ENDED);  // "Turn was not incremented"
-        } else if (kind == 2) {
-            if (SREC) random_take_turn(root, R, StageRec{E.stage + (size_t)g * E.SCAP * STAGE_BYTES, (uint32_t)E.SCAP, c.nsamples, k.ringdrop});
-            else random_take_turn(root, R, NoRec{});
-            fail = root.err != 0 || (root.cur == p && game_status(root, R) == ST_NOT_ENDED);
-        } else {
-            const uint32_t w = kind == 3 ? 1u : 0u;   // which AlphaZeroPlayer: its tree and its network
-            const Tree& tt = w ? t2 : t;
-            if (w) swap_tree_ctl(c, x2);
-            // the player's own trimNodes at the start of a turn, setRootState's at the start of every search: at a turn's first decision
-            // both run back to back, which leaves an empty tree (tree_trim_twice)
-            if (!c.turn_started && !c.search_active) tree_trim_twice(tt, c);
-            else if (!c.turn_started || !c.search_active) tree_trim(tt, c);
-            c.turn_started = 1;
-            if (!c.search_active) { c.sims_done = 0; c.sims_started = 0; c.search_active = 1; }
-            c.search_tree = w;
-            c.rng = root.rng;
-            uint32_t err = 0;
-            // every AlphaZeroPlayer owns an AlphaZeroMCTS with its own Settings: player B's simulation count and PUCT constant
-            // (azr_arena_set_opponent_search); the noise term is shared, and it is the constant one: evaluation games are played
-            // without root noise, whatever azr_mcts_set_root_noise / azr_selfplay_set_dirichlet say
-            Search Sw = E.search;
-            if (w) { Sw.simulations = E.search2_simulations; Sw.hp = E.search2_hp; }
-            int r = search_round<false>(E, Sw, g, tt, c, root, scratch, k, err, 0.0f);
-            root.rng = c.rng;
-            if (r == RD_LEAF) { if (w) swap_tree_ctl(c, x2); break; }
-            if (r == RD_FAIL) { fail = true; root.err = err; }
-            else {
-                uint32_t N; uint64_t valid;
-                uint32_t mv = NONE;
-                if (root_node(tt, root, N, valid) != NO_NODE) {
-                    const float pi = root_policy(N, valid);
-                    mv = pick_highest(pi);
-                    if (E.arena_collect) {  // AlphaZeroPlayer::takeTurn with trainStorage set (alphazero_player.cpp:15-18)
-                        if (c.nsamples < (uint32_t)E.SCAP) {
-                            uint8_t* rec = E.stage + ((size_t)g * E.SCAP + c.nsamples) * STAGE_BYTES;
-                            encode88(root, rec);
-                            if (lane_id() < MOVES) reinterpret_cast<float*>(rec + 88)[lane_id()] = pi;
-                            if (lane_id() == 0) rec[260] = (uint8_t)root.cur;
-                            c.nsamples++;
-                        } else k.ringdrop++;
-                    }
-                }
-                if (mv != NONE) make_move(root, mv, R); else root.err = E_LOGIC;
-                c.search_active = 0;
-                c.last_move = mv;
-                k.dec++;
-                fail = root.err != 0;
-                if (root.cur != p || game_status(root, R) != ST_NOT_ENDED) c.turn_started = 0;
-            }
-            if (w) swap_tree_ctl(c, x2);
-        }
-        if (fail) {  // the reference would have thrown out of GameGroup: drop the game, start a fresh pair
-            k.err++;
-            c.error = root.err ? root.err : (uint32_t)E_LOGIC;
-            root.err = 0;
-            c.player_start = 0; c.pair_phase = 0; c.arena_state = 0;
-            c.pending = 0; c.search_active = 0; c.turn_started = 0;
-            if (E.arena_mirror == AZR_MIRROR_CONCURRENT) c.slot_games++;   // statically assigned: go on with the slot's next pair
-            if (SREC) { ring_release(E, (uint32_t)E.SCAP); c.nsamples = 0; }   // the game's staged records go with it
-        }
-    }
-    if (two && lane_id() == 0) { uint32_t* d2 = E.tctl2 + (size_t)g * 4; d2[0] = x2.search_id; d2[1] = x2.nfree; d2[2] = x2.hiwater; }
-    // hand every waiting leaf to the network of the player that is searching (list 0 when there is one network): a pass
-    // evaluates the listed slots only — most slots of an arena idle (scripted players' turns, finished quotas)
-    if (c.pending) {
-        const uint32_t tree = two ? c.search_tree : 0u;
-        int base = 0;
-        if (lane_id() == 0) base = atomicAdd(&E.leaf_count[E.lc_base + tree], (int)__builtin_popcount(c.pending));   // one atomic per slot
-        base = (int)rfl((uint32_t)base);
-        const uint32_t l = lane_id();
-        if (l < (uint32_t)E.T && ((c.pending >> l) & 1u))
-            E.leaf_list[(size_t)tree * E.G * E.T + base + (int)__builtin_popcount(c.pending & ((1u << l) - 1u))] = g * E.T + (int)l;
-    }
-    c.rng = root.rng;
-    ws_store(root, E.state + (size_t)g * GREC);
-    {
-        ScriptW* dst = reinterpret_cast<ScriptW*>(E.script) + (size_t)g * 2;
-        if (lane_id() == 0) { dst[0] = sp[0]; dst[1] = sp[1]; }
-    }
-    ctl_store(c, &E.ctl[g]);
-    flush_counters(E, g, c, k, false, cnt0);
 }
 
 __global__ __launch_bounds__(64) void k_arena_step(Dev E)
@@ -903,19 +316,9 @@ __global__ __launch_bounds__(64) void k_root_stats(Dev E, uint32_t* n_out, float
     Tree t = tree_of(E, g);
     WS root;
     ws_load(root, E.state + (size_t)g * GREC);
-    uint32_t kd = ws_record_dword(root);
-    uint32_t idx = tree_lookup(t, kd, key_hash(kd));
+    uint32_t N; uint64_t valid; float Q = 0, P = 0, pi = 0;
+    if (root_node(t, root, N, valid, &Q, &P) != NO_NODE) pi = root_policy(N, valid);
     const uint32_t l = lane_id();
-    uint32_t N = 0; float Q = 0, P = 0, pi = 0;
-    if (idx != NO_NODE) {
-        const uint8_t* n = node_ptr(t, idx);
-        N = reinterpret_cast<const uint32_t*>(n + ND_N)[l < MOVES ? l : 0] & N_MASK;
-        Q = reinterpret_cast<const float*>(n + ND_Q)[l < MOVES ? l : 0];
-        P = reinterpret_cast<const float*>(n + ND_P)[l < MOVES ? l : 0];
-        uint64_t valid = (uint64_t)rfl(*reinterpret_cast<const uint32_t*>(n + ND_VALID_LO)) |
-                         ((uint64_t)rfl(*reinterpret_cast<const uint32_t*>(n + ND_VALID_HI)) << 32);
-        pi = root_policy(N, valid);
-    }
     if (l < MOVES) {
         if (n_out) n_out[(size_t)g * MOVES + l] = N;
         if (q_out) q_out[(size_t)g * MOVES + l] = Q;
@@ -933,15 +336,9 @@ __global__ __launch_bounds__(64) void k_pick(Dev E, int sample, uint8_t* moves)
     WS root;
     ws_load(root, E.state + (size_t)g * GREC);
     root.rng = c.rng;
-    uint32_t kd = ws_record_dword(root);
-    uint32_t idx = tree_lookup(t, kd, key_hash(kd));
+    uint32_t N; uint64_t valid;
     uint32_t mv = NONE;
-    if (idx != NO_NODE) {
-        const uint8_t* n = node_ptr(t, idx);
-        const uint32_t l = lane_id();
-        uint32_t N = reinterpret_cast<const uint32_t*>(n + ND_N)[l < MOVES ? l : 0] & N_MASK;
-        uint64_t valid = (uint64_t)rfl(*reinterpret_cast<const uint32_t*>(n + ND_VALID_LO)) |
-                         ((uint64_t)rfl(*reinterpret_cast<const uint32_t*>(n + ND_VALID_HI)) << 32);
+    if (root_node(t, root, N, valid) != NO_NODE) {
         float pi = root_policy(N, valid);
         mv = sample ? pick_random(root, pi) : pick_highest(pi);
     }
@@ -1163,7 +560,8 @@ extern "C" int azr_engine_destroy(azr_engine* h)
     dp_free(h);
     train_free(h);
     net_free(h);
-    for (hipEvent_t e : h->ev) hipEventDestroy(e);
+    for (const ProfEvents& e : h->ev)
+        for (hipEvent_t x : {e.tree0, e.tree1, e.net1, e.tower0, e.tower1}) if (x) hipEventDestroy(x);
 #ifdef AZR_TREE_PROF
     {
         unsigned long long t[25] = {0}, u[25] = {0}, hh[16] = {0};
@@ -1212,14 +610,30 @@ struct DevBuf {
         HIPCHK(h, hipGetLastError());                                                 \
     } while (0)
 // the arena step of this handle: with the scripted players' recorder (azr_arena_collect_scripted_samples) or without
-#define ARENA_STEP(h, dev)                                                       \
-    do {                                                                         \
-        if ((h)->arena_rec) LAUNCH(h, k_arena_step_rec, dev);                    \
-        else LAUNCH(h, k_arena_step, dev);                                       \
+#define ARENA_STEP(h, dev) LAUNCH(h, (h)->arena_rec ? k_arena_step_rec : k_arena_step, dev)
+// a boundary call that hands back one array: `kern(args..., buf)` fills a temporary device buffer of `bytes`, copied out to `dst`
+#define LAUNCH_OUT(h, dst, bytes, T, kern, ...)              \
+    do {                                                     \
+        DevBuf buf_;                                          \
+        HIPCHK(h, buf_.alloc(bytes));                         \
+        LAUNCH(h, kern, __VA_ARGS__, (T*)buf_.p);             \
+        D2H(h, dst, buf_.p, bytes);                           \
+        SYNC(h);                                             \
     } while (0)
 #define ENTER(h)                                 \
     if (!(h)) return AZR_E_BAD_HANDLE;           \
     HIPCHK(h, hipSetDevice((h)->cfg.device))
+
+// one 32-bit field of every game's Ctl line <-> a packed host array of G values (`field` = offsetof(Ctl, ...)): a strided copy queued on
+// the handle's stream, the caller synchronises
+static hipError_t ctl_field_get(azr_engine* h, size_t field, void* dst)
+{
+    return hipMemcpy2DAsync(dst, 4, (const uint8_t*)h->d.ctl + field, sizeof(Ctl), 4, h->d.G, hipMemcpyDeviceToHost, h->stream);
+}
+static hipError_t ctl_field_set(azr_engine* h, size_t field, const void* src)
+{
+    return hipMemcpy2DAsync((uint8_t*)h->d.ctl + field, sizeof(Ctl), src, 4, 4, h->d.G, hipMemcpyHostToDevice, h->stream);
+}
 
 extern "C" int azr_engine_new_games(azr_engine* h, const uint32_t* seeds)
 {
@@ -1250,11 +664,7 @@ extern "C" int azr_engine_get_states(azr_engine* h, void* data160)
 {
     ENTER(h);
     if (!data160) return AZR_E_INVALID_ARGUMENT;
-    DevBuf b;
-    HIPCHK(h, b.alloc((size_t)h->d.G * 160));
-    LAUNCH(h, k_export160, h->d, (const uint8_t*)h->d.state, (uint8_t*)b.p);
-    D2H(h, data160, b.p, (size_t)h->d.G * 160);
-    SYNC(h);
+    LAUNCH_OUT(h, data160, (size_t)h->d.G * 160, uint8_t, k_export160, h->d, (const uint8_t*)h->d.state);
     return AZR_OK;
 }
 
@@ -1262,7 +672,7 @@ extern "C" int azr_engine_set_rng(azr_engine* h, const uint32_t* st)
 {
     ENTER(h);
     if (!st) return AZR_E_INVALID_ARGUMENT;
-    HIPCHK(h, hipMemcpy2DAsync(&h->d.ctl[0].rng, sizeof(Ctl), st, 4, 4, h->d.G, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, ctl_field_set(h, offsetof(Ctl, rng), st));
     SYNC(h);
     return AZR_OK;
 }
@@ -1271,7 +681,7 @@ extern "C" int azr_engine_get_rng(azr_engine* h, uint32_t* st)
 {
     ENTER(h);
     if (!st) return AZR_E_INVALID_ARGUMENT;
-    HIPCHK(h, hipMemcpy2DAsync(st, 4, &h->d.ctl[0].rng, sizeof(Ctl), 4, h->d.G, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, ctl_field_get(h, offsetof(Ctl, rng), st));
     SYNC(h);
     return AZR_OK;
 }
@@ -1280,11 +690,7 @@ extern "C" int azr_engine_valid_moves(azr_engine* h, uint64_t* masks)
 {
     ENTER(h);
     if (!masks) return AZR_E_INVALID_ARGUMENT;
-    DevBuf b;
-    HIPCHK(h, b.alloc((size_t)h->d.G * 8));
-    LAUNCH(h, k_valid_moves, h->d, (uint64_t*)b.p);
-    D2H(h, masks, b.p, (size_t)h->d.G * 8);
-    SYNC(h);
+    LAUNCH_OUT(h, masks, (size_t)h->d.G * 8, uint64_t, k_valid_moves, h->d);
     return AZR_OK;
 }
 
@@ -1312,11 +718,7 @@ extern "C" int azr_engine_status(azr_engine* h, int8_t* status)
 {
     ENTER(h);
     if (!status) return AZR_E_INVALID_ARGUMENT;
-    DevBuf b;
-    HIPCHK(h, b.alloc(h->d.G));
-    LAUNCH(h, k_status, h->d, (int8_t*)b.p);
-    D2H(h, status, b.p, (size_t)h->d.G);
-    SYNC(h);
+    LAUNCH_OUT(h, status, (size_t)h->d.G, int8_t, k_status, h->d);
     return AZR_OK;
 }
 
@@ -1359,11 +761,19 @@ extern "C" int azr_mcts_begin(azr_engine* h)
     return AZR_OK;
 }
 
+// the k_tree_step instantiation of a host-stepped search (azr_mcts_*) or of device self-play, with or without root noise
+static hipError_t launch_tree_step(azr_engine* h, bool selfplay, bool noise)
+{
+    void (*const step)(Dev) = selfplay ? (noise ? k_tree_step<true, true> : k_tree_step<true, false>)
+                                       : (noise ? k_tree_step<false, true> : k_tree_step<false, false>);
+    hipLaunchKernelGGL(step, dim3(h->d.G), dim3(64), 0, h->stream, h->d);
+    return hipGetLastError();
+}
+
 static int tree_step_host(azr_engine* h, uint32_t* active)
 {
     HIPCHK(h, hipMemsetAsync(h->d.active, 0, 4, h->stream));
-    if (h->noise_host) LAUNCH(h, (k_tree_step<false, true>), h->d);
-    else LAUNCH(h, (k_tree_step<false, false>), h->d);
+    HIPCHK(h, launch_tree_step(h, false, h->noise_host));
     D2H(h, active, h->d.active, 4);
     SYNC(h);
     return AZR_OK;
@@ -1379,7 +789,7 @@ extern "C" int azr_mcts_leaves(azr_engine* h, void* in88, uint8_t* need, int* ac
     if (in88) HIPCHK(h, hipMemcpy2DAsync(in88, 88, h->d.leaf_in, LEAF_STRIDE, 88, (size_t)G * T, hipMemcpyDeviceToHost, h->stream));
     if (need) {
         std::vector<uint32_t> p(G);
-        HIPCHK(h, hipMemcpy2DAsync(p.data(), 4, &h->d.ctl[0].pending, sizeof(Ctl), 4, G, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, ctl_field_get(h, offsetof(Ctl, pending), p.data()));
         SYNC(h);
         for (int g = 0; g < G; g++)
             for (int k = 0; k < T; k++) need[g * T + k] = (uint8_t)((p[g] >> k) & 1u);
@@ -1416,7 +826,7 @@ extern "C" int azr_mcts_simulate(azr_engine* h)
     }
     // surface per-game errors
     std::vector<uint32_t> e(h->d.G);
-    HIPCHK(h, hipMemcpy2DAsync(e.data(), 4, &h->d.ctl[0].error, sizeof(Ctl), 4, h->d.G, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, ctl_field_get(h, offsetof(Ctl, error), e.data()));
     SYNC(h);
     for (int g = 0; g < h->d.G; g++)
         if (e[g]) { h->err = "search error in game " + std::to_string(g) + " code " + std::to_string(e[g]); return (int)e[g]; }
@@ -1441,12 +851,7 @@ extern "C" int azr_mcts_policy(azr_engine* h, float* pi)
 {
     ENTER(h);
     if (!pi) return AZR_E_INVALID_ARGUMENT;
-    const size_t sz = (size_t)h->d.G * MOVES * 4;
-    DevBuf b;
-    HIPCHK(h, b.alloc(sz));
-    LAUNCH(h, k_root_stats, h->d, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)b.p);
-    D2H(h, pi, b.p, sz);
-    SYNC(h);
+    LAUNCH_OUT(h, pi, (size_t)h->d.G * MOVES * 4, float, k_root_stats, h->d, (uint32_t*)nullptr, (float*)nullptr, (float*)nullptr);
     return AZR_OK;
 }
 
@@ -1454,11 +859,7 @@ extern "C" int azr_mcts_pick(azr_engine* h, int sample, uint8_t* moves)
 {
     ENTER(h);
     if (!moves) return AZR_E_INVALID_ARGUMENT;
-    DevBuf b;
-    HIPCHK(h, b.alloc(h->d.G));
-    LAUNCH(h, k_pick, h->d, sample, (uint8_t*)b.p);
-    D2H(h, moves, b.p, (size_t)h->d.G);
-    SYNC(h);
+    LAUNCH_OUT(h, moves, (size_t)h->d.G, uint8_t, k_pick, h->d, sample);
     return AZR_OK;
 }
 
@@ -1574,13 +975,10 @@ extern "C" int azr_selfplay_run(azr_engine* h, int passes)
     if (!h->weights_set) { h->err = "azr_selfplay_run: no weights"; return AZR_E_STATE; }
     // launches timed with HIP events, spread evenly over the run.  A sample, not every pass: an event is a marker packet the
     // queue has to retire, and five of them per pass cost ~18 us of a 1.1 ms pass.
-    const int PROF_MAX = 24;
     const int nprof = std::min(passes, PROF_MAX);
-    while ((int)h->ev.size() < 5 * PROF_MAX) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreate(&e));
-        h->ev.push_back(e);
-    }
+    for (ProfEvents& e : h->ev)
+        for (hipEvent_t* x : {&e.tree0, &e.tree1, &e.net1, &e.tower0, &e.tower1})
+            if (!*x) HIPCHK(h, hipEventCreate(x));
     const int stride = passes > nprof ? passes / nprof : 1;
     int k = 0;
     const int GT = h->d.G * h->d.T;
@@ -1599,34 +997,35 @@ extern "C" int azr_selfplay_run(azr_engine* h, int passes)
         const int* map = nullptr;
         const bool prof = (p % stride == 0) && k < nprof;
         if (h->sp_tail) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, sizeof(int), h->stream));
-        if (prof) HIPCHK(h, hipEventRecord(h->ev[3 * k + 0], h->stream));
-        if (h->sp_noise) LAUNCH(h, (k_tree_step<true, true>), h->d);
-        else LAUNCH(h, (k_tree_step<true, false>), h->d);
-        if (prof) HIPCHK(h, hipEventRecord(h->ev[3 * k + 1], h->stream));
+        const ProfEvents* ev = prof ? &h->ev[k] : nullptr;   // this pass's events, if it is a sampled one
+        if (ev) HIPCHK(h, hipEventRecord(ev->tree0, h->stream));
+        HIPCHK(h, launch_tree_step(h, true, h->sp_noise));
+        if (ev) HIPCHK(h, hipEventRecord(ev->tree1, h->stream));
         if (h->sp_tail) {
             D2H(h, &n_eval, h->d.leaf_count, sizeof(int));
             SYNC(h);
             map = h->d.leaf_list;
             if (n_eval == 0) {   // nothing waits for the net: every game of the quota is over
-                if (prof) { HIPCHK(h, hipEventRecord(h->ev[3 * k + 2], h->stream)); h->pe_tower0 = h->pe_tower1 = nullptr; }
+                if (ev) HIPCHK(h, hipEventRecord(ev->net1, h->stream));
                 break;
             }
         }
-        h->pe_tower0 = prof ? h->ev[3 * PROF_MAX + 2 * k] : nullptr;
-        h->pe_tower1 = prof ? h->ev[3 * PROF_MAX + 2 * k + 1] : nullptr;
+        h->pe_tower0 = ev ? ev->tower0 : nullptr;
+        h->pe_tower1 = ev ? ev->tower1 : nullptr;
         int rc = net_forward_ex(h, h->d.leaf_in, LEAF_STRIDE, n_eval, h->d.net_pi, h->d.net_v, map, h->stream);
         h->pe_tower0 = h->pe_tower1 = nullptr;
         if (rc) return rc;
-        if (prof) { HIPCHK(h, hipEventRecord(h->ev[3 * k + 2], h->stream)); k++; }
+        if (ev) { HIPCHK(h, hipEventRecord(ev->net1, h->stream)); k++; }
     }
     SYNC(h);
     double tn = 0, tt = 0, tw = 0;
     const bool tower_timed = h->cfg.net_dtype == AZR_NET_BF16 || h->cfg.net_dtype == AZR_NET_F32X || h->cfg.net_dtype == AZR_NET_F16;   // one kernel = one net forward, bracketed by events
     for (int i = 0; i < k; i++) {
         float a = 0, b = 0, c = 0;
-        HIPCHK(h, hipEventElapsedTime(&a, h->ev[3 * i + 0], h->ev[3 * i + 1]));
-        HIPCHK(h, hipEventElapsedTime(&b, h->ev[3 * i + 1], h->ev[3 * i + 2]));
-        if (tower_timed) HIPCHK(h, hipEventElapsedTime(&c, h->ev[3 * PROF_MAX + 2 * i], h->ev[3 * PROF_MAX + 2 * i + 1]));
+        const ProfEvents& ev = h->ev[i];
+        HIPCHK(h, hipEventElapsedTime(&a, ev.tree0, ev.tree1));
+        HIPCHK(h, hipEventElapsedTime(&b, ev.tree1, ev.net1));
+        if (tower_timed) HIPCHK(h, hipEventElapsedTime(&c, ev.tower0, ev.tower1));
         tt += a; tn += b; tw += c;
     }
     h->prof_tower_ms = k ? (float)(tw / k) : 0;
@@ -1679,13 +1078,21 @@ extern "C" int azr_selfplay_counters(azr_engine* h, azr_counters* out)
     return AZR_OK;
 }
 
+// records in the ring (the counter runs past the capacity when flushes were dropped)
+static int ring_fill(azr_engine* h, unsigned long long* n)
+{
+    D2H(h, n, h->d.ring_count, 8);
+    SYNC(h);
+    if (*n > h->d.ring_cap) *n = h->d.ring_cap;
+    return AZR_OK;
+}
+
 extern "C" int azr_samples_drain(azr_engine* h, void* rec265, size_t cap, size_t* n_out)
 {
     ENTER(h);
     unsigned long long n = 0;
-    D2H(h, &n, h->d.ring_count, 8);
-    SYNC(h);
-    if (n > h->d.ring_cap) n = h->d.ring_cap;
+    int rc = ring_fill(h, &n);
+    if (rc) return rc;
     if (!rec265) cap = (size_t)n;   // no buffer: discard everything (reset of the ring)
     size_t take = std::min((size_t)n, cap);
     if (take && rec265) D2H(h, rec265, h->d.ring, take * AZR_RECORD_BYTES);
@@ -1714,9 +1121,8 @@ extern "C" int azr_samples_device_view(azr_engine* h, void** dev_ptr, size_t* n_
 {
     ENTER(h);
     unsigned long long n = 0;
-    D2H(h, &n, h->d.ring_count, 8);
-    SYNC(h);
-    if (n > h->d.ring_cap) n = h->d.ring_cap;
+    int rc = ring_fill(h, &n);
+    if (rc) return rc;
     if (dev_ptr) *dev_ptr = h->d.ring;
     if (n_out) *n_out = (size_t)n;
     return AZR_OK;
@@ -1726,9 +1132,8 @@ extern "C" int azr_samples_copy_device(azr_engine* h, void* dst_device, size_t c
 {
     ENTER(h);
     unsigned long long n = 0;
-    D2H(h, &n, h->d.ring_count, 8);
-    SYNC(h);
-    if (n > h->d.ring_cap) n = h->d.ring_cap;
+    int rc = ring_fill(h, &n);
+    if (rc) return rc;
     const size_t take = std::min((size_t)n, cap);
     if (take && !dst_device) return AZR_E_INVALID_ARGUMENT;
     if (take) HIPCHK(h, hipMemcpyAsync(dst_device, h->d.ring, take * AZR_RECORD_BYTES, hipMemcpyDeviceToDevice, h->stream));
@@ -1786,12 +1191,23 @@ extern "C" int azr_arena_start(azr_engine* h, int player1, int player2, int game
     return AZR_OK;
 }
 
+// slots that have played out their share of the arena (arena_state 2)
+static int arena_idle_slots(azr_engine* h, int* idle)
+{
+    std::vector<uint32_t> st(h->d.G);
+    HIPCHK(h, ctl_field_get(h, offsetof(Ctl, arena_state), st.data()));
+    SYNC(h);
+    *idle = (int)std::count(st.begin(), st.end(), 2u);
+    return AZR_OK;
+}
+
 extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
 {
     ENTER(h);
     if (h->mode != 3) { h->err = "azr_arena_run: call azr_arena_start first"; return AZR_E_STATE; }
-    const bool needs_net = h->d.kind0 == AZR_PLAYER_ALPHAZERO || h->d.kind1 == AZR_PLAYER_ALPHAZERO;
     const int GT = h->d.G * h->d.T;
+    const bool needs_net = h->d.kind0 == AZR_PLAYER_ALPHAZERO || h->d.kind1 == AZR_PLAYER_ALPHAZERO;
+    const bool any_net = needs_net || h->d.nodes2;   // (neither: scripted players only, a pass is the step alone)
     // Up to 256 waiting leaves on the 16-bit towers and the NET_F32X tower, in any pairing of them: the net launches read the tree step's
     // leaf counts from device memory themselves (net_forward_counted), so a pass is queued without a read-back and the host looks at the
     // slots' states once per CHUNK passes — the passes of a slot that went idle meanwhile end at their first instruction.  An arena with a
@@ -1800,14 +1216,15 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
     const int NB_MAX = std::min(h->d.G, std::max(1, h->d.arena_total)) * h->d.T;
     const int form = hook_env_int("AZR_ARENA_COUNTED", 1);
     const bool can_count = net_forward_counted_ok(h, NB_MAX) && (!h->d.nodes2 || net_forward_counted_ok(h->opponent, NB_MAX));
-    const bool counted = form != 0 && can_count;
-    if (form == 2 && !can_count && (needs_net || h->d.nodes2)) { h->err = "azr_arena_run: AZR_ARENA_COUNTED=2 and this arena reads back"; return AZR_E_STATE; }
-    if (counted && (needs_net || h->d.nodes2)) {
-        constexpr int CHUNK = 16;
-        if (!h->arena_ev) HIPCHK(h, hipEventCreateWithFlags(&h->arena_ev, hipEventDisableTiming));
-        if (!h->arena_ev2) HIPCHK(h, hipEventCreateWithFlags(&h->arena_ev2, hipEventDisableTiming));
-        std::vector<uint32_t> st0(h->d.G);
-        for (int p = 0; p < passes; p++) {
+    const bool counted = form != 0 && can_count && any_net;
+    if (form == 2 && !can_count && any_net) { h->err = "azr_arena_run: AZR_ARENA_COUNTED=2 and this arena reads back"; return AZR_E_STATE; }
+    constexpr int CHUNK = 16;
+    if (h->d.nodes2 && !h->arena_ev) HIPCHK(h, hipEventCreateWithFlags(&h->arena_ev, hipEventDisableTiming));
+    if (h->d.nodes2 && counted && !h->arena_ev2) HIPCHK(h, hipEventCreateWithFlags(&h->arena_ev2, hipEventDisableTiming));
+    int idle = 0;
+    for (int p = 0; p < passes; p++) {
+        bool look;   // at the slots' states after this pass: the arena may be over
+        if (counted) {
             // the counts of this pass go to row (pass & 1) of leaf_count — zero since the pass before the last (or azr_arena_start) — and the
             // step zeroes the other row for the next pass: no memset between a pass's launches either
             const int row = 2 * (int)(h->arena_pass++ & 1u);
@@ -1832,29 +1249,21 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
             int rc = net_forward_counted(h, h->d.leaf_in, LEAF_STRIDE, NB_MAX, cnt_dev, beside ? cnt_dev + 1 : nullptr, wgpp_opp, h->d.net_pi, h->d.net_v, h->d.leaf_list, h->stream);
             if (rc) return rc;
             if (h->d.nodes2) HIPCHK(h, hipStreamWaitEvent(h->stream, h->arena_ev, 0));
-            if (p % CHUNK == CHUNK - 1 && p + 1 < passes) {
-                HIPCHK(h, hipMemcpy2DAsync(st0.data(), 4, &h->d.ctl[0].arena_state, sizeof(Ctl), 4, h->d.G, hipMemcpyDeviceToHost, h->stream));
-                SYNC(h);
-                bool all_idle = true;
-                for (uint32_t v : st0) all_idle = all_idle && v == 2;
-                if (all_idle) break;
-            }
-        }
-    } else
-    if (h->d.nodes2) {  // two networks: every pass evaluates each net on the leaves of its own player only
-        if (!h->arena_ev) HIPCHK(h, hipEventCreateWithFlags(&h->arena_ev, hipEventDisableTiming));
-        for (int p = 0; p < passes; p++) {
-            HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, 2 * sizeof(int), h->stream));
-            ARENA_STEP(h, h->d);
+            look = p % CHUNK == CHUNK - 1 && p + 1 < passes;
+        } else {   // one count read-back per pass: every net evaluates the waiting leaf slots of its own player only
             int cnt[2] = {0, 0};
-            D2H(h, cnt, h->d.leaf_count, sizeof cnt);
-            SYNC(h);
-            if (cnt[0] == 0 && cnt[1] == 0) break;  // every slot is idle: the quota is exhausted
+            const size_t words = !any_net ? 0 : h->d.nodes2 ? sizeof cnt : sizeof cnt[0];   // the count words in play: one per net
+            if (words) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, words, h->stream));
+            ARENA_STEP(h, h->d);
+            if (words) {
+                D2H(h, cnt, h->d.leaf_count, words);
+                SYNC(h);
+            }
             // The two launches are independent (own weights, disjoint leaf slots) and small — an arena of 100 games is
             // 1 board per workgroup on fewer than half of the CUs each — so they run side by side: this net on this
             // handle's stream, the opponent's on the opponent's; the next tree step waits for both.  (The tree step that
             // wrote the leaves has completed: the count read-back above synchronised the stream.)
-            int rc = net_forward_ex(h, h->d.leaf_in, LEAF_STRIDE, cnt[0], h->d.net_pi, h->d.net_v, h->d.leaf_list, h->stream);
+            int rc = net_forward_ex(h, h->d.leaf_in, LEAF_STRIDE, cnt[0], h->d.net_pi, h->d.net_v, h->d.leaf_list, h->stream);   // (no launch for a count of 0)
             if (rc) return rc;
             if (cnt[1] > 0) {
                 rc = net_forward_ex(h->opponent, h->d.leaf_in, LEAF_STRIDE, cnt[1], h->d.net_pi, h->d.net_v, h->d.leaf_list + GT, h->opponent->stream);
@@ -1862,34 +1271,17 @@ extern "C" int azr_arena_run(azr_engine* h, int passes, int* finished_out)
                 HIPCHK(h, hipEventRecord(h->arena_ev, h->opponent->stream));
                 HIPCHK(h, hipStreamWaitEvent(h->stream, h->arena_ev, 0));
             }
+            // nobody waits for a net: either every slot is idle (quota exhausted), or only scripted players moved or waited for ring room
+            look = any_net && cnt[0] == 0 && cnt[1] == 0;
         }
-    } else
-    for (int p = 0; p < passes; p++) {
-        if (needs_net) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, sizeof(int), h->stream));
-        ARENA_STEP(h, h->d);
-        if (needs_net) {   // one network: evaluate the waiting leaf slots only (one count read-back per pass)
-            int cnt = 0;
-            D2H(h, &cnt, h->d.leaf_count, sizeof cnt);
-            SYNC(h);
-            if (cnt == 0) {
-                // nobody waits for the net: either every slot is idle (quota exhausted) or only scripted players moved
-                std::vector<uint32_t> st0(h->d.G);
-                HIPCHK(h, hipMemcpy2DAsync(st0.data(), 4, &h->d.ctl[0].arena_state, sizeof(Ctl), 4, h->d.G, hipMemcpyDeviceToHost, h->stream));
-                SYNC(h);
-                bool all_idle = true;
-                for (uint32_t v : st0) all_idle = all_idle && v == 2;
-                if (all_idle) break;
-                continue;
-            }
-            int rc = net_forward_ex(h, h->d.leaf_in, LEAF_STRIDE, cnt, h->d.net_pi, h->d.net_v, h->d.leaf_list, h->stream);
+        if (look) {
+            int rc = arena_idle_slots(h, &idle);
             if (rc) return rc;
+            if (idle == h->d.G) break;
         }
     }
-    std::vector<uint32_t> st(h->d.G);
-    HIPCHK(h, hipMemcpy2DAsync(st.data(), 4, &h->d.ctl[0].arena_state, sizeof(Ctl), 4, h->d.G, hipMemcpyDeviceToHost, h->stream));
-    SYNC(h);
-    int idle = 0;
-    for (uint32_t v : st) idle += v == 2;
+    int rc = arena_idle_slots(h, &idle);
+    if (rc) return rc;
     if (idle == h->d.G) h->arena_open = false;
     if (finished_out) *finished_out = idle == h->d.G;
     return AZR_OK;
@@ -1992,8 +1384,7 @@ extern "C" int azr_arena_log(azr_engine* h, int32_t* games_per_slot, int8_t* sta
 {
     ENTER(h);
     const int G = h->d.G;
-    if (games_per_slot)
-        HIPCHK(h, hipMemcpy2DAsync(games_per_slot, 4, &h->d.ctl[0].slot_games, sizeof(Ctl), 4, G, hipMemcpyDeviceToHost, h->stream));
+    if (games_per_slot) HIPCHK(h, ctl_field_get(h, offsetof(Ctl, slot_games), games_per_slot));
     if (status) D2H(h, status, h->d.alog_status, (size_t)G * ALOG);
     if (rounds) D2H(h, rounds, h->d.alog_rounds, (size_t)G * ALOG * 2);
     if (finals160) {

@@ -131,6 +131,13 @@ struct NetDev {
     float* actT;       // [G][42][256]
 };
 
+// the events of one sampled pass of azr_selfplay_run, in stream order: the tree step begins / ends (= the net begins), around the net's
+// dominant kernel (pe_tower0 / pe_tower1 below), the net ends
+struct ProfEvents {
+    hipEvent_t tree0, tree1, net1, tower0, tower1;
+};
+constexpr int PROF_MAX = 24;   // sampled passes per run
+
 }  // namespace azr
 
 struct azr_engine {
@@ -141,8 +148,8 @@ struct azr_engine {
     std::string err;
     std::vector<float> flat;      // AZRW host copy
     int mode;                     // 0 rules only / stepwise, 2 self-play
-    // profiling of the last azr_selfplay_run
-    std::vector<hipEvent_t> ev;
+    // profiling of the last azr_selfplay_run: one set of events per sampled pass, created by the first run
+    azr::ProfEvents ev[azr::PROF_MAX] = {};
     float prof_net_ms, prof_tree_ms, prof_tower_ms;
     hipEvent_t pe_tower0 = nullptr, pe_tower1 = nullptr;  // when set, the net records these around its dominant kernel
     int prof_launches;

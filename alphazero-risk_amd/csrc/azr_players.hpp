@@ -40,7 +40,7 @@ struct NoRec {
     __device__ __forceinline__ void operator()(const WS&, uint32_t) const {}
 };
 // StageRec stages (encode88(s), one-hot pi = e_move over 43 entries, player = s.cur) into the slot's staging buffer, in the
-// layout the AlphaZero decisions use (azr_engine.hip, k_arena_step); a record past the buffer's end is counted, not staged
+// layout the AlphaZero decisions use (stage_sample, azr_search.hpp); a record past the buffer's end is counted, not staged
 struct StageRec {
     uint8_t* stage;              // the slot's [cap][STAGE_BYTES]
     uint32_t cap;

@@ -385,9 +385,7 @@ __device__ __forceinline__ uint32_t tree_select(const Tree& t, uint32_t idx, con
     }
     const uint32_t mv = (ties & (ties - 1)) == 0 ? (uint32_t)ctz64(ties) : umap_first(valid, ties, scratch);
     if (l == mv) reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(n) + ND_N)[l] = W + ACT_ONE;  // sv.active_N++
-#ifndef AZR_EXP_LATE_FENCE
     wave_mem_sync();
-#endif
     return mv;
 }
 // NNOutputData::normalize (alphazero_nn_data.cpp:3-27): sequential fp32 sum over the legal entries, index order
