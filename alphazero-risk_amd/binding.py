@@ -84,6 +84,7 @@ EXPORTS = [
     "azr_device_synchronize", "azr_debug_tower_clock", "azr_debug_tower_trace", "azr_debug_tower_plan", "azr_arena_start", "azr_arena_run", "azr_arena_results", "azr_arena_log",
     "azr_arena_set_opponent_net", "azr_arena_set_opponent_search", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
     "azr_mcts_set_root_noise", "azr_selfplay_set_dirichlet", "azr_mcts_root_noise", "azr_debug_root_noise",
+    "azr_selfplay_set_playout_cap", "azr_selfplay_decision_kind", "azr_debug_playout_cap",
 ]
 
 
@@ -154,6 +155,9 @@ def load_library(test_hooks=False):
         L.azr_selfplay_set_dirichlet.argtypes = [C.c_void_p, C.c_float, C.c_uint32]
         L.azr_mcts_root_noise.argtypes = [C.c_void_p, C.c_void_p]
         L.azr_debug_root_noise.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.azr_selfplay_set_playout_cap.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_uint32]
+        L.azr_selfplay_decision_kind.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_debug_playout_cap.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _libs[test_hooks] = L
         if not test_hooks:
             _lib = L
@@ -441,6 +445,28 @@ class Engine:
         e = np.zeros((len(s), MOVES), np.float32)
         self._chk(self.L.azr_debug_root_noise(self.h, float(alpha), int(noise_seed), _p(s), _p(d), _p(v), len(s), _p(e)))
         return e
+
+    # ---- playout cap (this engine's own; off = every decision gets the whole budget and a record)
+    def selfplay_set_playout_cap(self, full_prob, fast_simulations, cap_seed=0):
+        """device self-play: a decision is full (mcts_simulations, sampled root noise, a record) with probability full_prob by a coin of
+        (cap_seed, game seed, decision), else fast (fast_simulations, the constant noise, no record); full_prob >= 1 or
+        fast_simulations <= 0 = off; read by selfplay_start*"""
+        self._chk(self.L.azr_selfplay_set_playout_cap(self.h, float(full_prob), int(fast_simulations), int(cap_seed)))
+
+    def decision_kind(self):
+        """1 = full, 0 = fast for each slot's current decision, [G] uint8; all 1 without a cap or outside self-play"""
+        k = np.zeros(self.G, np.uint8)
+        self._chk(self.L.azr_selfplay_decision_kind(self.h, _p(k)))
+        return k
+
+    def debug_playout_cap(self, full_prob, cap_seed, game_seed, decision):
+        """the coin alone, on the device: 1 = full, 0 = fast per (game_seed[i], decision[i]) -> [n] uint8"""
+        s = np.ascontiguousarray(game_seed, np.uint32)
+        d = np.ascontiguousarray(decision, np.uint32)
+        assert s.ndim == 1 and s.shape == d.shape
+        o = np.zeros(len(s), np.uint8)
+        self._chk(self.L.azr_debug_playout_cap(self.h, float(full_prob), int(cap_seed), _p(s), _p(d), len(s), _p(o)))
+        return o
 
     # ---- self-play
     def selfplay_start(self, base_seed=20260001):

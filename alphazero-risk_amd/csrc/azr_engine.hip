@@ -180,7 +180,10 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // self-play mode decisions, moves and game restarts — until the next leaf that needs the net.
 // NOISE: root noise is in force (host-stepped: azr_mcts_set_root_noise's vector; self-play: a Dirichlet draw per new root).  The
 // default instantiations carry none of it.
-template <bool SELFPLAY, bool NOISE>
+// CAP (self-play only): a playout cap is in force (azr_selfplay_set_playout_cap).  The decision in progress is full or fast by the coin
+// of (cap seed, game seed, decision) — recomputed here from the Ctl line, never stored; a fast decision searches E.cap_fast descents
+// with the constant root vector and stages no record.  Everything else — trim, pick, move, turnover, z back-fill — is the same code.
+template <bool SELFPLAY, bool NOISE, bool CAP = false>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
     __shared__ int8_t scratch[128];
@@ -193,6 +196,11 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
     Tree t = tree_of(E, g);
     const Rules R = E.rules;
     const Search S = E.search;
+    // the budget of the decision in progress: S's own without a cap, else by the decision's kind (re-derived after every decision and
+    // every new game, below)
+    Search Sd = S;
+    bool full = true;
+    if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
     WS root;
     ws_load(root, E.state + (size_t)g * GREC);
     StepCount k;
@@ -203,7 +211,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
     consume_pending(E, g, t, c, k);
     for (;;) {
         TP(6);
-        if ((int)c.sims_done >= S.simulations) {
+        if ((int)c.sims_done >= (CAP ? Sd.simulations : S.simulations)) {
             if (!SELFPLAY) { c.search_done = 1; break; }
             // ---- one decision of the trainer's move loop (alphazero_trainer.cpp:91-112) ----
             root.rng = c.rng;
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             if (root_node(t, root, N, valid) != NO_NODE) {
                 float pi = root_policy(N, valid);
                 mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
-                stage_sample(E, g, c, root, pi, k);
+                if (!CAP || full) stage_sample(E, g, c, root, pi, k);
             }
             TP(16);
             if (mv != NONE) make_move(root, mv, R); else root.err = E_LOGIC;
@@ -235,14 +243,15 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             }
             root_dirty = true;
             TP(18);
-            if (NOISE) eta = new_root_noise(E, g, c, root);   // the next decision's root, or the next game's first
+            if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
+            if (NOISE) eta = CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);   // the next decision's root, or the next game's first
             if (c.mode == 0) break;  // quota exhausted: the slot idles
             tree_trim(t, c);
             c.sims_done = 0; c.sims_started = 0;
             TP(14);
         }
         uint32_t err = 0;
-        int r = search_round<NOISE>(E, S, g, t, c, root, scratch, k, err, eta);
+        int r = search_round<NOISE>(E, CAP ? Sd : S, g, t, c, root, scratch, k, err, eta);
         if (r == RD_LEAF) break;
         if (r == RD_FAIL) {
             k.err++;
@@ -250,7 +259,8 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             if (SELFPLAY) {  // abandon the game (the reference would have thrown): restart the slot
                 selfplay_next_game(E, g, t, c, root);
                 root_dirty = true;
-                if (NOISE) eta = new_root_noise(E, g, c, root);
+                if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
+                if (NOISE) eta = CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);
                 if (c.mode == 0) break;
                 tree_trim(t, c);
                 continue;
@@ -384,6 +394,35 @@ __global__ __launch_bounds__(64) void k_selfplay_noise(Dev E)
     new_root_noise(E, g, c, root);
 }
 
+// the same with a playout cap in force: a slot whose first decision is fast starts on the constant vector
+__global__ __launch_bounds__(64) void k_selfplay_noise_cap(Dev E)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    WS root;
+    ws_load(root, E.state + (size_t)g * GREC);
+    new_root_noise_cap(E, g, c, root, cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions));
+}
+
+// azr_selfplay_decision_kind: the kind of each slot's decision in progress, one wave per game (1 = full, 0 = fast; 1 for an idle slot)
+__global__ __launch_bounds__(64) void k_decision_kind(Dev E, uint8_t* out)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    const bool full = c.mode == 0 || cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions);
+    if (lane_id() == 0) out[g] = full ? 1 : 0;
+}
+
+// azr_debug_playout_cap: the coin alone, one lane per (game seed, decision)
+__global__ __launch_bounds__(64) void k_debug_playout_cap(uint32_t threshold, uint32_t cap_seed, const uint32_t* game_seed, const uint32_t* decision,
+                                                          int n, uint8_t* out)
+{
+    const int i = (int)(blockIdx.x * 64u + threadIdx.x);
+    if (i < n) out[i] = cap_full(threshold, cap_seed, game_seed[i], decision[i]) ? 1 : 0;
+}
+
 // azr_debug_root_noise: the sampler alone, one wave per vector
 __global__ __launch_bounds__(64) void k_debug_root_noise(float alpha, uint32_t noise_seed, const uint32_t* game_seed, const uint32_t* decision,
                                                          const uint64_t* valid, float* out)
@@ -490,6 +529,10 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     d.search.hp = s->hp_exploration;
     d.search.temperature_threshold = s->temperature_threshold;
     d.noise_eps = s->dir_noise_epsi;
+    d.noise_value = s->dir_noise_value;
+    d.cap_threshold = 1u << 24;   // no cap: every decision is full
+    d.cap_seed = 0;
+    d.cap_fast = d.search.simulations;
     d.search2_simulations = d.search.simulations;   // player B of a two-net arena: this handle's own until azr_arena_set_opponent_search
     d.search2_hp = d.search.hp;
     const size_t G = d.G, GT = G * d.T;
@@ -762,9 +805,11 @@ extern "C" int azr_mcts_begin(azr_engine* h)
 }
 
 // the k_tree_step instantiation of a host-stepped search (azr_mcts_*) or of device self-play, with or without root noise
-static hipError_t launch_tree_step(azr_engine* h, bool selfplay, bool noise)
+// or a playout cap (self-play only)
+static hipError_t launch_tree_step(azr_engine* h, bool selfplay, bool noise, bool cap = false)
 {
-    void (*const step)(Dev) = selfplay ? (noise ? k_tree_step<true, true> : k_tree_step<true, false>)
+    void (*const step)(Dev) = selfplay ? (cap ? (noise ? k_tree_step<true, true, true> : k_tree_step<true, false, true>)
+                                              : (noise ? k_tree_step<true, true> : k_tree_step<true, false>))
                                        : (noise ? k_tree_step<false, true> : k_tree_step<false, false>);
     hipLaunchKernelGGL(step, dim3(h->d.G), dim3(64), 0, h->stream, h->d);
     return hipGetLastError();
@@ -882,7 +927,13 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
     h->sp_noise = h->sp_alpha > 0.0f;
     h->d.noise_alpha = h->sp_alpha;
     h->d.noise_seed = h->sp_noise_seed;
-    if (h->sp_noise) LAUNCH(h, k_selfplay_noise, h->d);
+    // the playout cap as azr_selfplay_set_playout_cap stands now, read the same way
+    h->sp_cap = h->cap_prob < 1.0f && h->cap_fast_sims > 0;
+    h->d.cap_threshold = h->sp_cap ? (uint32_t)(h->cap_prob * 16777216.0f) : (1u << 24);
+    h->d.cap_seed = h->cap_seed;
+    h->d.cap_fast = h->sp_cap ? h->cap_fast_sims - h->cap_fast_sims % h->d.T : h->d.search.simulations;
+    if (h->sp_noise && h->sp_cap) LAUNCH(h, k_selfplay_noise_cap, h->d);
+    else if (h->sp_noise) LAUNCH(h, k_selfplay_noise, h->d);
     else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, (size_t)h->d.G * MOVES * sizeof(float), h->stream));
     SYNC(h);
     return AZR_OK;
@@ -949,6 +1000,59 @@ extern "C" int azr_debug_root_noise(azr_engine* h, float alpha, uint32_t noise_s
     return AZR_OK;
 }
 
+// ---- playout cap ----------------------------------------------------------------------------------------
+extern "C" int azr_selfplay_set_playout_cap(azr_engine* h, float full_prob, int fast_simulations, uint32_t cap_seed)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (full_prob != full_prob || full_prob < 0.0f) {
+        h->err = "azr_selfplay_set_playout_cap: full_prob must be a number >= 0 (>= 1 = off)";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    const bool on = full_prob < 1.0f && fast_simulations > 0;
+    if (on && (fast_simulations < h->cfg.mcts_threads || fast_simulations > h->cfg.mcts_simulations)) {
+        h->err = "azr_selfplay_set_playout_cap: fast_simulations = " + std::to_string(fast_simulations) + " outside [mcts_threads = " +
+                 std::to_string(h->cfg.mcts_threads) + ", mcts_simulations = " + std::to_string(h->cfg.mcts_simulations) +
+                 "] (F - F % T descents would be none, or more than a full decision's)";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    h->cap_prob = on ? full_prob : 1.0f;
+    h->cap_fast_sims = on ? fast_simulations : 0;
+    h->cap_seed = cap_seed;
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_decision_kind(azr_engine* h, uint8_t* full_host)
+{
+    ENTER(h);
+    if (!full_host) return AZR_E_INVALID_ARGUMENT;
+    if (h->mode != 2 || !h->sp_cap) { memset(full_host, 1, (size_t)h->d.G); return AZR_OK; }
+    LAUNCH_OUT(h, full_host, (size_t)h->d.G, uint8_t, k_decision_kind, h->d);
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_playout_cap(azr_engine* h, float full_prob, uint32_t cap_seed, const uint32_t* game_seed, const uint32_t* decision,
+                                     int n, uint8_t* full_out)
+{
+    ENTER(h);
+    if (full_prob != full_prob || full_prob < 0.0f) {
+        h->err = "azr_debug_playout_cap: full_prob must be a number >= 0";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    if (n < 0 || (n > 0 && (!game_seed || !decision || !full_out))) return AZR_E_INVALID_ARGUMENT;
+    if (n == 0) return AZR_OK;
+    const uint32_t threshold = full_prob >= 1.0f ? (1u << 24) : (uint32_t)(full_prob * 16777216.0f);
+    DevBuf bs, bd, bo;
+    HIPCHK(h, bs.alloc((size_t)n * 4)); HIPCHK(h, bd.alloc((size_t)n * 4)); HIPCHK(h, bo.alloc((size_t)n));
+    H2D(h, bs.p, game_seed, (size_t)n * 4);
+    H2D(h, bd.p, decision, (size_t)n * 4);
+    hipLaunchKernelGGL(k_debug_playout_cap, dim3((n + 63) / 64), dim3(64), 0, h->stream, threshold, cap_seed, (const uint32_t*)bs.p,
+                       (const uint32_t*)bd.p, n, (uint8_t*)bo.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, full_out, bo.p, (size_t)n);
+    SYNC(h);
+    return AZR_OK;
+}
+
 extern "C" int azr_selfplay_start_from_states(azr_engine* h, uint32_t base_seed)
 {
     ENTER(h);
@@ -999,7 +1103,7 @@ extern "C" int azr_selfplay_run(azr_engine* h, int passes)
         if (h->sp_tail) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, sizeof(int), h->stream));
         const ProfEvents* ev = prof ? &h->ev[k] : nullptr;   // this pass's events, if it is a sampled one
         if (ev) HIPCHK(h, hipEventRecord(ev->tree0, h->stream));
-        HIPCHK(h, launch_tree_step(h, true, h->sp_noise));
+        HIPCHK(h, launch_tree_step(h, true, h->sp_noise, h->sp_cap));
         if (ev) HIPCHK(h, hipEventRecord(ev->tree1, h->stream));
         if (h->sp_tail) {
             D2H(h, &n_eval, h->d.leaf_count, sizeof(int));

@@ -104,6 +104,12 @@ struct Dev {
     float noise_eps;           // DIR_NOISE_EPSI: noiseP = c1 * P + noise_eps * eta at path depth 0
     float noise_alpha;         // device self-play: Dirichlet(alpha) per new root ...
     uint32_t noise_seed;       // ... keyed by (noise_seed, game seed, decision, move)
+    // playout cap (this engine's own; read by k_tree_step<true, .., true> and the kernels of azr_selfplay_decision_kind /
+    // azr_debug_playout_cap only): decision d of the game with seed s is full iff cap_full(cap_threshold, cap_seed, s, d) (azr_cap.hpp)
+    uint32_t cap_threshold;    // (uint32_t)(full_prob * 2^24)
+    uint32_t cap_seed;
+    int cap_fast;              // descents of a fast decision: fast_simulations - fast_simulations % T
+    float noise_value;         // DIR_NOISE_VALUE: every entry of a fast root's vector (the constant form, bit for bit)
 };
 constexpr int ALOG = 16;
 
@@ -168,6 +174,10 @@ struct azr_engine {
     float sp_alpha = 0.0f;        // azr_selfplay_set_dirichlet, as set ...
     uint32_t sp_noise_seed = 0;
     bool sp_noise = false;        // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, true>
+    float cap_prob = 1.0f;        // azr_selfplay_set_playout_cap, as set (off: cap_prob >= 1 or cap_fast_sims <= 0) ...
+    int cap_fast_sims = 0;
+    uint32_t cap_seed = 0;
+    bool sp_cap = false;          // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, .., true>
     bool sp_tail = false;         // quota self-play: no game is left to start, slots go idle -> compacted net batches
     void* train = nullptr;        // azr_train.hip: optimiser state + activation slabs, created by the first azr_nn_train*
     void* dp_comm = nullptr;      // azr_dp_init: this handle's RCCL communicator (ncclComm_t), rank and world

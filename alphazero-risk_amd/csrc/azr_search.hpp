@@ -2,6 +2,7 @@
 // net's answers, descents, one search round, record staging and the self-play game turnover.  Included by azr_engine.hip only.
 #pragma once
 #include "azr_internal.hpp"
+#include "azr_cap.hpp"
 #include "azr_noise.hpp"
 
 namespace azr {
@@ -352,6 +353,16 @@ __device__ __forceinline__ float new_root_noise(const Dev& E, int g, const Ctl& 
 {
     float eta = 0.0f;
     if (c.mode != 0) eta = dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules));
+    if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
+    return eta;
+}
+
+// the same under a playout cap: a full root draws as above, a fast root gets the constant vector (DIR_NOISE_VALUE in all 43 entries:
+// the first selection then computes eps * DIR_NOISE_VALUE, the constant form's c2, bit for bit)
+__device__ __forceinline__ float new_root_noise_cap(const Dev& E, int g, const Ctl& c, const WS& root, bool full)
+{
+    float eta = 0.0f;
+    if (c.mode != 0) eta = full ? dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules)) : E.noise_value;
     if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
     return eta;
 }

@@ -100,6 +100,9 @@ void Settings::init(int argc, char* argv[])
         {"pair-halves", "[this build] mirrored pairs: 1 = both games of a pair at the same time on two slots, 0 = one after the other on one slot", std::to_string(CONCURRENT_PAIR_HALVES), true},
         {"dir-alpha", "[this build] self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision (0 = the reference's constant --dnv; at most 10)", "0", false},
         {"dir-seed", "[this build] seed of the self-play root noise (independent of --seed: the games' dice and deals do not move)", std::to_string(DIR_SEED), false},
+        {"cap-prob", "[this build] self-play playout cap: share of decisions that get the whole --mcts search, root noise and a training record; the others search --cap-fast simulations and write none (1 = off: every decision)", "1", false},
+        {"cap-fast", "[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])", "0", false},
+        {"cap-seed", "[this build] seed of the playout cap's coin (independent of --seed and --dir-seed: dice, deals and noise do not move)", std::to_string(CAP_SEED), false},
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -226,6 +229,29 @@ void Settings::init(int argc, char* argv[])
         DIR_ALPHA = (float)al;
     }
     DIR_SEED = (uint32_t)strtoul(get("dir-seed").c_str(), nullptr, 10);
+    {
+        char* end = nullptr;
+        const std::string pv = get("cap-prob");
+        const double pr = strtod(pv.c_str(), &end);
+        if (pv.empty() || *end != '\0' || !(pr >= 0.0) || pr > 1.0) {
+            fprintf(stderr, "--cap-prob: '%s' is not a probability (a number in [0, 1]; 1 = off)\n", pv.c_str());
+            exit(2);
+        }
+        CAP_PROB = (float)pr;
+        const std::string fv = get("cap-fast");
+        const long fs = strtol(fv.c_str(), &end, 10);
+        if (fv.empty() || *end != '\0' || fs < 0) {
+            fprintf(stderr, "--cap-fast: '%s' is not a simulation count (0 = off)\n", fv.c_str());
+            exit(2);
+        }
+        const int threads = std::max(1, std::min(8, THREADS_PER_MCTS));
+        if (CAP_PROB < 1.0f && fs > 0 && (fs < threads || fs > MCTS_SIMULATIONS)) {   // the cap is on: F - F % T descents, at most a full decision's
+            fprintf(stderr, "--cap-fast: %ld simulations are outside [%d search threads (-t), %d simulations (--mcts)]\n", fs, threads, MCTS_SIMULATIONS);
+            exit(2);
+        }
+        CAP_FAST = (int)fs;
+    }
+    CAP_SEED = (uint32_t)strtoul(get("cap-seed").c_str(), nullptr, 10);
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
     DEVICE_MAP.clear();
@@ -695,6 +721,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         // TRAIN_ITERATION_GAMES, alphazero_trainer.cpp:83)
         // root noise of the generated games: --dir-alpha 0 (default) keeps the reference's constant
         e.check(azr_selfplay_set_dirichlet(e.h, SETTINGS.DIR_ALPHA, SETTINGS.DIR_SEED), "selfplay_set_dirichlet");
+        // playout cap of the generated games: --cap-prob 1 / --cap-fast 0 (default) search and record every decision
+        e.check(azr_selfplay_set_playout_cap(e.h, SETTINGS.CAP_PROB, SETTINGS.CAP_FAST, SETTINGS.CAP_SEED), "selfplay_set_playout_cap");
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);

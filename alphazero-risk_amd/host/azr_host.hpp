@@ -25,7 +25,7 @@ namespace azrhost {
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
 // `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2,
-// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play), the others marked "[this build]" in --help.
+// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap), the others marked "[this build]" in --help.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:
@@ -76,6 +76,9 @@ public:
     bool CONCURRENT_PAIR_HALVES = true;  // --pair-halves: the two games of a mirrored pair on two slots at the same time (AZR_MIRROR_CONCURRENT)
     float DIR_ALPHA = 0.0f;              // --dir-alpha: self-play root noise ~ Dirichlet(alpha) per decision (0 = the reference's constant DIR_NOISE_VALUE)
     uint32_t DIR_SEED = 0;               // --dir-seed: seed of that noise (self-play generation of -m train only: compare, benchmark and -m play games have none)
+    float CAP_PROB = 1.0f;               // --cap-prob: self-play playout cap, the share of full decisions (1 = off) ...
+    int CAP_FAST = 0;                    // --cap-fast: ... the simulations of the others, which write no record (0 = off) ...
+    uint32_t CAP_SEED = 0;               // --cap-seed: ... and the seed of the coin (self-play generation of -m train only, like --dir-alpha)
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 

@@ -204,6 +204,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
             # exactly `share` games, each played to its end (Counter::hasNext, alphazero_trainer.cpp:83); this rank's seed
             # stream continues where its previous iteration stopped, so no (iteration, rank) pair ever replays a game
             gen.selfplay_set_dirichlet(getattr(a, "dir_alpha", 0.0), getattr(a, "dir_seed", 0))   # root noise of the generated games only (0 = the reference's constant)
+            gen.selfplay_set_playout_cap(getattr(a, "cap_prob", 1.0), getattr(a, "cap_fast", 0), getattr(a, "cap_seed", 0))   # playout cap of the generated games only (1 / 0 = off)
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -337,6 +338,11 @@ def main():
                     help="self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision on the device "
                          "(0 = the reference's constant DIR_NOISE_VALUE; at most 10); compare and benchmark games have none")
     ap.add_argument("--dir-seed", type=int, default=0, help="seed of the self-play root noise (the games' dice and deals do not move)")
+    ap.add_argument("--cap-prob", type=float, default=1.0,
+                    help="[this build] self-play playout cap: share of decisions that get the whole --mcts search, root noise and a training "
+                         "record; the others search --cap-fast simulations and write none (1 = off)")
+    ap.add_argument("--cap-fast", type=int, default=0, help="[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])")
+    ap.add_argument("--cap-seed", type=int, default=0, help="[this build] seed of the playout cap's coin (dice, deals and root noise do not move)")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -350,6 +356,10 @@ def main():
                     help="1 = the data-parallel step's sums go through torch.distributed (one host hand-over each) instead of the engine's own "
                          "in-stream RCCL communicator")
     a = ap.parse_args()
+    if not 0.0 <= a.cap_prob <= 1.0:   # (a NaN fails both comparisons)
+        ap.error(f"--cap-prob: {a.cap_prob} is not a probability (a number in [0, 1]; 1 = off)")
+    if a.cap_fast < 0 or (a.cap_prob < 1.0 and a.cap_fast > 0 and not a.t <= a.cap_fast <= a.mcts):
+        ap.error(f"--cap-fast: {a.cap_fast} simulations are outside [{a.t} search threads (-t), {a.mcts} simulations (--mcts)]")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():
         learn(a)

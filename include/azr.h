@@ -215,6 +215,42 @@ int azr_mcts_root_noise(azr_engine* h, float* eta_host);
 int azr_debug_root_noise(azr_engine* h, float alpha, uint32_t noise_seed, const uint32_t* game_seed,
                          const uint32_t* decision, const uint64_t* valid, int n, float* eta_out);
 
+/* ---- playout cap randomisation in device self-play (this engine's own; off after azr_engine_create) -----------------
+ * The reference spends MCTS_SIMULATIONS on every decision of a self-play game and records every decision.  With a cap in force
+ * each decision is FULL or FAST by a coin:
+ *
+ * The coin.  d = the number of decisions already taken in the running game (0 at a game's first decision, and 0 again where
+ * azr_selfplay_start_from_states enters a game); s = the game's seed.  All arithmetic is uint32:
+ *     mix(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *     k = mix(cap_seed + 0xC2B2AE35);   k = mix(k ^ s);   k = mix((k ^ d) + 0x27D4EB2F)
+ *     full  <=>  (k >> 8) < (uint32_t)(full_prob * 16777216.0f)          (the threshold is computed once on the host, in float)
+ * otherwise the decision is fast.  The coin is a function of (cap_seed, s, d, full_prob) alone: not of the slot, the number of games
+ * or threads, the pass schedule, the noise seed or the game's own RNG stream, from which nothing is drawn.  Its domain constants are
+ * not the Dirichlet sampler's, so equal seeds do not correlate coin and noise.
+ *
+ * A full decision is the decision without a cap, exactly: S = mcts_simulations - mcts_simulations % mcts_threads descents, the
+ * Dirichlet vector at path depth 0 if azr_selfplay_set_dirichlet is in force, one (s, pi, z) record staged.
+ * A fast decision runs F = fast_simulations - fast_simulations % mcts_threads descents; with azr_selfplay_set_dirichlet in force its
+ * root vector is the constant eta[m] = DIR_NOISE_VALUE for all 43 entries — the constant form bit for bit (see above) — which is what
+ * the engine stores for that root and what azr_mcts_root_noise reports as the vector in force; and it stages NO record.
+ * Everything else is the same for both kinds: trim and tree reuse between decisions, the temperature pick against
+ * temperature_threshold including its one rFloat, the move, game turnover, quota tickets, and the z back-fill of the staged records
+ * when the game ends (every record's z comes from a game played with real searches throughout).
+ * Counters: decisions and simulations count both kinds; samples counts written records only.
+ * The arena (azr_arena_*) and the host-stepped searches (azr_mcts_*) never see the cap.
+ *
+ * Read by azr_selfplay_start*; a running self-play never sees a change.  Off (the state after create) for full_prob >= 1 or
+ * fast_simulations <= 0.  full_prob == 0 is legal: no decision is full and no record is written.  AZR_E_INVALID_ARGUMENT, with a
+ * reason in azr_last_error, for a NaN or negative full_prob, or — when the cap is on — a fast_simulations outside
+ * [mcts_threads, mcts_simulations].  The node pool is sized for the full budget. */
+int azr_selfplay_set_playout_cap(azr_engine* h, float full_prob, int fast_simulations, uint32_t cap_seed);
+/* the kind of each slot's current decision, full_host [G]: 1 = full, 0 = fast.  All 1 when no cap is in force or the engine is not
+ * in self-play; 1 for a slot that has gone idle. */
+int azr_selfplay_decision_kind(azr_engine* h, uint8_t* full_host);
+/* the coin alone, on the device: full_out[i] = 1 / 0 for (game_seed[i], decision[i]), i < n; full_prob >= 0 (>= 1: all full) */
+int azr_debug_playout_cap(azr_engine* h, float full_prob, uint32_t cap_seed, const uint32_t* game_seed,
+                          const uint32_t* decision, int n, uint8_t* full_out);
+
 /* ---- device-resident self-play (trainer move loop, alphazero_trainer.cpp:80-119) --------------------------- */
 /* (Re)start all G games: game g plays seeds base_seed + g, then base_seed + G + g, ... */
 int azr_selfplay_start(azr_engine* h, uint32_t base_seed);
