@@ -85,6 +85,8 @@ EXPORTS = [
     "azr_arena_set_opponent_net", "azr_arena_set_opponent_search", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
     "azr_mcts_set_root_noise", "azr_selfplay_set_dirichlet", "azr_mcts_root_noise", "azr_debug_root_noise",
     "azr_selfplay_set_playout_cap", "azr_selfplay_decision_kind", "azr_debug_playout_cap",
+    "azr_mcts_set_forced_playouts", "azr_mcts_pruned_policy", "azr_selfplay_set_forced_playouts", "azr_mcts_set_simulations",
+    "azr_selfplay_start_games_from_states",
 ]
 
 
@@ -158,6 +160,11 @@ def load_library(test_hooks=False):
         L.azr_selfplay_set_playout_cap.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_uint32]
         L.azr_selfplay_decision_kind.argtypes = [C.c_void_p, C.c_void_p]
         L.azr_debug_playout_cap.argtypes = [C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.azr_mcts_set_forced_playouts.argtypes = [C.c_void_p, C.c_float]
+        L.azr_mcts_pruned_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_selfplay_set_forced_playouts.argtypes = [C.c_void_p, C.c_float, C.c_int]
+        L.azr_mcts_set_simulations.argtypes = [C.c_void_p, C.c_int]
+        L.azr_selfplay_start_games_from_states.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
         _libs[test_hooks] = L
         if not test_hooks:
             _lib = L
@@ -468,6 +475,29 @@ class Engine:
         self._chk(self.L.azr_debug_playout_cap(self.h, float(full_prob), int(cap_seed), _p(s), _p(d), len(s), _p(o)))
         return o
 
+    # ---- forced playouts and policy target pruning (this engine's own; off = the search and the records above)
+    def set_forced_playouts(self, k):
+        """host-stepped searches: at path depth 0 a tried root move is selected until it has sqrt(k * noiseP * sumN) visits;
+        k <= 0 = off; holds until set again or selfplay_start*"""
+        self._chk(self.L.azr_mcts_set_forced_playouts(self.h, float(k)))
+
+    def pruned_policy(self):
+        """(pi [G, 43], N' [G, 43]) of the last search's roots under policy target pruning with the factor and vector in force;
+        policy() stays the unpruned one"""
+        pi = np.zeros((self.G, MOVES), np.float32)
+        n = np.zeros((self.G, MOVES), np.uint32)
+        self._chk(self.L.azr_mcts_pruned_policy(self.h, _p(pi), _p(n)))
+        return pi, n
+
+    def selfplay_set_forced_playouts(self, k, prune=False):
+        """device self-play: forced playouts in every full decision, and with prune the pruned policy in the records; k <= 0 = off;
+        read by selfplay_start*"""
+        self._chk(self.L.azr_selfplay_set_forced_playouts(self.h, float(k), int(bool(prune))))
+
+    def set_simulations(self, simulations):
+        """host-stepped searches: the budget per search, within [threads, sims]; <= 0 = the settings' own"""
+        self._chk(self.L.azr_mcts_set_simulations(self.h, int(simulations)))
+
     # ---- self-play
     def selfplay_start(self, base_seed=20260001):
         self._chk(self.L.azr_selfplay_start(self.h, base_seed))
@@ -479,6 +509,10 @@ class Engine:
     def selfplay_start_from_states(self, base_seed=20260001):
         """self-play goes on from the states / RNG streams set with set_states / set_rng"""
         self._chk(self.L.azr_selfplay_start_from_states(self.h, base_seed))
+
+    def selfplay_start_games_from_states(self, base_seed, games):
+        """the games of slots 0 .. min(games, G) - 1 go on from the states / RNG streams set; no other game starts while games <= G"""
+        self._chk(self.L.azr_selfplay_start_games_from_states(self.h, base_seed, games))
 
     def selfplay_run(self, passes):
         self._chk(self.L.azr_selfplay_run(self.h, passes))

@@ -183,7 +183,10 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // CAP (self-play only): a playout cap is in force (azr_selfplay_set_playout_cap).  The decision in progress is full or fast by the coin
 // of (cap seed, game seed, decision) — recomputed here from the Ctl line, never stored; a fast decision searches E.cap_fast descents
 // with the constant root vector and stages no record.  Everything else — trim, pick, move, turnover, z back-fill — is the same code.
-template <bool SELFPLAY, bool NOISE, bool CAP = false>
+// FORCED (with NOISE only; a search without a sampled vector runs on the constant one, which is the constant form bit for bit): forced
+// playouts at path depth 0 with the factor E.forced_k (azr_forced.hpp) — not in a fast decision; with E.prune the staged record's pi
+// comes from the pruned counts N', the move still from N.
+template <bool SELFPLAY, bool NOISE, bool CAP = false, bool FORCED = false>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
     __shared__ int8_t scratch[128];
@@ -207,6 +210,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
     bool root_dirty = false;
     float eta = 0.0f;
     if (NOISE) eta = E.root_eta[(size_t)g * MOVES + (lane_id() < MOVES ? lane_id() : 0)];
+    if (FORCED && !SELFPLAY && E.eta_const) eta = E.noise_value;   // host-stepped, no vector set: the constant form
     TP(0);
     consume_pending(E, g, t, c, k);
     for (;;) {
@@ -220,6 +224,10 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             if (root_node(t, root, N, valid) != NO_NODE) {
                 float pi = root_policy(N, valid);
                 mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
+                if (FORCED && E.prune && (!CAP || full)) {   // the record's pi from N'; the move above is N's
+                    const uint32_t rkd = ws_record_dword(root);
+                    pi = root_policy(root_pruned_counts(E, S, t, tree_lookup(t, rkd, key_hash(rkd)), N, valid, eta, E.forced_k), valid);
+                }
                 if (!CAP || full) stage_sample(E, g, c, root, pi, k);
             }
             TP(16);
@@ -244,14 +252,14 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             root_dirty = true;
             TP(18);
             if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
-            if (NOISE) eta = CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);   // the next decision's root, or the next game's first
+            if (NOISE) eta = FORCED ? new_root_noise_forced(E, g, c, root, full) : CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);   // the next decision's root, or the next game's first
             if (c.mode == 0) break;  // quota exhausted: the slot idles
             tree_trim(t, c);
             c.sims_done = 0; c.sims_started = 0;
             TP(14);
         }
         uint32_t err = 0;
-        int r = search_round<NOISE>(E, CAP ? Sd : S, g, t, c, root, scratch, k, err, eta);
+        int r = search_round<NOISE, FORCED>(E, CAP ? Sd : S, g, t, c, root, scratch, k, err, eta, (FORCED && (!CAP || full)) ? E.forced_k : 0.0f);
         if (r == RD_LEAF) break;
         if (r == RD_FAIL) {
             k.err++;
@@ -260,7 +268,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                 selfplay_next_game(E, g, t, c, root);
                 root_dirty = true;
                 if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
-                if (NOISE) eta = CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);
+                if (NOISE) eta = FORCED ? new_root_noise_forced(E, g, c, root, full) : CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);
                 if (c.mode == 0) break;
                 tree_trim(t, c);
                 continue;
@@ -405,6 +413,41 @@ __global__ __launch_bounds__(64) void k_selfplay_noise_cap(Dev E)
     new_root_noise_cap(E, g, c, root, cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions));
 }
 
+// the same with forced playouts in force: a root without a draw (no Dirichlet set, or a fast first decision) starts on the constant vector
+__global__ __launch_bounds__(64) void k_selfplay_noise_forced(Dev E)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    WS root;
+    ws_load(root, E.state + (size_t)g * GREC);
+    new_root_noise_forced(E, g, c, root, cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions));
+}
+
+// azr_mcts_pruned_policy: N' and the policy over N' of every game's root, under E.forced_k (<= 0: N' = N) and the root vector in force
+// (E.eta_const: none, the constant form)
+__global__ __launch_bounds__(64) void k_pruned_policy(Dev E, uint32_t* n_out, float* pi_out)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    Tree t = tree_of(E, g);
+    WS root;
+    ws_load(root, E.state + (size_t)g * GREC);
+    const uint32_t l = lane_id();
+    const float eta = E.eta_const ? E.noise_value : E.root_eta[(size_t)g * MOVES + (l < MOVES ? l : 0)];
+    uint32_t N; uint64_t valid; float pi = 0;
+    const uint32_t ridx = root_node(t, root, N, valid);
+    if (ridx != NO_NODE) {
+        if (E.forced_k > 0.0f) N = root_pruned_counts(E, E.search, t, ridx, N, valid, eta, E.forced_k);
+        pi = root_policy(N, valid);
+    }
+    if (l < MOVES) {
+        if (n_out) n_out[(size_t)g * MOVES + l] = N;
+        pi_out[(size_t)g * MOVES + l] = pi;
+    }
+}
+
 // azr_selfplay_decision_kind: the kind of each slot's decision in progress, one wave per game (1 = full, 0 = fast; 1 for an idle slot)
 __global__ __launch_bounds__(64) void k_decision_kind(Dev E, uint8_t* out)
 {
@@ -533,6 +576,9 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     d.cap_threshold = 1u << 24;   // no cap: every decision is full
     d.cap_seed = 0;
     d.cap_fast = d.search.simulations;
+    d.forced_k = 0.0f;            // no forced playouts, no pruning
+    d.prune = 0;
+    d.eta_const = 0;
     d.search2_simulations = d.search.simulations;   // player B of a two-net arena: this handle's own until azr_arena_set_opponent_search
     d.search2_hp = d.search.hp;
     const size_t G = d.G, GT = G * d.T;
@@ -805,20 +851,33 @@ extern "C" int azr_mcts_begin(azr_engine* h)
 }
 
 // the k_tree_step instantiation of a host-stepped search (azr_mcts_*) or of device self-play, with or without root noise
-// or a playout cap (self-play only)
-static hipError_t launch_tree_step(azr_engine* h, bool selfplay, bool noise, bool cap = false)
+// or a playout cap (self-play only); with forced playouts the three FORCED instantiations, which carry NOISE
+static hipError_t launch_tree_step(azr_engine* h, const Dev& d, bool selfplay, bool noise, bool cap = false, bool forced = false)
 {
-    void (*const step)(Dev) = selfplay ? (cap ? (noise ? k_tree_step<true, true, true> : k_tree_step<true, false, true>)
-                                              : (noise ? k_tree_step<true, true> : k_tree_step<true, false>))
-                                       : (noise ? k_tree_step<false, true> : k_tree_step<false, false>);
-    hipLaunchKernelGGL(step, dim3(h->d.G), dim3(64), 0, h->stream, h->d);
+    void (*step)(Dev) = selfplay ? (cap ? (noise ? k_tree_step<true, true, true> : k_tree_step<true, false, true>)
+                                        : (noise ? k_tree_step<true, true> : k_tree_step<true, false>))
+                                 : (noise ? k_tree_step<false, true> : k_tree_step<false, false>);
+    if (forced) step = selfplay ? (cap ? k_tree_step<true, true, true, true> : k_tree_step<true, true, false, true>) : k_tree_step<false, true, false, true>;
+    hipLaunchKernelGGL(step, dim3(d.G), dim3(64), 0, h->stream, d);
     return hipGetLastError();
+}
+
+// the device view of a host-stepped search: the handle's, with azr_mcts_set_forced_playouts / azr_mcts_set_simulations applied
+static Dev host_search_view(const azr_engine* h)
+{
+    Dev d = h->d;
+    d.forced_k = h->forced_host;
+    d.prune = 0;
+    d.eta_const = h->noise_host ? 0 : 1;
+    if (h->host_sims > 0) d.search.simulations = h->host_sims - h->host_sims % d.T;
+    return d;
 }
 
 static int tree_step_host(azr_engine* h, uint32_t* active)
 {
     HIPCHK(h, hipMemsetAsync(h->d.active, 0, 4, h->stream));
-    HIPCHK(h, launch_tree_step(h, false, h->noise_host));
+    if (h->forced_host > 0.0f || h->host_sims > 0) HIPCHK(h, launch_tree_step(h, host_search_view(h), false, h->noise_host || h->forced_host > 0.0f, false, h->forced_host > 0.0f));
+    else HIPCHK(h, launch_tree_step(h, h->d, false, h->noise_host));
     D2H(h, active, h->d.active, 4);
     SYNC(h);
     return AZR_OK;
@@ -932,7 +991,15 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
     h->d.cap_threshold = h->sp_cap ? (uint32_t)(h->cap_prob * 16777216.0f) : (1u << 24);
     h->d.cap_seed = h->cap_seed;
     h->d.cap_fast = h->sp_cap ? h->cap_fast_sims - h->cap_fast_sims % h->d.T : h->d.search.simulations;
-    if (h->sp_noise && h->sp_cap) LAUNCH(h, k_selfplay_noise_cap, h->d);
+    // forced playouts and pruning as azr_selfplay_set_forced_playouts stands now; the host-stepped factor and budget end here
+    h->forced_host = 0.0f;
+    h->host_sims = 0;
+    h->sp_forced = h->sp_forced_k > 0.0f;
+    h->d.forced_k = h->sp_forced ? h->sp_forced_k : 0.0f;
+    h->d.prune = h->sp_forced && h->sp_prune ? 1 : 0;
+    h->d.eta_const = 0;
+    if (h->sp_forced) LAUNCH(h, k_selfplay_noise_forced, h->d);
+    else if (h->sp_noise && h->sp_cap) LAUNCH(h, k_selfplay_noise_cap, h->d);
     else if (h->sp_noise) LAUNCH(h, k_selfplay_noise, h->d);
     else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, (size_t)h->d.G * MOVES * sizeof(float), h->stream));
     SYNC(h);
@@ -998,6 +1065,75 @@ extern "C" int azr_debug_root_noise(azr_engine* h, float alpha, uint32_t noise_s
     D2H(h, eta_out, bo.p, (size_t)n * MOVES * sizeof(float));
     SYNC(h);
     return AZR_OK;
+}
+
+// ---- forced playouts and policy target pruning ----------------------------------------------------------
+static int forced_k_check(azr_engine* h, const char* who, float k)
+{
+    if (k != k || k > FORCED_K_MAX) {
+        h->err = std::string(who) + ": k must be a number <= 8 (<= 0 = off)";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_set_forced_playouts(azr_engine* h, float k)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    int rc = forced_k_check(h, "azr_mcts_set_forced_playouts", k);
+    if (rc) return rc;
+    h->forced_host = k > 0.0f ? k : 0.0f;
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_set_simulations(azr_engine* h, int simulations)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (simulations > 0 && (simulations < h->cfg.mcts_threads || simulations > h->cfg.mcts_simulations)) {
+        h->err = "azr_mcts_set_simulations: simulations = " + std::to_string(simulations) + " outside [mcts_threads = " +
+                 std::to_string(h->cfg.mcts_threads) + ", mcts_simulations = " + std::to_string(h->cfg.mcts_simulations) + "]";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    h->host_sims = simulations > 0 ? simulations : 0;
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_set_forced_playouts(azr_engine* h, float k, int prune)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    int rc = forced_k_check(h, "azr_selfplay_set_forced_playouts", k);
+    if (rc) return rc;
+    if (prune && !(k > 0.0f)) {
+        h->err = "azr_selfplay_set_forced_playouts: prune != 0 needs k > 0 (pruning subtracts forced playouts; there are none)";
+        return AZR_E_INVALID_ARGUMENT;
+    }
+    h->sp_forced_k = k > 0.0f ? k : 0.0f;
+    h->sp_prune = prune != 0;
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_pruned_policy(azr_engine* h, float* pi, uint32_t* n_pruned)
+{
+    ENTER(h);
+    if (!pi) return AZR_E_INVALID_ARGUMENT;
+    Dev d = h->mode == 2 ? h->d : host_search_view(h);
+    if (h->mode == 2) d.eta_const = (h->sp_noise || h->sp_forced) ? 0 : 1;
+    if (h->mode == 3) d.forced_k = 0.0f;   // the arena never forces
+    const size_t sz = (size_t)h->d.G * MOVES * 4;
+    DevBuf bn, bp;
+    HIPCHK(h, bn.alloc(sz)); HIPCHK(h, bp.alloc(sz));
+    LAUNCH(h, k_pruned_policy, d, (uint32_t*)bn.p, (float*)bp.p);
+    if (n_pruned) D2H(h, n_pruned, bn.p, sz);
+    D2H(h, pi, bp.p, sz);
+    SYNC(h);
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_start_games_from_states(azr_engine* h, uint32_t base_seed, uint64_t games)
+{
+    ENTER(h);
+    if (games == 0) return AZR_E_INVALID_ARGUMENT;
+    return selfplay_start(h, base_seed, games, 1);
 }
 
 // ---- playout cap ----------------------------------------------------------------------------------------
@@ -1103,7 +1239,7 @@ extern "C" int azr_selfplay_run(azr_engine* h, int passes)
         if (h->sp_tail) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, sizeof(int), h->stream));
         const ProfEvents* ev = prof ? &h->ev[k] : nullptr;   // this pass's events, if it is a sampled one
         if (ev) HIPCHK(h, hipEventRecord(ev->tree0, h->stream));
-        HIPCHK(h, launch_tree_step(h, true, h->sp_noise, h->sp_cap));
+        HIPCHK(h, launch_tree_step(h, h->d, true, h->sp_noise, h->sp_cap, h->sp_forced));
         if (ev) HIPCHK(h, hipEventRecord(ev->tree1, h->stream));
         if (h->sp_tail) {
             D2H(h, &n_eval, h->d.leaf_count, sizeof(int));

@@ -110,6 +110,11 @@ struct Dev {
     uint32_t cap_seed;
     int cap_fast;              // descents of a fast decision: fast_simulations - fast_simulations % T
     float noise_value;         // DIR_NOISE_VALUE: every entry of a fast root's vector (the constant form, bit for bit)
+    // forced playouts and policy target pruning (this engine's own; read by k_tree_step<.., FORCED = true>, k_selfplay_noise_forced and
+    // k_pruned_policy only; azr_forced.hpp)
+    float forced_k;            // the factor k of nf = sqrt(k * noiseP * sumN) (0 = off)
+    int prune;                 // device self-play: a record's pi comes from the pruned counts
+    int eta_const;             // host-stepped: no root vector is set, the search runs on the constant one (noise_value)
 };
 constexpr int ALOG = 16;
 
@@ -178,6 +183,11 @@ struct azr_engine {
     int cap_fast_sims = 0;
     uint32_t cap_seed = 0;
     bool sp_cap = false;          // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, .., true>
+    float forced_host = 0.0f;     // azr_mcts_set_forced_playouts: host-stepped searches run k_tree_step<false, true, false, true> (0 = off)
+    int host_sims = 0;            // azr_mcts_set_simulations: the budget of host-stepped searches (0 = the settings')
+    float sp_forced_k = 0.0f;     // azr_selfplay_set_forced_playouts, as set ...
+    bool sp_prune = false;
+    bool sp_forced = false;       // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, true, CAP, true>
     bool sp_tail = false;         // quota self-play: no game is left to start, slots go idle -> compacted net batches
     void* train = nullptr;        // azr_train.hip: optimiser state + activation slabs, created by the first azr_nn_train*
     void* dp_comm = nullptr;      // azr_dp_init: this handle's RCCL communicator (ncclComm_t), rank and world

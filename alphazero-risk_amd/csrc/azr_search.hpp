@@ -217,9 +217,10 @@ enum : int { RD_DONE = 0, RD_LEAF = 1, RD_FAIL = 2 };
 // needs the net (RD_LEAF: leaf record written to slot g * T + th, pending bit set) or a rule error (RD_FAIL).
 // `S`: the settings of the tree that is searching (the arena's player B may carry its own budget and PUCT constant).
 // NOISE: the game's root noise vector `eta` (lane i <-> move i) enters the first selection of every descent (tree_select).
-template <bool NOISE>
+// FORCED: that selection forces playouts with the factor `fk` (0 = not in this search: a fast decision under a playout cap).
+template <bool NOISE, bool FORCED = false>
 __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out, float eta)
+                                            StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
 {
     const Rules R = E.rules;
     const Tree t = thread_tree(t0, th);
@@ -262,7 +263,7 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
                 break;
             }
             k.levels++;
-            uint32_t mv = tree_select<NOISE>(t, idx, nr, S, c.search_id, scratch, plen == 0, E.noise_eps, eta);
+            uint32_t mv = tree_select<NOISE, FORCED>(t, idx, nr, S, c.search_id, scratch, plen == 0, E.noise_eps, eta, fk);
             TP(12);
             if (mv == NONE) { fail = true; s.err = E_LOGIC; break; }
             uint32_t before = s.cur;
@@ -293,13 +294,13 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
 // One round of AlphaZeroMCTS::simulate for all T search threads of the game, in thread order: every thread without a
 // pending leaf runs descents until it blocks on the net.  RD_LEAF = at least one leaf is waiting; RD_DONE = the counter
 // is exhausted and every claimed simulation is backed up.
-template <bool NOISE>
+template <bool NOISE, bool FORCED = false>
 __device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out, float eta)
+                                            StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
 {
     for (int th = 0; th < E.T; th++) {
         if ((c.pending >> th) & 1u) continue;
-        int r = run_descents<NOISE>(E, S, g, t, th, c, root, scratch, k, err_out, eta);
+        int r = run_descents<NOISE, FORCED>(E, S, g, t, th, c, root, scratch, k, err_out, eta, fk);
         if (r == RD_FAIL) { c.pending = 0; return RD_FAIL; }
         if (r == RD_LEAF && plen_get(c, th) == 0) break;  // root expansion: the threads start after setRootState
     }
@@ -365,6 +366,30 @@ __device__ __forceinline__ float new_root_noise_cap(const Dev& E, int g, const C
     if (c.mode != 0) eta = full ? dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules)) : E.noise_value;
     if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
     return eta;
+}
+
+// the same with forced playouts in force (k_tree_step<.., NOISE = true, .., FORCED = true>, which also serves a self-play without
+// Dirichlet noise and the fast roots of a playout cap): a root that gets no draw gets the constant vector, as above
+__device__ __forceinline__ float new_root_noise_forced(const Dev& E, int g, const Ctl& c, const WS& root, bool full)
+{
+    float eta = 0.0f;
+    if (c.mode != 0)
+        eta = (full && E.noise_alpha > 0.0f) ? dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules)) : E.noise_value;
+    if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
+    return eta;
+}
+
+// N' of the root node `ridx` under policy target pruning (azr_forced.hpp), lane = move: the node's Q, P and sumN word, the root-level
+// noised prior of tree_select under the vector `eta`
+__device__ __forceinline__ uint32_t root_pruned_counts(const Dev& E, const Search& S, const Tree& t, uint32_t ridx, uint32_t N, uint64_t valid, float eta, float fk)
+{
+    const uint8_t* n = node_ptr(t, ridx);
+    const uint32_t l = lane_id(), ll = l < MOVES ? l : 0;
+    const float P = reinterpret_cast<const float*>(n + ND_P)[ll];
+    const float Q = reinterpret_cast<const float*>(n + ND_Q)[ll];
+    const uint32_t sumN = rfl(*reinterpret_cast<const uint32_t*>(n + ND_SUMN));
+    const float noiseP = __fadd_rn(__fmul_rn(S.c1, P), __fmul_rn(E.noise_eps, eta));
+    return prune_counts(N, Q, noiseP, valid, sumN, fk, S.hp);
 }
 
 }  // namespace azr

@@ -16,6 +16,7 @@
 // Everything is private to the game's wave: no atomics, no inter-wave sharing.
 #pragma once
 #include "azr_wave.hpp"
+#include "azr_forced.hpp"
 
 namespace azr {
 
@@ -357,9 +358,12 @@ __device__ __forceinline__ uint32_t tree_lookup_node(const Tree& t, uint32_t kd,
 // NOISE (this engine's own, off by default): at path depth 0 of a descent — `root_level`, the first selection of a search thread's
 // descent — the constant second term c2 = eps * DIR_NOISE_VALUE becomes eps * eta[move], eta the game's root noise vector (lane i <->
 // move i); every other level keeps c2.  The stored P stays the clean prior.  Without NOISE the parameters are dead.
-template <bool NOISE = false>
+// FORCED (this engine's own, off by default; instantiated with NOISE only): at `root_level` with a factor fk > 0, the moves that have
+// been tried and are short of nf = sqrt(fk * noiseP * sumN) completed visits (azr_forced.hpp) are, if there are any, the only
+// candidates; score, strict maximum and tie rule stay.  No forced move: the selection below, bit for bit.
+template <bool NOISE = false, bool FORCED = false>
 __device__ __forceinline__ uint32_t tree_select(const Tree& t, uint32_t idx, const NodeRegs& nr, const Search& S, uint32_t stamp, int8_t* scratch,
-                                                bool root_level = false, float eps = 0.0f, float eta = 0.0f)
+                                                bool root_level = false, float eps = 0.0f, float eta = 0.0f, float fk = 0.0f)
 {
     const uint8_t* n = node_ptr(t, idx);
     const uint32_t l = lane_id();
@@ -378,6 +382,13 @@ __device__ __forceinline__ uint32_t tree_select(const Tree& t, uint32_t idx, con
     const bool skip = ok && N == 0 && act == 1;
     float best = wave_max((ok && !skip) ? u : -INFINITY);
     uint64_t ties = ballot64(ok && !skip && u == best && u > -INFINITY);
+    if (FORCED && root_level && fk > 0.0f) {  // (a forced move has N > 0, so it is never a skipped one)
+        const bool forced = forced_move(ok, N, forced_nf(fk, noiseP, sumN));
+        if (ballot64(forced)) {
+            best = wave_max(forced ? u : -INFINITY);
+            ties = ballot64(forced && u == best && u > -INFINITY);
+        }
+    }
     if (ties == 0) {  // bestMove == None: duplicate the best skipped request (alphazero_mcts.cpp:111-114)
         best = wave_max(skip ? u : -INFINITY);
         ties = ballot64(skip && u == best && u > -INFINITY);

@@ -103,6 +103,8 @@ void Settings::init(int argc, char* argv[])
         {"cap-prob", "[this build] self-play playout cap: share of decisions that get the whole --mcts search, root noise and a training record; the others search --cap-fast simulations and write none (1 = off: every decision)", "1", false},
         {"cap-fast", "[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])", "0", false},
         {"cap-seed", "[this build] seed of the playout cap's coin (independent of --seed and --dir-seed: dice, deals and noise do not move)", std::to_string(CAP_SEED), false},
+        {"forced-k", "[this build] self-play forced playouts: a tried root move of a full decision is searched until it has sqrt(k * prior * visits) visits (0 = off; at most 8; KataGo runs 2)", "0", false},
+        {"prune-target", "[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits PUCT would not have spent (0 = off)", "0", false},
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -252,6 +254,27 @@ void Settings::init(int argc, char* argv[])
         CAP_FAST = (int)fs;
     }
     CAP_SEED = (uint32_t)strtoul(get("cap-seed").c_str(), nullptr, 10);
+    {
+        char* end = nullptr;
+        const std::string kv = get("forced-k");
+        const double fk = strtod(kv.c_str(), &end);
+        if (kv.empty() || *end != '\0' || !(fk >= 0.0) || fk > 8.0) {
+            fprintf(stderr, "--forced-k: '%s' is not a forced-playout factor (a number in [0, 8]; 0 = off)\n", kv.c_str());
+            exit(2);
+        }
+        FORCED_K = (float)fk;
+        const std::string pv = get("prune-target");
+        const long pt = strtol(pv.c_str(), &end, 10);
+        if (pv.empty() || *end != '\0' || (pt != 0 && pt != 1)) {
+            fprintf(stderr, "--prune-target: '%s' is neither 0 nor 1\n", pv.c_str());
+            exit(2);
+        }
+        if (pt == 1 && !(FORCED_K > 0.0f)) {
+            fprintf(stderr, "--prune-target: 1 needs --forced-k above 0 (pruning subtracts forced playouts; there are none)\n");
+            exit(2);
+        }
+        PRUNE_TARGET = (int)pt;
+    }
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
     DEVICE_MAP.clear();
@@ -723,6 +746,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         e.check(azr_selfplay_set_dirichlet(e.h, SETTINGS.DIR_ALPHA, SETTINGS.DIR_SEED), "selfplay_set_dirichlet");
         // playout cap of the generated games: --cap-prob 1 / --cap-fast 0 (default) search and record every decision
         e.check(azr_selfplay_set_playout_cap(e.h, SETTINGS.CAP_PROB, SETTINGS.CAP_FAST, SETTINGS.CAP_SEED), "selfplay_set_playout_cap");
+        // forced playouts / policy target pruning of the generated games: --forced-k 0 / --prune-target 0 (default) are the search and the records above
+        e.check(azr_selfplay_set_forced_playouts(e.h, SETTINGS.FORCED_K, SETTINGS.PRUNE_TARGET), "selfplay_set_forced_playouts");
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);

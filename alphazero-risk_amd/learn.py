@@ -205,6 +205,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
             # stream continues where its previous iteration stopped, so no (iteration, rank) pair ever replays a game
             gen.selfplay_set_dirichlet(getattr(a, "dir_alpha", 0.0), getattr(a, "dir_seed", 0))   # root noise of the generated games only (0 = the reference's constant)
             gen.selfplay_set_playout_cap(getattr(a, "cap_prob", 1.0), getattr(a, "cap_fast", 0), getattr(a, "cap_seed", 0))   # playout cap of the generated games only (1 / 0 = off)
+            gen.selfplay_set_forced_playouts(getattr(a, "forced_k", 0.0), getattr(a, "prune_target", 0))   # forced playouts / target pruning of the generated games only (0 / 0 = off)
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -343,6 +344,12 @@ def main():
                          "record; the others search --cap-fast simulations and write none (1 = off)")
     ap.add_argument("--cap-fast", type=int, default=0, help="[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])")
     ap.add_argument("--cap-seed", type=int, default=0, help="[this build] seed of the playout cap's coin (dice, deals and root noise do not move)")
+    ap.add_argument("--forced-k", type=float, default=0.0,
+                    help="[this build] self-play forced playouts: a tried root move of a full decision is searched until it has "
+                         "sqrt(k * prior * visits) visits (0 = off; at most 8)")
+    ap.add_argument("--prune-target", type=int, default=0,
+                    help="[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits "
+                         "PUCT would not have spent (0 = off)")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -360,6 +367,10 @@ def main():
         ap.error(f"--cap-prob: {a.cap_prob} is not a probability (a number in [0, 1]; 1 = off)")
     if a.cap_fast < 0 or (a.cap_prob < 1.0 and a.cap_fast > 0 and not a.t <= a.cap_fast <= a.mcts):
         ap.error(f"--cap-fast: {a.cap_fast} simulations are outside [{a.t} search threads (-t), {a.mcts} simulations (--mcts)]")
+    if not 0.0 <= a.forced_k <= 8.0:   # (a NaN fails both comparisons)
+        ap.error(f"--forced-k: {a.forced_k} is not a forced-playout factor (a number in [0, 8]; 0 = off)")
+    if a.prune_target not in (0, 1) or (a.prune_target == 1 and not a.forced_k > 0.0):
+        ap.error(f"--prune-target: {a.prune_target} is neither 0 nor 1, or is 1 without --forced-k above 0")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():
         learn(a)

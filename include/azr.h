@@ -251,6 +251,52 @@ int azr_selfplay_decision_kind(azr_engine* h, uint8_t* full_host);
 int azr_debug_playout_cap(azr_engine* h, float full_prob, uint32_t cap_seed, const uint32_t* game_seed,
                           const uint32_t* decision, int n, uint8_t* full_out);
 
+/* ---- forced playouts and policy target pruning at the root (this engine's own; off after azr_engine_create) ---------
+ * The reference has neither.  Both follow KataGo (Wu 2019, section 3.2) and exist to make sampled root noise worth having: a noised
+ * root move is tried often enough for its value to be known, and the visits spent that way do not reach the recorded pi.
+ * All arithmetic below is fp32, each operation rounded on its own (no fused multiply-add), in the order written.
+ *
+ * noiseP[m] is the root-level noised prior of the selection: (1 - DIR_NOISE_EPSI) * P[m] + DIR_NOISE_EPSI * eta[m] with a root
+ * vector in force (see "root noise"), (1 - DIR_NOISE_EPSI) * P[m] + DIR_NOISE_EPSI * DIR_NOISE_VALUE otherwise — the same number as
+ * eta[m] = DIR_NOISE_VALUE gives.  sumN is the root node's visit total as the selection reads it, N[m] the completed visits of
+ * move m (visits in flight in other search threads are not counted, as in the PUCT term).
+ *     nf[m] = sqrt((k * noiseP[m]) * (float)sumN)
+ *
+ * Forced playouts, factor k > 0.  At the FIRST selection of a descent (path depth 0) a legal move m is forced iff N[m] > 0 and
+ * (float)N[m] < nf[m].  If at least one move is forced, the selection runs over the forced moves alone — same score, same strict
+ * maximum, same tie rule, same bookkeeping; if none is, it is the selection without the feature, bit for bit.  Deeper levels never
+ * force.  A root that carries visits over from the previous decision's tree is under the rule from its first descent.
+ *
+ * Policy target pruning.  With v[m] = (noiseP[m] * hp_exploration) * sqrt(1 + (float)sumN) and sumN, N, Q as the finished search
+ * left them:
+ *   1. c* = the legal move with the largest N, the lowest index on ties;  U* = Q[c*] + v[c*] / (1 + (float)N[c*]).
+ *   2. for every other legal m with N[m] > 0:  f = (uint32)nf[m] truncated (0 where nf is not a positive number);
+ *      lower = N[m] > f ? N[m] - f : 0;  N' = N[m];
+ *      while (N' > lower  &&  Q[m] + v[m] / (1 + (float)(N' - 1)) < U*)  N' -= 1;
+ *      if (N' == 1 && N' < N[m])  N' = 0;                      (a child reduced to a single playout is pruned outright)
+ *   3. N'[c*] = N[c*]; a move with N[m] == 0 keeps 0.
+ *   4. the pruned policy is azr_mcts_policy's formula on N'.
+ * The MOVE of a decision is always picked from the unpruned N: a search with pruning on plays the same games with the same RNG
+ * streams and the same z as with pruning off; only pi (bytes 93..264) of its records differs.
+ *
+ * With a playout cap: a fast decision never forces (and writes no record, so has nothing to prune); a full one forces and prunes.
+ * The arena (azr_arena_*) never sees either.
+ *
+ * host-stepped searches: k <= 0 = off.  Holds until set again; azr_selfplay_start* ends it. */
+int azr_mcts_set_forced_playouts(azr_engine* h, float k);
+/* the pruned policy pi_host [G][43] and, if not NULL, N' n_pruned_host [G][43] of the last search's roots, under the factor and the
+ * root vector in force (a running self-play's, else the host-stepped ones); no factor in force: N' = N.  azr_mcts_policy stays the
+ * unpruned policy. */
+int azr_mcts_pruned_policy(azr_engine* h, float* pi_host, uint32_t* n_pruned_host);
+/* device self-play: k > 0 forces playouts in every full decision; prune != 0 also writes the pruned policy into the records.
+ * k <= 0 = off (default).  Read by azr_selfplay_start*; a running self-play never sees a change.  prune != 0 with k <= 0 is an
+ * error.  Every setter: AZR_E_INVALID_ARGUMENT, with a reason in azr_last_error, for a NaN k or k > 8. */
+int azr_selfplay_set_forced_playouts(azr_engine* h, float k, int prune);
+/* the budget of host-stepped searches (azr_mcts_simulate / azr_mcts_begin..apply), so that a caller can retrace a capped self-play
+ * decision by decision: simulations in [mcts_threads, mcts_simulations] (S - S % mcts_threads descents), <= 0 = the settings' own
+ * (default).  Holds until set again; azr_selfplay_start* ends it.  The arena and device self-play never see it. */
+int azr_mcts_set_simulations(azr_engine* h, int simulations);
+
 /* ---- device-resident self-play (trainer move loop, alphazero_trainer.cpp:80-119) --------------------------- */
 /* (Re)start all G games: game g plays seeds base_seed + g, then base_seed + G + g, ... */
 int azr_selfplay_start(azr_engine* h, uint32_t base_seed);
@@ -262,6 +308,9 @@ int azr_selfplay_start_games(azr_engine* h, uint32_t base_seed, uint64_t games);
  * (azr_engine_set_states / azr_engine_set_rng; states must be running games), its records start there; a finished game's
  * slot restarts as under azr_selfplay_start (seeds base_seed + G + g, base_seed + 2G + g, ...). */
 int azr_selfplay_start_from_states(azr_engine* h, uint32_t base_seed);
+/* Both at once: the games of slots 0 .. min(games, G) - 1 go on from the states and RNG streams the caller has set, seeds
+ * base_seed + slot; the other slots idle.  With games <= G no further game is started: the run is over when those games are. */
+int azr_selfplay_start_games_from_states(azr_engine* h, uint32_t base_seed, uint64_t games);
 /* Run `passes` passes of the hot path: every pass = one tree step (backup/expand + select to the next leaf,
  * decisions, moves, game restarts — all on device) + one batched net evaluation of the G leaves. */
 int azr_selfplay_run(azr_engine* h, int passes);
