@@ -442,11 +442,12 @@ static int plan_sb(int sb_mode, int n)
         // Relative time of one 256-workgroup round of 2 / 3 / 4 boards per workgroup.  One workgroup per CU is resident, so a launch
         // of w workgroups takes ceil(w / 256) rounds, and only the RATIOS of the round times enter the choice: the three tiles are
         // the same MFMA-bound code, so a box that clocks lower stretches all three alike.  The ratios are those of the tiles'
-        // measured shader cycles per workgroup (1.115 / 1.415 / 1.938 M cycles); launch times measured on three
-        // boxes of the pool (1.77 - 2.0 GHz sustained): 0.61 / 0.80 / 1.05 ms, 0.63 / 0.82 / 1.07 and 0.68 / 0.89 / 1.18 — the same
-        // ratios to 2 %, far inside the margins the plan turns on (the closest call, 768 boards: 3 x 256 at 0.73 against 2 rounds of
-        // 2-board tiles at 1.15).
-        static const float T[5] = {0.0f, 0.0f, 0.575f, 0.730f, 1.0f};
+        // measured shader cycles per workgroup (1.126 / 1.414 / 1.903 M cycles, profiles/tower_boundary_timing.txt;
+        // launch times there 0.568 / 0.724 / 0.955 ms).  Before the 4-board tile lost its LDS residual slots the ratios were
+        // 0.575 / 0.730, and launch times on three boxes of the pool (1.77 - 2.0 GHz sustained) — 0.61 / 0.80 / 1.05 ms, 0.63 / 0.82 / 1.07
+        // and 0.68 / 0.89 / 1.18 — gave the same ratios to 2 %: far inside the margins the plan turns on (the closest call, 768 boards:
+        // 3 x 256 at 0.74 against 2 rounds of 2-board tiles at 1.18; the two sets of ratios choose alike up to 10 752 boards).
+        static const float T[5] = {0.0f, 0.0f, 0.590f, 0.743f, 1.0f};
         float best = 0.0f;
         for (int c = 4; c >= 2; c--) {
             const int w = (n + c - 1) / c;
