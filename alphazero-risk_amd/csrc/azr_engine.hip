@@ -186,9 +186,10 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // FORCED (with NOISE only; a search without a sampled vector runs on the constant one, which is the constant form bit for bit): forced
 // playouts at path depth 0 with the factor E.forced_k (azr_forced.hpp) — not in a fast decision; with E.prune the staged record's pi
 // comes from the pruned counts N', the move still from N.
-template <bool SELFPLAY, bool NOISE, bool CAP = false, bool FORCED = false>
+template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
+    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED), "CAP needs SELFPLAY, FORCED implies NOISE: tree_step_kernel lists the nine");
     __shared__ int8_t scratch[128];
     const int g = blockIdx.x;
     TP_BEGIN();
@@ -252,7 +253,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             root_dirty = true;
             TP(18);
             if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
-            if (NOISE) eta = FORCED ? new_root_noise_forced(E, g, c, root, full) : CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);   // the next decision's root, or the next game's first
+            if (NOISE) eta = new_root_noise<CAP, FORCED>(E, g, c, root, full);   // the next decision's root, or the next game's first
             if (c.mode == 0) break;  // quota exhausted: the slot idles
             tree_trim(t, c);
             c.sims_done = 0; c.sims_started = 0;
@@ -268,7 +269,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                 selfplay_next_game(E, g, t, c, root);
                 root_dirty = true;
                 if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
-                if (NOISE) eta = FORCED ? new_root_noise_forced(E, g, c, root, full) : CAP ? new_root_noise_cap(E, g, c, root, full) : new_root_noise(E, g, c, root);
+                if (NOISE) eta = new_root_noise<CAP, FORCED>(E, g, c, root, full);
                 if (c.mode == 0) break;
                 tree_trim(t, c);
                 continue;
@@ -391,7 +392,10 @@ __global__ __launch_bounds__(64) void k_selfplay_start(Dev E, int keep)
     ctl_store(c, &E.ctl[g]);
 }
 
-// the first root's noise vector of every slot (azr_selfplay_start* with azr_selfplay_set_dirichlet in force)
+// the first root's vector of every slot (azr_selfplay_start* whose steps carry NOISE).  CAP: a slot whose first decision is fast starts on
+// the constant vector; FORCED: so does every root without a draw (no Dirichlet set, or a fast first decision; without a cap the coin says
+// full).  Without either the coin is not computed.
+template <bool CAP, bool FORCED>
 __global__ __launch_bounds__(64) void k_selfplay_noise(Dev E)
 {
     const int g = blockIdx.x;
@@ -399,29 +403,7 @@ __global__ __launch_bounds__(64) void k_selfplay_noise(Dev E)
     ctl_load(c, &E.ctl[g]);
     WS root;
     ws_load(root, E.state + (size_t)g * GREC);
-    new_root_noise(E, g, c, root);
-}
-
-// the same with a playout cap in force: a slot whose first decision is fast starts on the constant vector
-__global__ __launch_bounds__(64) void k_selfplay_noise_cap(Dev E)
-{
-    const int g = blockIdx.x;
-    Ctl c;
-    ctl_load(c, &E.ctl[g]);
-    WS root;
-    ws_load(root, E.state + (size_t)g * GREC);
-    new_root_noise_cap(E, g, c, root, cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions));
-}
-
-// the same with forced playouts in force: a root without a draw (no Dirichlet set, or a fast first decision) starts on the constant vector
-__global__ __launch_bounds__(64) void k_selfplay_noise_forced(Dev E)
-{
-    const int g = blockIdx.x;
-    Ctl c;
-    ctl_load(c, &E.ctl[g]);
-    WS root;
-    ws_load(root, E.state + (size_t)g * GREC);
-    new_root_noise_forced(E, g, c, root, cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions));
+    new_root_noise<CAP, FORCED>(E, g, c, root, (CAP || FORCED) ? cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions) : true);
 }
 
 // azr_mcts_pruned_policy: N' and the policy over N' of every game's root, under E.forced_k (<= 0: N' = N) and the root vector in force
@@ -713,6 +695,8 @@ struct DevBuf {
     if (!(h)) return AZR_E_BAD_HANDLE;           \
     HIPCHK(h, hipSetDevice((h)->cfg.device))
 
+static int bad_argument(azr_engine* h, const std::string& why) { h->err = why; return AZR_E_INVALID_ARGUMENT; }
+
 // one 32-bit field of every game's Ctl line <-> a packed host array of G values (`field` = offsetof(Ctl, ...)): a strided copy queued on
 // the handle's stream, the caller synchronises
 static hipError_t ctl_field_get(azr_engine* h, size_t field, void* dst)
@@ -850,34 +834,52 @@ extern "C" int azr_mcts_begin(azr_engine* h)
     return AZR_OK;
 }
 
-// the k_tree_step instantiation of a host-stepped search (azr_mcts_*) or of device self-play, with or without root noise
-// or a playout cap (self-play only); with forced playouts the three FORCED instantiations, which carry NOISE
-static hipError_t launch_tree_step(azr_engine* h, const Dev& d, bool selfplay, bool noise, bool cap = false, bool forced = false)
+// The nine k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
+// self-play also under a CAP, which doubles its three.  CAP needs SELFPLAY and FORCED implies NOISE (k_tree_step asserts both).
+// Callers say what is in force; forced playouts without root noise run the NOISE instantiation, on the constant vector.
+static int launch_tree_step(azr_engine* h, const Dev& d, bool selfplay, const StepOpts& o)
 {
-    void (*step)(Dev) = selfplay ? (cap ? (noise ? k_tree_step<true, true, true> : k_tree_step<true, false, true>)
-                                        : (noise ? k_tree_step<true, true> : k_tree_step<true, false>))
-                                 : (noise ? k_tree_step<false, true> : k_tree_step<false, false>);
-    if (forced) step = selfplay ? (cap ? k_tree_step<true, true, true, true> : k_tree_step<true, true, false, true>) : k_tree_step<false, true, false, true>;
+    void (*step)(Dev) = nullptr;
+#define AZR_STEP(SP, N, C, F) case (SP) << 3 | (N) << 2 | (C) << 1 | (F): step = k_tree_step<SP, N, C, F>; break
+    switch (selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
+        AZR_STEP(0, 0, 0, 0); AZR_STEP(0, 1, 0, 0); AZR_STEP(0, 1, 0, 1);
+        AZR_STEP(1, 0, 0, 0); AZR_STEP(1, 1, 0, 0); AZR_STEP(1, 1, 0, 1);
+        AZR_STEP(1, 0, 1, 0); AZR_STEP(1, 1, 1, 0); AZR_STEP(1, 1, 1, 1);
+    }
+#undef AZR_STEP
+    if (!step) { h->err = "launch_tree_step: a playout cap on a host-stepped search: there is no such k_tree_step"; return AZR_E_LOGIC; }
     hipLaunchKernelGGL(step, dim3(d.G), dim3(64), 0, h->stream, d);
-    return hipGetLastError();
+    HIPCHK(h, hipGetLastError());
+    return AZR_OK;
 }
 
-// the device view of a host-stepped search: the handle's, with azr_mcts_set_forced_playouts / azr_mcts_set_simulations applied
-static Dev host_search_view(const azr_engine* h)
+// What is in force in `mode` (the handle's, or 1 for a host-stepped step whatever the handle ran before): a running self-play's options
+// as azr_selfplay_start* found them, nothing in an arena, else the host-stepped ones as they stand.
+static StepOpts options_in_force(const azr_engine* h, int mode)
+{
+    if (mode == 2) return h->sp;
+    if (mode == 3) return StepOpts{};
+    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f};
+}
+// ... and the device view a search-related launch sees with it.  eta_const: no root vector is there to read (a self-play whose steps
+// carry NOISE keeps one per root).  Outside a self-play: the handle's without a self-play's leftovers, with azr_mcts_set_forced_playouts /
+// azr_mcts_set_simulations applied; the steps without FORCED read none of forced_k, prune and eta_const.
+static Dev search_view(const azr_engine* h, int mode)
 {
     Dev d = h->d;
-    d.forced_k = h->forced_host;
+    const StepOpts o = options_in_force(h, mode);
+    d.eta_const = (o.noise || (mode == 2 && o.forced)) ? 0 : 1;
+    if (mode == 2) return d;
+    d.forced_k = o.forced ? h->host.forced_k : 0.0f;
     d.prune = 0;
-    d.eta_const = h->noise_host ? 0 : 1;
-    if (h->host_sims > 0) d.search.simulations = h->host_sims - h->host_sims % d.T;
+    if (mode != 3 && h->host.sims > 0) d.search.simulations = h->host.sims - h->host.sims % d.T;
     return d;
 }
 
 static int tree_step_host(azr_engine* h, uint32_t* active)
 {
     HIPCHK(h, hipMemsetAsync(h->d.active, 0, 4, h->stream));
-    if (h->forced_host > 0.0f || h->host_sims > 0) HIPCHK(h, launch_tree_step(h, host_search_view(h), false, h->noise_host || h->forced_host > 0.0f, false, h->forced_host > 0.0f));
-    else HIPCHK(h, launch_tree_step(h, h->d, false, h->noise_host));
+    if (int rc = launch_tree_step(h, search_view(h, 1), false, options_in_force(h, 1))) return rc;
     D2H(h, active, h->d.active, 4);
     SYNC(h);
     return AZR_OK;
@@ -968,6 +970,31 @@ extern "C" int azr_mcts_pick(azr_engine* h, int sample, uint8_t* moves)
 }
 
 // ---- device-resident self-play ------------------------------------------------------------------------
+// a playout cap's full_prob: a number >= 0, and the coin's threshold it stands for (2^24, every decision full, from 1 up)
+static int full_prob_check(azr_engine* h, const char* who, float full_prob, const char* note)
+{
+    return full_prob >= 0.0f ? AZR_OK : bad_argument(h, std::string(who) + ": full_prob must be a number >= 0" + note);   // (NaN fails)
+}
+static uint32_t cap_threshold_of(float full_prob) { return full_prob >= 1.0f ? (1u << 24) : (uint32_t)(full_prob * 16777216.0f); }
+
+// The azr_selfplay_set_* options as they stand now, into what this self-play's steps carry (h->sp) and the Dev fields they read: a
+// running self-play never sees a setter's change.  The host-stepped options end here (root_eta is this self-play's from now on).
+static void resolve_selfplay_options(azr_engine* h)
+{
+    const SelfplayOpts& o = h->sp_set;
+    Dev& d = h->d;
+    h->host = HostOpts{};
+    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f};
+    d.noise_alpha = o.alpha;
+    d.noise_seed = o.noise_seed;
+    d.cap_threshold = cap_threshold_of(o.cap_prob);
+    d.cap_seed = o.cap_seed;
+    d.cap_fast = h->sp.cap ? o.cap_fast_sims - o.cap_fast_sims % d.T : d.search.simulations;
+    d.forced_k = o.forced_k;
+    d.prune = h->sp.forced && o.prune ? 1 : 0;
+    d.eta_const = 0;
+}
+
 static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long quota, int keep = 0)
 {
     h->d.base_seed = base_seed;
@@ -980,27 +1007,10 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
     HIPCHK(h, hipMemsetAsync(h->d.counters, 0, (size_t)h->d.G * sizeof(Counters), h->stream));
     HIPCHK(h, hipMemsetAsync(h->d.ring_count, 0, sizeof(unsigned long long), h->stream));
     LAUNCH(h, k_selfplay_start, h->d, keep);
-    // root noise as azr_selfplay_set_dirichlet stands now: a running self-play never sees a change.  A vector set for host-stepped
-    // searches ends here (the array is this self-play's from now on).
-    h->noise_host = false;
-    h->sp_noise = h->sp_alpha > 0.0f;
-    h->d.noise_alpha = h->sp_alpha;
-    h->d.noise_seed = h->sp_noise_seed;
-    // the playout cap as azr_selfplay_set_playout_cap stands now, read the same way
-    h->sp_cap = h->cap_prob < 1.0f && h->cap_fast_sims > 0;
-    h->d.cap_threshold = h->sp_cap ? (uint32_t)(h->cap_prob * 16777216.0f) : (1u << 24);
-    h->d.cap_seed = h->cap_seed;
-    h->d.cap_fast = h->sp_cap ? h->cap_fast_sims - h->cap_fast_sims % h->d.T : h->d.search.simulations;
-    // forced playouts and pruning as azr_selfplay_set_forced_playouts stands now; the host-stepped factor and budget end here
-    h->forced_host = 0.0f;
-    h->host_sims = 0;
-    h->sp_forced = h->sp_forced_k > 0.0f;
-    h->d.forced_k = h->sp_forced ? h->sp_forced_k : 0.0f;
-    h->d.prune = h->sp_forced && h->sp_prune ? 1 : 0;
-    h->d.eta_const = 0;
-    if (h->sp_forced) LAUNCH(h, k_selfplay_noise_forced, h->d);
-    else if (h->sp_noise && h->sp_cap) LAUNCH(h, k_selfplay_noise_cap, h->d);
-    else if (h->sp_noise) LAUNCH(h, k_selfplay_noise, h->d);
+    resolve_selfplay_options(h);
+    if (h->sp.forced) LAUNCH(h, (k_selfplay_noise<false, true>), h->d);
+    else if (h->sp.noise && h->sp.cap) LAUNCH(h, (k_selfplay_noise<true, false>), h->d);
+    else if (h->sp.noise) LAUNCH(h, (k_selfplay_noise<false, false>), h->d);
     else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, (size_t)h->d.G * MOVES * sizeof(float), h->stream));
     SYNC(h);
     return AZR_OK;
@@ -1014,20 +1024,24 @@ extern "C" int azr_mcts_set_root_noise(azr_engine* h, const float* eta)
     if (eta) H2D(h, h->d.root_eta, eta, sz);
     else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, sz, h->stream));
     SYNC(h);
-    h->noise_host = eta != nullptr;
+    h->host.noise = eta != nullptr;
     if (h->mode == 2) h->mode = 0;   // the array was a running self-play's: that self-play is over (azr_selfplay_start* begins the next)
     return AZR_OK;
+}
+
+// alpha of a Dirichlet draw: a number in (0, 10]; `off_ok`: or <= 0, which switches the noise off
+static int alpha_check(azr_engine* h, const char* who, float alpha, bool off_ok)
+{
+    if (alpha <= DIR_ALPHA_MAX && (off_ok || alpha > 0.0f)) return AZR_OK;   // (NaN fails)
+    return bad_argument(h, std::string(who) + (off_ok ? ": alpha must be a number <= 10 (<= 0 = off)" : ": alpha must be a number in (0, 10]"));
 }
 
 extern "C" int azr_selfplay_set_dirichlet(azr_engine* h, float alpha, uint32_t noise_seed)
 {
     if (!h) return AZR_E_BAD_HANDLE;
-    if (alpha != alpha || alpha > DIR_ALPHA_MAX) {
-        h->err = "azr_selfplay_set_dirichlet: alpha must be a number <= 10 (<= 0 = off)";
-        return AZR_E_INVALID_ARGUMENT;
-    }
-    h->sp_alpha = alpha > 0.0f ? alpha : 0.0f;
-    h->sp_noise_seed = noise_seed;
+    if (int rc = alpha_check(h, "azr_selfplay_set_dirichlet", alpha, true)) return rc;
+    h->sp_set.alpha = alpha > 0.0f ? alpha : 0.0f;
+    h->sp_set.noise_seed = noise_seed;
     return AZR_OK;
 }
 
@@ -1036,8 +1050,7 @@ extern "C" int azr_mcts_root_noise(azr_engine* h, float* eta)
     ENTER(h);
     if (!eta) return AZR_E_INVALID_ARGUMENT;
     const size_t sz = (size_t)h->d.G * MOVES * sizeof(float);
-    const bool in_force = h->mode == 2 ? h->sp_noise : h->mode == 3 ? false : h->noise_host;
-    if (!in_force) { memset(eta, 0, sz); return AZR_OK; }
+    if (!options_in_force(h, h->mode).noise) { memset(eta, 0, sz); return AZR_OK; }
     D2H(h, eta, h->d.root_eta, sz);
     SYNC(h);
     return AZR_OK;
@@ -1047,10 +1060,7 @@ extern "C" int azr_debug_root_noise(azr_engine* h, float alpha, uint32_t noise_s
                                     const uint64_t* valid, int n, float* eta_out)
 {
     ENTER(h);
-    if (alpha != alpha || alpha > DIR_ALPHA_MAX || !(alpha > 0.0f)) {
-        h->err = "azr_debug_root_noise: alpha must be a number in (0, 10]";
-        return AZR_E_INVALID_ARGUMENT;
-    }
+    if (int rc = alpha_check(h, "azr_debug_root_noise", alpha, false)) return rc;
     if (n < 0 || (n > 0 && (!game_seed || !decision || !valid || !eta_out))) return AZR_E_INVALID_ARGUMENT;
     if (n == 0) return AZR_OK;
     DevBuf bs, bd, bv, bo;
@@ -1082,19 +1092,23 @@ extern "C" int azr_mcts_set_forced_playouts(azr_engine* h, float k)
     if (!h) return AZR_E_BAD_HANDLE;
     int rc = forced_k_check(h, "azr_mcts_set_forced_playouts", k);
     if (rc) return rc;
-    h->forced_host = k > 0.0f ? k : 0.0f;
+    h->host.forced_k = k > 0.0f ? k : 0.0f;
     return AZR_OK;
+}
+
+// a search budget below the settings': n - n % T descents, at least one per search thread and no more than mcts_simulations
+static int simulations_check(azr_engine* h, const char* who, const char* what, int n, const char* note)
+{
+    if (n >= h->cfg.mcts_threads && n <= h->cfg.mcts_simulations) return AZR_OK;
+    return bad_argument(h, std::string(who) + ": " + what + " = " + std::to_string(n) + " outside [mcts_threads = " + std::to_string(h->cfg.mcts_threads) +
+                               ", mcts_simulations = " + std::to_string(h->cfg.mcts_simulations) + "]" + note);
 }
 
 extern "C" int azr_mcts_set_simulations(azr_engine* h, int simulations)
 {
     if (!h) return AZR_E_BAD_HANDLE;
-    if (simulations > 0 && (simulations < h->cfg.mcts_threads || simulations > h->cfg.mcts_simulations)) {
-        h->err = "azr_mcts_set_simulations: simulations = " + std::to_string(simulations) + " outside [mcts_threads = " +
-                 std::to_string(h->cfg.mcts_threads) + ", mcts_simulations = " + std::to_string(h->cfg.mcts_simulations) + "]";
-        return AZR_E_INVALID_ARGUMENT;
-    }
-    h->host_sims = simulations > 0 ? simulations : 0;
+    if (int rc = simulations > 0 ? simulations_check(h, "azr_mcts_set_simulations", "simulations", simulations, "") : AZR_OK) return rc;
+    h->host.sims = simulations > 0 ? simulations : 0;
     return AZR_OK;
 }
 
@@ -1107,8 +1121,8 @@ extern "C" int azr_selfplay_set_forced_playouts(azr_engine* h, float k, int prun
         h->err = "azr_selfplay_set_forced_playouts: prune != 0 needs k > 0 (pruning subtracts forced playouts; there are none)";
         return AZR_E_INVALID_ARGUMENT;
     }
-    h->sp_forced_k = k > 0.0f ? k : 0.0f;
-    h->sp_prune = prune != 0;
+    h->sp_set.forced_k = k > 0.0f ? k : 0.0f;
+    h->sp_set.prune = prune != 0;
     return AZR_OK;
 }
 
@@ -1116,9 +1130,7 @@ extern "C" int azr_mcts_pruned_policy(azr_engine* h, float* pi, uint32_t* n_prun
 {
     ENTER(h);
     if (!pi) return AZR_E_INVALID_ARGUMENT;
-    Dev d = h->mode == 2 ? h->d : host_search_view(h);
-    if (h->mode == 2) d.eta_const = (h->sp_noise || h->sp_forced) ? 0 : 1;
-    if (h->mode == 3) d.forced_k = 0.0f;   // the arena never forces
+    const Dev d = search_view(h, h->mode);
     const size_t sz = (size_t)h->d.G * MOVES * 4;
     DevBuf bn, bp;
     HIPCHK(h, bn.alloc(sz)); HIPCHK(h, bp.alloc(sz));
@@ -1140,20 +1152,13 @@ extern "C" int azr_selfplay_start_games_from_states(azr_engine* h, uint32_t base
 extern "C" int azr_selfplay_set_playout_cap(azr_engine* h, float full_prob, int fast_simulations, uint32_t cap_seed)
 {
     if (!h) return AZR_E_BAD_HANDLE;
-    if (full_prob != full_prob || full_prob < 0.0f) {
-        h->err = "azr_selfplay_set_playout_cap: full_prob must be a number >= 0 (>= 1 = off)";
-        return AZR_E_INVALID_ARGUMENT;
-    }
+    if (int rc = full_prob_check(h, "azr_selfplay_set_playout_cap", full_prob, " (>= 1 = off)")) return rc;
     const bool on = full_prob < 1.0f && fast_simulations > 0;
-    if (on && (fast_simulations < h->cfg.mcts_threads || fast_simulations > h->cfg.mcts_simulations)) {
-        h->err = "azr_selfplay_set_playout_cap: fast_simulations = " + std::to_string(fast_simulations) + " outside [mcts_threads = " +
-                 std::to_string(h->cfg.mcts_threads) + ", mcts_simulations = " + std::to_string(h->cfg.mcts_simulations) +
-                 "] (F - F % T descents would be none, or more than a full decision's)";
-        return AZR_E_INVALID_ARGUMENT;
-    }
-    h->cap_prob = on ? full_prob : 1.0f;
-    h->cap_fast_sims = on ? fast_simulations : 0;
-    h->cap_seed = cap_seed;
+    if (int rc = on ? simulations_check(h, "azr_selfplay_set_playout_cap", "fast_simulations", fast_simulations,
+                                        " (F - F % T descents would be none, or more than a full decision's)") : AZR_OK) return rc;
+    h->sp_set.cap_prob = on ? full_prob : 1.0f;
+    h->sp_set.cap_fast_sims = on ? fast_simulations : 0;
+    h->sp_set.cap_seed = cap_seed;
     return AZR_OK;
 }
 
@@ -1161,7 +1166,7 @@ extern "C" int azr_selfplay_decision_kind(azr_engine* h, uint8_t* full_host)
 {
     ENTER(h);
     if (!full_host) return AZR_E_INVALID_ARGUMENT;
-    if (h->mode != 2 || !h->sp_cap) { memset(full_host, 1, (size_t)h->d.G); return AZR_OK; }
+    if (!options_in_force(h, h->mode).cap) { memset(full_host, 1, (size_t)h->d.G); return AZR_OK; }
     LAUNCH_OUT(h, full_host, (size_t)h->d.G, uint8_t, k_decision_kind, h->d);
     return AZR_OK;
 }
@@ -1170,18 +1175,14 @@ extern "C" int azr_debug_playout_cap(azr_engine* h, float full_prob, uint32_t ca
                                      int n, uint8_t* full_out)
 {
     ENTER(h);
-    if (full_prob != full_prob || full_prob < 0.0f) {
-        h->err = "azr_debug_playout_cap: full_prob must be a number >= 0";
-        return AZR_E_INVALID_ARGUMENT;
-    }
+    if (int rc = full_prob_check(h, "azr_debug_playout_cap", full_prob, "")) return rc;
     if (n < 0 || (n > 0 && (!game_seed || !decision || !full_out))) return AZR_E_INVALID_ARGUMENT;
     if (n == 0) return AZR_OK;
-    const uint32_t threshold = full_prob >= 1.0f ? (1u << 24) : (uint32_t)(full_prob * 16777216.0f);
     DevBuf bs, bd, bo;
     HIPCHK(h, bs.alloc((size_t)n * 4)); HIPCHK(h, bd.alloc((size_t)n * 4)); HIPCHK(h, bo.alloc((size_t)n));
     H2D(h, bs.p, game_seed, (size_t)n * 4);
     H2D(h, bd.p, decision, (size_t)n * 4);
-    hipLaunchKernelGGL(k_debug_playout_cap, dim3((n + 63) / 64), dim3(64), 0, h->stream, threshold, cap_seed, (const uint32_t*)bs.p,
+    hipLaunchKernelGGL(k_debug_playout_cap, dim3((n + 63) / 64), dim3(64), 0, h->stream, cap_threshold_of(full_prob), cap_seed, (const uint32_t*)bs.p,
                        (const uint32_t*)bd.p, n, (uint8_t*)bo.p);
     HIPCHK(h, hipGetLastError());
     D2H(h, full_out, bo.p, (size_t)n);
@@ -1239,7 +1240,7 @@ extern "C" int azr_selfplay_run(azr_engine* h, int passes)
         if (h->sp_tail) HIPCHK(h, hipMemsetAsync(h->d.leaf_count, 0, sizeof(int), h->stream));
         const ProfEvents* ev = prof ? &h->ev[k] : nullptr;   // this pass's events, if it is a sampled one
         if (ev) HIPCHK(h, hipEventRecord(ev->tree0, h->stream));
-        HIPCHK(h, launch_tree_step(h, h->d, true, h->sp_noise, h->sp_cap, h->sp_forced));
+        if (int rc = launch_tree_step(h, h->d, true, h->sp)) return rc;
         if (ev) HIPCHK(h, hipEventRecord(ev->tree1, h->stream));
         if (h->sp_tail) {
             D2H(h, &n_eval, h->d.leaf_count, sizeof(int));

@@ -99,24 +99,45 @@ struct Dev {
     int lc_base;               // ... row (x 2) the arena step counts into
     int lc_zero;               // ... row (x 2) the arena step zeroes for the next pass (nobody reads it any more), or -1
     int arena_collect;         // stage (s, pi, player) per AlphaZero decision and flush finished games to the record ring
-    // root noise (this engine's own; read by k_tree_step<.., true> only, never by the arena)
+    // root noise (this engine's own; read by the k_tree_step instantiations with NOISE only, never by the arena)
     float* root_eta;           // [G][43]  the vector in force at each game's root (lane i <-> move i)
     float noise_eps;           // DIR_NOISE_EPSI: noiseP = c1 * P + noise_eps * eta at path depth 0
     float noise_alpha;         // device self-play: Dirichlet(alpha) per new root ...
     uint32_t noise_seed;       // ... keyed by (noise_seed, game seed, decision, move)
-    // playout cap (this engine's own; read by k_tree_step<true, .., true> and the kernels of azr_selfplay_decision_kind /
-    // azr_debug_playout_cap only): decision d of the game with seed s is full iff cap_full(cap_threshold, cap_seed, s, d) (azr_cap.hpp)
+    // playout cap (this engine's own; read by the k_tree_step instantiations with CAP, k_selfplay_noise with CAP or FORCED and
+    // k_decision_kind only): decision d of the game with seed s is full iff cap_full(cap_threshold, cap_seed, s, d) (azr_cap.hpp)
     uint32_t cap_threshold;    // (uint32_t)(full_prob * 2^24)
     uint32_t cap_seed;
     int cap_fast;              // descents of a fast decision: fast_simulations - fast_simulations % T
     float noise_value;         // DIR_NOISE_VALUE: every entry of a fast root's vector (the constant form, bit for bit)
-    // forced playouts and policy target pruning (this engine's own; read by k_tree_step<.., FORCED = true>, k_selfplay_noise_forced and
-    // k_pruned_policy only; azr_forced.hpp)
+    // forced playouts and policy target pruning (this engine's own; read by the k_tree_step instantiations with FORCED,
+    // k_selfplay_noise<false, true> and k_pruned_policy only; azr_forced.hpp)
     float forced_k;            // the factor k of nf = sqrt(k * noiseP * sumN) (0 = off)
     int prune;                 // device self-play: a record's pi comes from the pruned counts
     int eta_const;             // host-stepped: no root vector is set, the search runs on the constant one (noise_value)
 };
 constexpr int ALOG = 16;
+
+// The options of the search variants (host side).  Which of them a tree step carries: root noise, a playout cap (self-play only),
+// forced playouts — the template arguments of k_tree_step after SELFPLAY.
+struct StepOpts { bool noise = false, cap = false, forced = false; };
+// Host-stepped searches (azr_mcts_*): in force from the setter's call until the next azr_selfplay_start*.
+struct HostOpts {
+    bool noise = false;        // azr_mcts_set_root_noise: a vector per game is set in d.root_eta
+    float forced_k = 0.0f;     // azr_mcts_set_forced_playouts (0 = off)
+    int sims = 0;              // azr_mcts_set_simulations: the budget (0 = the settings')
+};
+// Device self-play, as the azr_selfplay_set_* setters leave them.  A running self-play never sees a change: azr_selfplay_start* resolves
+// them into a StepOpts and Dev's noise_*, cap_*, forced_k and prune.
+struct SelfplayOpts {
+    float alpha = 0.0f;        // azr_selfplay_set_dirichlet (0 = off)
+    uint32_t noise_seed = 0;
+    float cap_prob = 1.0f;     // azr_selfplay_set_playout_cap (off: cap_prob >= 1 or cap_fast_sims <= 0)
+    int cap_fast_sims = 0;
+    uint32_t cap_seed = 0;
+    float forced_k = 0.0f;     // azr_selfplay_set_forced_playouts (0 = off)
+    bool prune = false;
+};
 
 // folded network parameters on device
 struct NetDev {
@@ -175,19 +196,9 @@ struct azr_engine {
     bool arena_open = false;      // between azr_arena_start and the azr_arena_run that found every slot idle
     int opp_simulations = -1;     // azr_arena_set_opponent_search: player B's count per decision and PUCT constant (< 0 = the handle's own);
     float opp_hp = -1.0f;         // copied into d.search2_* by azr_arena_start
-    bool noise_host = false;      // azr_mcts_set_root_noise: host-stepped searches run k_tree_step<false, true> on d.root_eta
-    float sp_alpha = 0.0f;        // azr_selfplay_set_dirichlet, as set ...
-    uint32_t sp_noise_seed = 0;
-    bool sp_noise = false;        // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, true>
-    float cap_prob = 1.0f;        // azr_selfplay_set_playout_cap, as set (off: cap_prob >= 1 or cap_fast_sims <= 0) ...
-    int cap_fast_sims = 0;
-    uint32_t cap_seed = 0;
-    bool sp_cap = false;          // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, .., true>
-    float forced_host = 0.0f;     // azr_mcts_set_forced_playouts: host-stepped searches run k_tree_step<false, true, false, true> (0 = off)
-    int host_sims = 0;            // azr_mcts_set_simulations: the budget of host-stepped searches (0 = the settings')
-    float sp_forced_k = 0.0f;     // azr_selfplay_set_forced_playouts, as set ...
-    bool sp_prune = false;
-    bool sp_forced = false;       // ... and as azr_selfplay_start* found it: this self-play's steps run k_tree_step<true, true, CAP, true>
+    azr::HostOpts host;           // the host-stepped options as they stand
+    azr::SelfplayOpts sp_set;     // the self-play options as set ...
+    azr::StepOpts sp;             // ... and what azr_selfplay_start* found in force: this self-play's steps carry it (the values are in d)
     bool sp_tail = false;         // quota self-play: no game is left to start, slots go idle -> compacted net batches
     void* train = nullptr;        // azr_train.hip: optimiser state + activation slabs, created by the first azr_nn_train*
     void* dp_comm = nullptr;      // azr_dp_init: this handle's RCCL communicator (ncclComm_t), rank and world

@@ -348,33 +348,17 @@ __device__ __forceinline__ void selfplay_next_game(const Dev& E, int g, const Tr
     tree_clear(t, c);
 }
 
-// the noise vector of game g's NEW root (device self-play with azr_selfplay_set_dirichlet): drawn for (seed, decision) of the running
-// game over the root's legal moves, stored for azr_mcts_root_noise and handed to the descents; zeros for a slot that went idle
-__device__ __forceinline__ float new_root_noise(const Dev& E, int g, const Ctl& c, const WS& root)
+// the vector of game g's NEW root in a self-play whose steps carry NOISE: stored for azr_mcts_root_noise and handed to the descents; zeros
+// for a slot that went idle.  A root that draws gets Dirichlet(E.noise_alpha) for (seed, decision) of the running game over its legal
+// moves; one that does not gets the constant vector (DIR_NOISE_VALUE in all 43 entries: the first selection then computes
+// eps * DIR_NOISE_VALUE, the constant form's c2, bit for bit).  Every root draws; under a playout cap (CAP) the full ones; with forced
+// playouts (FORCED, whose NOISE also serves a self-play without azr_selfplay_set_dirichlet) the full ones of a self-play that set an alpha.
+template <bool CAP, bool FORCED>
+__device__ __forceinline__ float new_root_noise(const Dev& E, int g, const Ctl& c, const WS& root, bool full)
 {
+    const bool draw = FORCED ? (full && E.noise_alpha > 0.0f) : CAP ? full : true;
     float eta = 0.0f;
-    if (c.mode != 0) eta = dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules));
-    if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
-    return eta;
-}
-
-// the same under a playout cap: a full root draws as above, a fast root gets the constant vector (DIR_NOISE_VALUE in all 43 entries:
-// the first selection then computes eps * DIR_NOISE_VALUE, the constant form's c2, bit for bit)
-__device__ __forceinline__ float new_root_noise_cap(const Dev& E, int g, const Ctl& c, const WS& root, bool full)
-{
-    float eta = 0.0f;
-    if (c.mode != 0) eta = full ? dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules)) : E.noise_value;
-    if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
-    return eta;
-}
-
-// the same with forced playouts in force (k_tree_step<.., NOISE = true, .., FORCED = true>, which also serves a self-play without
-// Dirichlet noise and the fast roots of a playout cap): a root that gets no draw gets the constant vector, as above
-__device__ __forceinline__ float new_root_noise_forced(const Dev& E, int g, const Ctl& c, const WS& root, bool full)
-{
-    float eta = 0.0f;
-    if (c.mode != 0)
-        eta = (full && E.noise_alpha > 0.0f) ? dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules)) : E.noise_value;
+    if (c.mode != 0) eta = draw ? dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules)) : E.noise_value;
     if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
     return eta;
 }

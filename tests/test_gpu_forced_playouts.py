@@ -2,7 +2,8 @@
 azr_selfplay_set_forced_playouts).  The contract is include/azr.h's; tests/forced_playouts_ref.py restates it in np.float32.  Checked
 here: the root rule pass by pass, bit for bit; off is the engine that never called the setter; depth 0 only; the pruned counts and
 policy against the restatement over three decisions with tree reuse; device self-play against the same games retraced decision by
-decision through the host-stepped entry points (with and without a playout cap), and against itself with pruning off; argument checks.
+decision through the host-stepped entry points (with and without a playout cap, with and without Dirichlet noise), and against itself
+with pruning off; argument checks.
 Engines of 8 games, one block, NET_F32."""
 import os
 
@@ -183,14 +184,16 @@ def _late_positions():
     return states, np.arange(600, 600 + G, dtype=np.uint32)
 
 
-def _selfplay(threads, cap, prune):
+def _selfplay(threads, cap, prune, alpha=ALPHA):
+    """alpha = 0: azr_selfplay_set_dirichlet is never called (forced playouts in force, no Dirichlet noise set)"""
     P = pkg()
     eng = P.Engine(G, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=threads)
     eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
     states, rngs = _late_positions()
     eng.set_states(states)
     eng.set_rng(rngs)
-    eng.selfplay_set_dirichlet(ALPHA, NSEED)
+    if alpha:
+        eng.selfplay_set_dirichlet(alpha, NSEED)
     eng.selfplay_set_forced_playouts(K, prune)
     if cap:
         eng.selfplay_set_playout_cap(0.5, FAST, CSEED)
@@ -198,6 +201,7 @@ def _selfplay(threads, cap, prune):
     recs = []
     for _ in range(400):
         eng.selfplay_run(64)
+        assert alpha or not eng.root_noise().any()                # no Dirichlet noise in force: azr_mcts_root_noise reads zeros
         recs.append(eng.drain())
         c = eng.counters()
         if c["games_finished"] + c["errors"] >= QUOTA:
@@ -208,9 +212,10 @@ def _selfplay(threads, cap, prune):
     return np.concatenate(recs), c
 
 
-def _retrace(threads, cap):
+def _retrace(threads, cap, alpha=ALPHA):
     """the same four games through azr_mcts_*: per decision the kind by the cap's coin, the vector of azr_debug_root_noise (or the
-    constant), the factor and the budget of that kind, one search, the pruned policy into the record, the unpruned pick as the move"""
+    constant: a fast decision, and every decision with alpha = 0), the factor and the budget of that kind, one search, the pruned
+    policy into the record, the unpruned pick as the move"""
     P = pkg()
     eng = P.Engine(G, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=threads)
     eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
@@ -225,7 +230,7 @@ def _retrace(threads, cap):
         while True:
             full = R.coin(0.5, CSEED, BASE + g, d) if cap else True
             valid = eng.valid_moves()
-            eta = eng.debug_root_noise(ALPHA, NSEED, [BASE + g], [d], valid[:1]) if full else np.full((1, 43), dnv, f32)
+            eta = eng.debug_root_noise(alpha, NSEED, [BASE + g], [d], valid[:1]) if full and alpha else np.full((1, 43), dnv, f32)
             eng.set_root_noise(np.repeat(eta, G, 0))
             eng.set_forced_playouts(K if full else 0.0)
             eng.set_simulations(SIMS if full else FAST)
@@ -254,10 +259,9 @@ def _retrace(threads, cap):
     return games, tot
 
 
-@pytest.mark.parametrize("threads,cap", [(1, False), (2, False), (2, True)])
-def test_selfplay_is_the_host_stepped_composition(threads, cap):
-    recs, c = _selfplay(threads, cap, True)
-    games, tot = _retrace(threads, cap)
+def _check_composition(threads, cap, alpha):
+    recs, c = _selfplay(threads, cap, True, alpha)
+    games, tot = _retrace(threads, cap, alpha)
     print("decisions per game:", [len(g) for g in games], tot)
     blob = recs.tobytes()
     for g, want in enumerate(games):
@@ -265,12 +269,23 @@ def test_selfplay_is_the_host_stepped_composition(threads, cap):
     assert len(recs) == sum(len(g) for g in games)
     assert {k: c[k] for k in tot} == tot
     # pruning off: the same games, the same records outside pi
-    plain, c0 = _selfplay(threads, cap, False)
+    plain, c0 = _selfplay(threads, cap, False, alpha)
     assert c0 == c and plain.shape == recs.shape
     assert (plain[:, :93] == recs[:, :93]).all()
     differ = (plain[:, 93:] != recs[:, 93:]).any(1)
     print("records whose pi pruning changed: %d of %d" % (differ.sum(), len(recs)))
     assert differ.any()
+
+
+@pytest.mark.parametrize("threads,cap", [(1, False), (2, False), (2, True)])
+def test_selfplay_is_the_host_stepped_composition(threads, cap):
+    _check_composition(threads, cap, ALPHA)
+
+
+@pytest.mark.parametrize("threads,cap", [(2, False), (2, True)])
+def test_selfplay_without_dirichlet_is_the_host_stepped_composition(threads, cap):
+    """forced playouts in force, azr_selfplay_set_dirichlet never called: every root, full or fast, runs on the constant vector"""
+    _check_composition(threads, cap, 0.0)
 
 
 # ---- 6. argument errors ------------------------------------------------------------------------------------------------------------
