@@ -87,6 +87,7 @@ EXPORTS = [
     "azr_selfplay_set_playout_cap", "azr_selfplay_decision_kind", "azr_debug_playout_cap",
     "azr_mcts_set_forced_playouts", "azr_mcts_pruned_policy", "azr_selfplay_set_forced_playouts", "azr_mcts_set_simulations",
     "azr_selfplay_start_games_from_states",
+    "azr_selfplay_set_surprise_weighting", "azr_debug_surprise_weights",
 ]
 
 
@@ -165,6 +166,9 @@ def load_library(test_hooks=False):
         L.azr_selfplay_set_forced_playouts.argtypes = [C.c_void_p, C.c_float, C.c_int]
         L.azr_mcts_set_simulations.argtypes = [C.c_void_p, C.c_int]
         L.azr_selfplay_start_games_from_states.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+        L.azr_selfplay_set_surprise_weighting.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32]
+        L.azr_debug_surprise_weights.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[test_hooks] = L
         if not test_hooks:
             _lib = L
@@ -497,6 +501,28 @@ class Engine:
     def set_simulations(self, simulations):
         """host-stepped searches: the budget per search, within [threads, sims]; <= 0 = the settings' own"""
         self._chk(self.L.azr_mcts_set_simulations(self.h, int(simulations)))
+
+    # ---- policy surprise weighting of the records (this engine's own; off = every record of a finished game is written once)
+    def selfplay_set_surprise_weighting(self, share, max_weight=4.0, seed=0):
+        """device self-play: a finished game's n records share the weight n, `share` of it in proportion to KL(pi || prior), each weight
+        capped at max_weight; record r is written floor(w) or ceil(w) times by a coin of (seed, game seed, r); share <= 0 = off; read by
+        selfplay_start*"""
+        self._chk(self.L.azr_selfplay_set_surprise_weighting(self.h, float(share), float(max_weight), int(seed)))
+
+    def debug_surprise_weights(self, share, max_weight, seed, pi, prior, valid, game_len, game_seed):
+        """the rule alone, on the device: pi, prior [rows, 43] and valid [rows] hold the games' records one game after the other
+        (rows = sum(game_len)) -> (kl, w, copies), each [rows]"""
+        pi = np.ascontiguousarray(pi, np.float32)
+        prior = np.ascontiguousarray(prior, np.float32)
+        v = np.ascontiguousarray(valid, np.uint64)
+        n = np.ascontiguousarray(game_len, np.uint32)
+        s = np.ascontiguousarray(game_seed, np.uint32)
+        rows = int(n.sum())
+        assert pi.shape == prior.shape == (rows, MOVES) and v.shape == (rows,) and n.ndim == 1 and n.shape == s.shape
+        kl, w, c = np.zeros(rows, np.float32), np.zeros(rows, np.float32), np.zeros(rows, np.uint32)
+        self._chk(self.L.azr_debug_surprise_weights(self.h, float(share), float(max_weight), int(seed), _p(pi), _p(prior), _p(v), _p(n), _p(s),
+                                                    len(n), _p(kl), _p(w), _p(c)))
+        return kl, w, c
 
     # ---- self-play
     def selfplay_start(self, base_seed=20260001):

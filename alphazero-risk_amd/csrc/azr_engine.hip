@@ -186,10 +186,14 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // FORCED (with NOISE only; a search without a sampled vector runs on the constant one, which is the constant form bit for bit): forced
 // playouts at path depth 0 with the factor E.forced_k (azr_forced.hpp) — not in a fast decision; with E.prune the staged record's pi
 // comes from the pruned counts N', the move still from N.
-template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED>
+// SURPRISE (self-play only): policy surprise weighting of the records (azr_surprise.hpp) — KL(pi || P) of every staged record is kept
+// beside it, and a finished game's records are written floor(w) or ceil(w) times each by flush_samples_weighted.  The search, the moves
+// and the staged records are the ones without it.
+template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
-    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED), "CAP needs SELFPLAY, FORCED implies NOISE: tree_step_kernel lists the nine");
+    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED) && (SELFPLAY || !SURPRISE),
+                  "CAP and SURPRISE need SELFPLAY, FORCED implies NOISE: launch_tree_step lists the fifteen");
     __shared__ int8_t scratch[128];
     const int g = blockIdx.x;
     TP_BEGIN();
@@ -222,13 +226,15 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             root.rng = c.rng;
             uint32_t N; uint64_t valid;
             uint32_t mv = NONE;
-            if (root_node(t, root, N, valid) != NO_NODE) {
+            float P = 0.0f;   // SURPRISE: the root's stored prior row
+            if (root_node(t, root, N, valid, nullptr, SURPRISE ? &P : nullptr) != NO_NODE) {
                 float pi = root_policy(N, valid);
                 mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
                 if (FORCED && E.prune && (!CAP || full)) {   // the record's pi from N'; the move above is N's
                     const uint32_t rkd = ws_record_dword(root);
                     pi = root_policy(root_pruned_counts(E, S, t, tree_lookup(t, rkd, key_hash(rkd)), N, valid, eta, E.forced_k), valid);
                 }
+                if (SURPRISE && (!CAP || full)) stage_surprise(E, g, c, pi, P, valid);
                 if (!CAP || full) stage_sample(E, g, c, root, pi, k);
             }
             TP(16);
@@ -243,8 +249,11 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                 if (root.err) { k.err++; c.error = root.err; }
                 else {
                     wave_mem_sync();
-                    flush_samples(E, g, c.nsamples, st, k.ringdrop);
-                    k.samples += c.nsamples;
+                    if (SURPRISE) k.samples += flush_samples_weighted(E, g, c.nsamples, st, c.seed, k.ringdrop);
+                    else {
+                        flush_samples(E, g, c.nsamples, st, k.ringdrop);
+                        k.samples += c.nsamples;
+                    }
                     k.games++;
                 }
                 c.status = st;
@@ -448,6 +457,29 @@ __global__ __launch_bounds__(64) void k_debug_playout_cap(uint32_t threshold, ui
     if (i < n) out[i] = cap_full(threshold, cap_seed, game_seed[i], decision[i]) ? 1 : 0;
 }
 
+// azr_debug_surprise_weights: the rule alone, one wave per game, through the device functions of the step and its weighted flush.
+// Game i's records are rows first[i] .. first[i] + game_len[i] - 1 of pi / prior / valid; its surprises go through kl_out.
+__global__ __launch_bounds__(64) void k_debug_surprise(float share, float max_weight, uint32_t seed, const float* pi, const float* prior,
+                                                       const uint64_t* valid, const uint32_t* first, const uint32_t* game_len,
+                                                       const uint32_t* game_seed, float* kl_out, float* w_out, uint32_t* copies_out)
+{
+    const size_t i = blockIdx.x;
+    const size_t r0 = rfl(first[i]);
+    const uint32_t n = rfl(game_len[i]), gs = rfl(game_seed[i]);
+    const uint32_t l = lane_id(), ll = l < MOVES ? l : 0;
+    for (uint32_t r = 0; r < n; r++) {
+        const float kl = record_surprise(pi[(r0 + r) * MOVES + ll], prior[(r0 + r) * MOVES + ll], rfl64(valid[r0 + r]));
+        if (l == 0) kl_out[r0 + r] = kl;
+    }
+    wave_mem_sync();
+    const float S = game_surprise_sum(kl_out + r0, n);
+    for (uint32_t r = l; r < n; r += 64) {
+        const float w = record_weight(kl_out[r0 + r], S, n, share, max_weight);
+        w_out[r0 + r] = w;
+        copies_out[r0 + r] = record_copies(w, seed, gs, r);
+    }
+}
+
 // azr_debug_root_noise: the sampler alone, one wave per vector
 __global__ __launch_bounds__(64) void k_debug_root_noise(float alpha, uint32_t noise_seed, const uint32_t* game_seed, const uint32_t* decision,
                                                          const uint64_t* valid, float* out)
@@ -623,7 +655,7 @@ extern "C" int azr_engine_destroy(azr_engine* h)
     Dev& d = h->d;
     void* ptrs[] = {d.sp_started, d.state, d.ctl, d.nodes, d.touch, d.nhash, d.table, d.freel, d.path, d.leaf_in, d.leaf_key,
                     d.leaf_valid, d.leaf_hash, d.net_pi, d.net_v, d.stage, d.ring, d.ring_count, d.counters, d.active,
-                    d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final, d.root_eta};
+                    d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final, d.root_eta, d.stage_kl};
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : h->tree2) if (p) hipFree(p);
     if (d.leaf_list) hipFree(d.leaf_list);
@@ -834,20 +866,23 @@ extern "C" int azr_mcts_begin(azr_engine* h)
     return AZR_OK;
 }
 
-// The nine k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
-// self-play also under a CAP, which doubles its three.  CAP needs SELFPLAY and FORCED implies NOISE (k_tree_step asserts both).
+// The fifteen k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
+// self-play also under a CAP, which doubles its three, and each of those six with SURPRISE.  CAP and SURPRISE need SELFPLAY and FORCED
+// implies NOISE (k_tree_step asserts all three).
 // Callers say what is in force; forced playouts without root noise run the NOISE instantiation, on the constant vector.
 static int launch_tree_step(azr_engine* h, const Dev& d, bool selfplay, const StepOpts& o)
 {
     void (*step)(Dev) = nullptr;
-#define AZR_STEP(SP, N, C, F) case (SP) << 3 | (N) << 2 | (C) << 1 | (F): step = k_tree_step<SP, N, C, F>; break
-    switch (selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
-        AZR_STEP(0, 0, 0, 0); AZR_STEP(0, 1, 0, 0); AZR_STEP(0, 1, 0, 1);
-        AZR_STEP(1, 0, 0, 0); AZR_STEP(1, 1, 0, 0); AZR_STEP(1, 1, 0, 1);
-        AZR_STEP(1, 0, 1, 0); AZR_STEP(1, 1, 1, 0); AZR_STEP(1, 1, 1, 1);
+#define AZR_STEP(SP, N, C, F, W) case (W) << 4 | (SP) << 3 | (N) << 2 | (C) << 1 | (F): step = k_tree_step<SP, N, C, F, W>; break
+    switch (o.surprise << 4 | selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
+        AZR_STEP(0, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 0, 0); AZR_STEP(0, 1, 0, 1, 0);
+        AZR_STEP(1, 0, 0, 0, 0); AZR_STEP(1, 1, 0, 0, 0); AZR_STEP(1, 1, 0, 1, 0);
+        AZR_STEP(1, 0, 1, 0, 0); AZR_STEP(1, 1, 1, 0, 0); AZR_STEP(1, 1, 1, 1, 0);
+        AZR_STEP(1, 0, 0, 0, 1); AZR_STEP(1, 1, 0, 0, 1); AZR_STEP(1, 1, 0, 1, 1);
+        AZR_STEP(1, 0, 1, 0, 1); AZR_STEP(1, 1, 1, 0, 1); AZR_STEP(1, 1, 1, 1, 1);
     }
 #undef AZR_STEP
-    if (!step) { h->err = "launch_tree_step: a playout cap on a host-stepped search: there is no such k_tree_step"; return AZR_E_LOGIC; }
+    if (!step) { h->err = "launch_tree_step: a playout cap or surprise weighting on a host-stepped search: there is no such k_tree_step"; return AZR_E_LOGIC; }
     hipLaunchKernelGGL(step, dim3(d.G), dim3(64), 0, h->stream, d);
     HIPCHK(h, hipGetLastError());
     return AZR_OK;
@@ -859,7 +894,7 @@ static StepOpts options_in_force(const azr_engine* h, int mode)
 {
     if (mode == 2) return h->sp;
     if (mode == 3) return StepOpts{};
-    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f};
+    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f, false};
 }
 // ... and the device view a search-related launch sees with it.  eta_const: no root vector is there to read (a self-play whose steps
 // carry NOISE keeps one per root).  Outside a self-play: the handle's without a self-play's leftovers, with azr_mcts_set_forced_playouts /
@@ -984,7 +1019,7 @@ static void resolve_selfplay_options(azr_engine* h)
     const SelfplayOpts& o = h->sp_set;
     Dev& d = h->d;
     h->host = HostOpts{};
-    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f};
+    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f, o.psw_share > 0.0f};
     d.noise_alpha = o.alpha;
     d.noise_seed = o.noise_seed;
     d.cap_threshold = cap_threshold_of(o.cap_prob);
@@ -992,11 +1027,16 @@ static void resolve_selfplay_options(azr_engine* h)
     d.cap_fast = h->sp.cap ? o.cap_fast_sims - o.cap_fast_sims % d.T : d.search.simulations;
     d.forced_k = o.forced_k;
     d.prune = h->sp.forced && o.prune ? 1 : 0;
+    d.psw_share = o.psw_share;
+    d.psw_max = o.psw_max;
+    d.psw_seed = o.psw_seed;
     d.eta_const = 0;
 }
 
 static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long quota, int keep = 0)
 {
+    // the surprises' buffer, with the first self-play that weights its records: an engine that never does allocates none
+    if (h->sp_set.psw_share > 0.0f && !h->d.stage_kl) HIPCHK(h, dmalloc(&h->d.stage_kl, (size_t)h->d.G * h->d.SCAP));
     h->d.base_seed = base_seed;
     h->d.sp_quota = quota;
     h->d.sp_compact = 0;
@@ -1146,6 +1186,66 @@ extern "C" int azr_selfplay_start_games_from_states(azr_engine* h, uint32_t base
     ENTER(h);
     if (games == 0) return AZR_E_INVALID_ARGUMENT;
     return selfplay_start(h, base_seed, games, 1);
+}
+
+// ---- policy surprise weighting ----------------------------------------------------------------------------
+// share: a number <= 1 (<= 0 = off); when on, max_weight in [1, 64]
+static int surprise_check(azr_engine* h, const char* who, float share, float max_weight)
+{
+    if (share != share || max_weight != max_weight || share > 1.0f)
+        return bad_argument(h, std::string(who) + ": share must be a number <= 1 (<= 0 = off) and max_weight a number");
+    if (share > 0.0f && !(max_weight >= 1.0f && max_weight <= PSW_MAX_WEIGHT))
+        return bad_argument(h, std::string(who) + ": max_weight must lie in [1, 64]");
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_set_surprise_weighting(azr_engine* h, float share, float max_weight, uint32_t seed)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (int rc = surprise_check(h, "azr_selfplay_set_surprise_weighting", share, max_weight)) return rc;
+    const bool on = share > 0.0f;
+    h->sp_set.psw_share = on ? share : 0.0f;
+    h->sp_set.psw_max = on ? max_weight : 1.0f;
+    h->sp_set.psw_seed = seed;
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_surprise_weights(azr_engine* h, float share, float max_weight, uint32_t seed, const float* pi, const float* prior,
+                                          const uint64_t* valid, const uint32_t* game_len, const uint32_t* game_seed, int games,
+                                          float* kl_out, float* w_out, uint32_t* copies_out)
+{
+    ENTER(h);
+    if (int rc = surprise_check(h, "azr_debug_surprise_weights", share, max_weight)) return rc;
+    if (!(share > 0.0f)) return bad_argument(h, "azr_debug_surprise_weights: share must lie in (0, 1]");
+    if (games < 0 || (games > 0 && (!game_len || !game_seed))) return AZR_E_INVALID_ARGUMENT;
+    std::vector<uint32_t> first((size_t)games);
+    size_t rows = 0;
+    for (int i = 0; i < games; i++) {
+        first[i] = (uint32_t)rows;
+        rows += game_len[i];
+        if (rows > 0x7fffffffu) return bad_argument(h, "azr_debug_surprise_weights: more than 2^31 - 1 records");
+    }
+    if (rows > 0 && (!pi || !prior || !valid || !kl_out || !w_out || !copies_out)) return AZR_E_INVALID_ARGUMENT;
+    if (rows == 0) return AZR_OK;
+    DevBuf bp, bq, bv, bf, bl, bs, bk, bw, bc;
+    HIPCHK(h, bp.alloc(rows * MOVES * 4)); HIPCHK(h, bq.alloc(rows * MOVES * 4)); HIPCHK(h, bv.alloc(rows * 8));
+    HIPCHK(h, bf.alloc((size_t)games * 4)); HIPCHK(h, bl.alloc((size_t)games * 4)); HIPCHK(h, bs.alloc((size_t)games * 4));
+    HIPCHK(h, bk.alloc(rows * 4)); HIPCHK(h, bw.alloc(rows * 4)); HIPCHK(h, bc.alloc(rows * 4));
+    H2D(h, bp.p, pi, rows * MOVES * 4);
+    H2D(h, bq.p, prior, rows * MOVES * 4);
+    H2D(h, bv.p, valid, rows * 8);
+    H2D(h, bf.p, first.data(), (size_t)games * 4);
+    H2D(h, bl.p, game_len, (size_t)games * 4);
+    H2D(h, bs.p, game_seed, (size_t)games * 4);
+    hipLaunchKernelGGL(k_debug_surprise, dim3(games), dim3(64), 0, h->stream, share, max_weight, seed, (const float*)bp.p, (const float*)bq.p,
+                       (const uint64_t*)bv.p, (const uint32_t*)bf.p, (const uint32_t*)bl.p, (const uint32_t*)bs.p, (float*)bk.p, (float*)bw.p,
+                       (uint32_t*)bc.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, kl_out, bk.p, rows * 4);
+    D2H(h, w_out, bw.p, rows * 4);
+    D2H(h, copies_out, bc.p, rows * 4);
+    SYNC(h);
+    return AZR_OK;
 }
 
 // ---- playout cap ----------------------------------------------------------------------------------------

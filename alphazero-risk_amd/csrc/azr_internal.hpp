@@ -115,12 +115,18 @@ struct Dev {
     float forced_k;            // the factor k of nf = sqrt(k * noiseP * sumN) (0 = off)
     int prune;                 // device self-play: a record's pi comes from the pruned counts
     int eta_const;             // host-stepped: no root vector is set, the search runs on the constant one (noise_value)
+    // policy surprise weighting of the records (this engine's own; read by the k_tree_step instantiations with SURPRISE only;
+    // azr_surprise.hpp)
+    float* stage_kl;           // [G][SCAP]  KL(pi || P) of each staged record (allocated by the first azr_selfplay_start* that weights)
+    float psw_share;           // the share of a game's record weight handed out by surprise (0 = off)
+    float psw_max;             // the cap on one record's weight
+    uint32_t psw_seed;         // the copy coin is keyed by (psw_seed, game seed, record)
 };
 constexpr int ALOG = 16;
 
 // The options of the search variants (host side).  Which of them a tree step carries: root noise, a playout cap (self-play only),
-// forced playouts — the template arguments of k_tree_step after SELFPLAY.
-struct StepOpts { bool noise = false, cap = false, forced = false; };
+// forced playouts, policy surprise weighting of the records (self-play only) — the template arguments of k_tree_step after SELFPLAY.
+struct StepOpts { bool noise = false, cap = false, forced = false, surprise = false; };
 // Host-stepped searches (azr_mcts_*): in force from the setter's call until the next azr_selfplay_start*.
 struct HostOpts {
     bool noise = false;        // azr_mcts_set_root_noise: a vector per game is set in d.root_eta
@@ -128,7 +134,7 @@ struct HostOpts {
     int sims = 0;              // azr_mcts_set_simulations: the budget (0 = the settings')
 };
 // Device self-play, as the azr_selfplay_set_* setters leave them.  A running self-play never sees a change: azr_selfplay_start* resolves
-// them into a StepOpts and Dev's noise_*, cap_*, forced_k and prune.
+// them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune and psw_*.
 struct SelfplayOpts {
     float alpha = 0.0f;        // azr_selfplay_set_dirichlet (0 = off)
     uint32_t noise_seed = 0;
@@ -137,6 +143,9 @@ struct SelfplayOpts {
     uint32_t cap_seed = 0;
     float forced_k = 0.0f;     // azr_selfplay_set_forced_playouts (0 = off)
     bool prune = false;
+    float psw_share = 0.0f;    // azr_selfplay_set_surprise_weighting (0 = off)
+    float psw_max = 1.0f;
+    uint32_t psw_seed = 0;
 };
 
 // folded network parameters on device

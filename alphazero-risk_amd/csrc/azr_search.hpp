@@ -4,6 +4,7 @@
 #include "azr_internal.hpp"
 #include "azr_cap.hpp"
 #include "azr_noise.hpp"
+#include "azr_surprise.hpp"
 
 namespace azr {
 
@@ -160,6 +161,15 @@ __device__ __forceinline__ void stage_sample(const Dev& E, int g, Ctl& c, const 
         if (l == 0) rec[260] = (uint8_t)root.cur;
         c.nsamples++;
     } else k.ringdrop++;
+}
+
+// Policy surprise weighting: the surprise of the record stage_sample stages next, into the float beside its staging slot (nothing for
+// a record past the buffer's end, which stage_sample counts and drops).  pi: what goes into the record; P: the root's stored prior row.
+__device__ __forceinline__ void stage_surprise(const Dev& E, int g, const Ctl& c, float pi, float P, uint64_t valid)
+{
+    if (c.nsamples >= (uint32_t)E.SCAP) return;
+    const float kl = record_surprise(pi, P, valid);
+    if (lane_id() == 0) E.stage_kl[(size_t)g * E.SCAP + c.nsamples] = kl;
 }
 
 // Lists this slot's waiting leaves (leaf slot g * T + thread, in thread order) behind those of the slots that came first: one atomic per

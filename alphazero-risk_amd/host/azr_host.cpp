@@ -105,6 +105,9 @@ void Settings::init(int argc, char* argv[])
         {"cap-seed", "[this build] seed of the playout cap's coin (independent of --seed and --dir-seed: dice, deals and noise do not move)", std::to_string(CAP_SEED), false},
         {"forced-k", "[this build] self-play forced playouts: a tried root move of a full decision is searched until it has sqrt(k * prior * visits) visits (0 = off; at most 8; KataGo runs 2)", "0", false},
         {"prune-target", "[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits PUCT would not have spent (0 = off)", "0", false},
+        {"psw-share", "[this build] self-play policy surprise weighting: share of a finished game's record weight handed out in proportion to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off: every record once; at most 1; KataGo runs 0.5)", "0", false},
+        {"psw-max", "[this build] cap on one record's weight under --psw-share (within [1, 64])", "4", false},
+        {"psw-seed", "[this build] seed of the coin that rounds a record's weight to its copy count (independent of --seed, --dir-seed and --cap-seed)", std::to_string(PSW_SEED), false},
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -274,6 +277,30 @@ void Settings::init(int argc, char* argv[])
             exit(2);
         }
         PRUNE_TARGET = (int)pt;
+    }
+    {
+        char* end = nullptr;
+        const std::string sv = get("psw-share");
+        const double sh = strtod(sv.c_str(), &end);
+        if (sv.empty() || *end != '\0' || !(sh >= 0.0) || sh > 1.0) {
+            fprintf(stderr, "--psw-share: '%s' is not a share (a number in [0, 1]; 0 = off)\n", sv.c_str());
+            exit(2);
+        }
+        PSW_SHARE = (float)sh;
+        const std::string mv = get("psw-max");
+        const double mx = strtod(mv.c_str(), &end);
+        if (mv.empty() || *end != '\0' || !(mx >= 1.0) || mx > 64.0) {
+            fprintf(stderr, "--psw-max: '%s' is not a weight cap (a number in [1, 64])\n", mv.c_str());
+            exit(2);
+        }
+        PSW_MAX = (float)mx;
+        const std::string dv = get("psw-seed");
+        const unsigned long long sd = dv.empty() || dv[0] == '-' ? 0 : strtoull(dv.c_str(), &end, 10);
+        if (dv.empty() || dv[0] == '-' || *end != '\0' || sd > 0xffffffffull) {
+            fprintf(stderr, "--psw-seed: '%s' is not a 32-bit seed\n", dv.c_str());
+            exit(2);
+        }
+        PSW_SEED = (uint32_t)sd;
     }
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
@@ -748,6 +775,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         e.check(azr_selfplay_set_playout_cap(e.h, SETTINGS.CAP_PROB, SETTINGS.CAP_FAST, SETTINGS.CAP_SEED), "selfplay_set_playout_cap");
         // forced playouts / policy target pruning of the generated games: --forced-k 0 / --prune-target 0 (default) are the search and the records above
         e.check(azr_selfplay_set_forced_playouts(e.h, SETTINGS.FORCED_K, SETTINGS.PRUNE_TARGET), "selfplay_set_forced_playouts");
+        // policy surprise weighting of the generated games' records: --psw-share 0 (default) writes every record once
+        e.check(azr_selfplay_set_surprise_weighting(e.h, SETTINGS.PSW_SHARE, SETTINGS.PSW_MAX, SETTINGS.PSW_SEED), "selfplay_set_surprise_weighting");
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);

@@ -206,6 +206,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
             gen.selfplay_set_dirichlet(getattr(a, "dir_alpha", 0.0), getattr(a, "dir_seed", 0))   # root noise of the generated games only (0 = the reference's constant)
             gen.selfplay_set_playout_cap(getattr(a, "cap_prob", 1.0), getattr(a, "cap_fast", 0), getattr(a, "cap_seed", 0))   # playout cap of the generated games only (1 / 0 = off)
             gen.selfplay_set_forced_playouts(getattr(a, "forced_k", 0.0), getattr(a, "prune_target", 0))   # forced playouts / target pruning of the generated games only (0 / 0 = off)
+            gen.selfplay_set_surprise_weighting(getattr(a, "psw_share", 0.0), getattr(a, "psw_max", 4.0), getattr(a, "psw_seed", 0))   # surprise weighting of the generated games' records only (0 = every record once)
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -350,6 +351,11 @@ def main():
     ap.add_argument("--prune-target", type=int, default=0,
                     help="[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits "
                          "PUCT would not have spent (0 = off)")
+    ap.add_argument("--psw-share", type=float, default=0.0,
+                    help="[this build] self-play policy surprise weighting: share of a finished game's record weight handed out in proportion "
+                         "to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off; at most 1)")
+    ap.add_argument("--psw-max", type=float, default=4.0, help="[this build] cap on one record's weight under --psw-share (within [1, 64])")
+    ap.add_argument("--psw-seed", type=int, default=0, help="[this build] seed of the coin that rounds a record's weight to its copy count")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -371,6 +377,12 @@ def main():
         ap.error(f"--forced-k: {a.forced_k} is not a forced-playout factor (a number in [0, 8]; 0 = off)")
     if a.prune_target not in (0, 1) or (a.prune_target == 1 and not a.forced_k > 0.0):
         ap.error(f"--prune-target: {a.prune_target} is neither 0 nor 1, or is 1 without --forced-k above 0")
+    if not 0.0 <= a.psw_share <= 1.0:   # (a NaN fails both comparisons)
+        ap.error(f"--psw-share: {a.psw_share} is not a share (a number in [0, 1]; 0 = off)")
+    if not 1.0 <= a.psw_max <= 64.0:
+        ap.error(f"--psw-max: {a.psw_max} is not a weight cap (a number in [1, 64])")
+    if not 0 <= a.psw_seed <= 0xFFFFFFFF:
+        ap.error(f"--psw-seed: {a.psw_seed} is not a 32-bit seed")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():
         learn(a)

@@ -297,6 +297,60 @@ int azr_selfplay_set_forced_playouts(azr_engine* h, float k, int prune);
  * (default).  Holds until set again; azr_selfplay_start* ends it.  The arena and device self-play never see it. */
 int azr_mcts_set_simulations(azr_engine* h, int simulations);
 
+/* ---- policy surprise weighting of the self-play records (this engine's own; off after azr_engine_create) -------------
+ * The reference writes every recorded decision of a finished game once.  With surprise weighting (KataGo, KataGoMethods.md) a game's
+ * total record weight stays its record count n, but a share of it is handed out in proportion to KL(pi || P) — the recorded search
+ * policy against the net's prior at that root — and realised by writing record r floor(w_r) or ceil(w_r) times.  The 265-byte record,
+ * the search, the moves, dice, games, pi and z are those of the same run without the feature.
+ * All arithmetic below is fp32, each operation rounded on its own (no fused multiply-add), in the order written.
+ *
+ * ln32(x), the engine's own logarithm:
+ *     if (x < 1.17549435e-38f) x = 1.17549435e-38f;                         (zero and subnormals included)
+ *     b = the bits of x;   e = (int)(b >> 23) - 127;   m = the float with bits (b & 0x7FFFFF) | 0x3F800000
+ *     if (m > 1.41421354f) { m = m * 0.5f;  e += 1; }
+ *     t = (m - 1) / (m + 1);   t2 = t * t
+ *     p = 0.111111112f;   then p = p * t2 + c for c = 0.142857149f, 0.2f, 0.333333343f, 1.0f in turn (a multiply, then an add)
+ *     ln32 = (float)e * 0.693147182f + (2.0f * t) * p
+ * Against the double logarithm on (1e-38, 2]: relative error below 5e-7 where |ln x| > 1e-3, absolute error below 1.6e-5;
+ * ln32(1) = 0 exactly.
+ *
+ * Surprise of a record, computed when it is staged.  pi = the policy that goes into the record (the pruned one under policy target
+ * pruning); P = the root node's stored prior row, before any noise (what azr_mcts_root_stats reports); valid = the root's legal moves.
+ *     term[m] = pi[m] * (ln32(pi[m]) - ln32(P[m]))   for a legal m with pi[m] > 0,  else 0
+ *     KL = term[0] + term[1] + ... + term[42] summed one after the other from 0.0f in index order;   KL = max(KL, 0)
+ *
+ * Weights of a finished game with n staged records KL_0 .. KL_{n-1} in staging order:
+ *     S = KL_0 + ... + KL_{n-1} summed one after the other from 0.0f
+ *     !(S > 0):   w_r = 1 for every r
+ *     else        w_r = (1.0f - share) + (share * (float)n) * (KL_r / S);   w_r = min(w_r, max_weight)
+ *
+ * Copies.  r = the record's ordinal among the game's staged records: 0 for the first record staged since the game — or an entry
+ * through azr_selfplay_start*_from_states — began; under a playout cap only full decisions are staged, so r counts those.
+ * s = the game's seed; mix as in the playout cap's coin:
+ *     base = (uint32)w_r (truncated);   fr = w_r - (float)base;   thr = (uint32)(fr * 16777216.0f)
+ *     k = mix(seed + 0x165667B1);   k = mix(k ^ s);   k = mix((k ^ r) + 0xD3A2646C)
+ *     c_r = base + ((k >> 8) < thr)
+ * The two constants are neither the Dirichlet sampler's (0x9E3779B9, 0x85EBCA6B) nor the playout cap's (0xC2B2AE35, 0x27D4EB2F), so
+ * equal seeds do not tie the copies to the noise or to the kind of a decision.  The copy count is a function of (seed, s, r, the
+ * game's pi and P) alone: not of the slot, the number of games or threads, the pass schedule or the other seeds; nothing is drawn
+ * from the game's own RNG stream.  An exact integer w_r has thr = 0 and never gets an extra copy.
+ *
+ * Flush.  A finished game reserves C = sum of c_r ring records in one reservation and writes record r c_r times, copies adjacent, in
+ * staging order; a record with c_r = 0 is not written.  Records past the ring's end are dropped and counted in records_dropped as
+ * without the feature.  Counters: samples counts C; every other counter is that of the same run without the feature.
+ * The arena (azr_arena_*), the host-stepped searches (azr_mcts_*) and scripted collection never see it.
+ *
+ * share <= 0 = off (default).  Read by azr_selfplay_start*; a running self-play never sees a change.  max_weight is the caller's
+ * choice (it is not read while off).  AZR_E_INVALID_ARGUMENT, with a reason in azr_last_error, for a NaN, for share > 1, or — when
+ * on — a max_weight outside [1, 64]. */
+int azr_selfplay_set_surprise_weighting(azr_engine* h, float share, float max_weight, uint32_t seed);
+/* the rule alone, on the device, one wavefront per game through the device functions of the self-play step: pi, prior [rows][43] and
+ * valid [rows] hold the games' records one game after the other, rows = the sum of game_len[i], i < games; game_seed[i] = the game's
+ * seed s.  kl_out, w_out, copies_out [rows].  share in (0, 1], max_weight in [1, 64]. */
+int azr_debug_surprise_weights(azr_engine* h, float share, float max_weight, uint32_t seed, const float* pi, const float* prior,
+                               const uint64_t* valid, const uint32_t* game_len, const uint32_t* game_seed, int games,
+                               float* kl_out, float* w_out, uint32_t* copies_out);
+
 /* ---- device-resident self-play (trainer move loop, alphazero_trainer.cpp:80-119) --------------------------- */
 /* (Re)start all G games: game g plays seeds base_seed + g, then base_seed + G + g, ... */
 int azr_selfplay_start(azr_engine* h, uint32_t base_seed);
