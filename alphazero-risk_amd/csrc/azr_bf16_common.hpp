@@ -1,16 +1,25 @@
-// azr_bf16_common.hpp — constants, packed-weight layout and device helpers shared by the LDS-resident tower kernels (azr_net_bf16.hip:
-// one board per workgroup, two LDS images; azr_tower_sb.hip: 2..4 boards, one image; azr_tower_sc.hip: split channels; azr_tower_fx.hip:
-// NET_F32X), among them the fused heads all four end with.
+// azr_bf16_common.hpp — what ALL four LDS-resident tower kernels share (azr_net_bf16.hip: one board per workgroup, two LDS images;
+// azr_tower_sb.hip: 2..4 boards, one image; azr_tower_sc.hip: split channels; azr_tower_fx.hip: NET_F32X): the vector register types,
+// constants, the packed-weight layout, the 16-bit element type and the fused heads all four end with.  What only the multi-board towers
+// share — LDS table region, launch prologue, 16-bit epilogue — is in azr_tower_common.hpp.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
 #include "azr_internal.hpp"
 
+// the vector register types of every MFMA kernel of the library (the towers and the training convs): one name per type
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef __attribute__((ext_vector_type(2))) short s16x2;
+typedef __attribute__((ext_vector_type(8))) float f32x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 namespace azr {
 constexpr int ROWB = 544;                 // LDS bytes per activation row: 256 bf16 + 32 B pad: 16-B slot = (2*row + kgroup) mod 16 -> ds_read_b128 lane groups conflict-free
@@ -42,7 +51,7 @@ __device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint
 // into the folded BN scale, as for NET_F32X) and activations saturate at 65504 instead of overflowing.
 template <bool F16> struct El;
 template <> struct El<false> {
-    typedef __attribute__((ext_vector_type(2))) __bf16 v2;
+    typedef bf16x2 v2;
     template <typename TB, typename TA>   // any 16-byte register types (a ring slot is a u32x4, an LDS fragment an s16x8)
     static __device__ __forceinline__ f32x4 mfma(const TB& b, const TA& a, const f32x4& c)
     {
@@ -55,17 +64,16 @@ template <> struct El<false> {
     static __device__ __forceinline__ float hi_of(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
     template <typename V2f> static __device__ __forceinline__ uint32_t pack_relu(const V2f& x)   // RNE, then ReLU on the rounded pair
     {
-        typedef __attribute__((ext_vector_type(2))) short s16x2_t;
-        const s16x2_t z = {0, 0};
-        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, __builtin_convertvector(x, v2)), z));
+        const s16x2 z = {0, 0};
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, __builtin_convertvector(x, v2)), z));
     }
 };
 template <> struct El<true> {
-    typedef __attribute__((ext_vector_type(2))) _Float16 v2;
+    typedef f16x2 v2;
     template <typename TB, typename TA>
     static __device__ __forceinline__ f32x4 mfma(const TB& b, const TA& a, const f32x4& c)
     {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, b), __builtin_bit_cast(f16x8_t, a), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b), __builtin_bit_cast(f16x8, a), c, 0, 0, 0);
     }
     static __device__ __forceinline__ uint16_t rne(float f) { return __builtin_bit_cast(uint16_t, (_Float16)fminf(f, 65504.0f)); }   // (stem features: once per launch)
     static __device__ __forceinline__ float tof(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
@@ -75,9 +83,8 @@ template <> struct El<true> {
     {
         // as signed 16-bit integers the non-negative fp16 bit patterns are ordered like their values, +inf = 0x7c00 just above the
         // largest finite 0x7bff: max with 0 is the ReLU (-0 -> +0), min with 0x7bff the saturation (v_pk_max_i16, v_pk_min_i16)
-        typedef __attribute__((ext_vector_type(2))) short s16x2_t;
-        const s16x2_t z = {0, 0}, m = {0x7bff, 0x7bff};
-        return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(__builtin_bit_cast(s16x2_t, __builtin_convertvector(x, v2)), z), m));
+        const s16x2 z = {0, 0}, m = {0x7bff, 0x7bff};
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_max(__builtin_bit_cast(s16x2, __builtin_convertvector(x, v2)), z), m));
     }
 };
 
@@ -100,8 +107,6 @@ __device__ __forceinline__ float plane_value(const uint8_t* in88, int pos, int c
     }
 }
 
-
-typedef __attribute__((ext_vector_type(8))) float f32x8;
 
 // Both heads (build_graph.py:76-90), fused onto the end of a tower kernel whose output stays in LDS: one arithmetic, the fma chains of
 // k_heads (azr_net.hip) in the same order, shared by every LDS-resident tower.  NB boards from board0 (of n), THREADS threads; `hp` = the
@@ -193,6 +198,8 @@ struct ImageAct {
 constexpr size_t KSTRIDE = FRAGS_PER_KSTEP * 64;   // s16x8 units between consecutive k-steps
 constexpr size_t KBYTES = KSTRIDE * 16;            // bytes per k-step of packed weights (all 16 column tiles)
 constexpr int MAX_RING = 16;                       // deepest weight ring any kernel runs ahead (k-steps): run-off padding
+// bytes of the packed 16-bit weight stream of a tower of `blocks` blocks: 2 layers per block + the ring's run-off
+constexpr size_t tower_stream_bytes(int blocks) { return ((size_t)2 * blocks * TOWER_LAYER_HALFS + MAX_RING * KSTRIDE * 8) * 2; }
 
 struct Bf16Net {
     bool f16 = false;                 // AZR_NET_F16: the packed weights and the activations are fp16 (El<true>), `fold16` carries the weight scales

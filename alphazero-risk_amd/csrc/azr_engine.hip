@@ -11,16 +11,6 @@
 
 using namespace azr;
 
-#define HIPCHK(h, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError(); /* the runtime's last-error slot is sticky: clear it */        \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return AZR_E_HIP;                                                                   \
-        }                                                                                       \
-    } while (0)
-
 // ================================================================================================
 // rules kernels (UtilityNN / State seams)
 // ================================================================================================

@@ -10,6 +10,17 @@
 #include "../../include/azr.h"
 #include "azr_tree.hpp"
 
+// a failed HIP call ends the C-ABI function that made it: its text goes into the handle's error string, AZR_E_HIP comes back
+#define HIPCHK(h, call)                                                                         \
+    do {                                                                                        \
+        hipError_t e__ = (call);                                                                \
+        if (e__ != hipSuccess) {                                                                \
+            (void)hipGetLastError(); /* the runtime's last-error slot is sticky: clear it */    \
+            (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
+            return AZR_E_HIP;                                                                   \
+        }                                                                                       \
+    } while (0)
+
 // Test hooks.  Environment switches that select an older or alternative formulation of the same arithmetic (the parity tests compare it
 // with the default one as an independently written implementation), force a hand-off to give up, or stand in for a communicator exist
 // ONLY in libazr_hip_test.so — the same sources compiled with -DAZR_TEST_HOOKS by `make test` (csrc/Makefile), loaded by the tests that

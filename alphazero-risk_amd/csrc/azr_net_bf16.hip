@@ -4,7 +4,8 @@
 //
 // Launches of 129..256 boards run this kernel, and it is the guarded recompute queued behind every k_tower_sc launch
 // (azr_tower_sc.hip).  Written independently of the multi-board tiles (k_tower_sb, k_tower_sc), it is the reference they are compared
-// with bit for bit (AZR_TOWER_SB=0 / AZR_TOWER_SC=0).
+// with bit for bit (AZR_TOWER_SB=0 / AZR_TOWER_SC=0): its tables, stem and epilogue are its own, and of what the towers share it takes the
+// element type, the packed layout and the fused heads (azr_bf16_common.hpp) only, nothing of azr_tower_common.hpp.
 //   * A workgroup (8 waves, 512 threads, two per CU) owns one board for the ENTIRE stem + 2B conv layers: 42 cells -> M = 48 GEMM
 //     rows (row = cell, rows 42..47 are zero pad rows).  The activations never leave LDS: two ping-pong images [48 rows + 1 zero
 //     row][256 + 16 pad] bf16.  HBM sees the 88-byte input, the weights, and 45 floats out.
@@ -29,17 +30,6 @@
 #include "azr_bf16_common.hpp"
 
 using namespace azr;
-
-#define HIPCHK(h, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError(); /* the runtime's last-error slot is sticky: clear it */        \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return AZR_E_HIP;                                                                   \
-        }                                                                                       \
-    } while (0)
-
 
 namespace {
 constexpr int THREADS = 512, NT = 2, WCOLS = NT * 16;   // 8 waves x 2 column tiles of 16 channels
@@ -321,8 +311,8 @@ int net_bf16_alloc(azr_engine* h)
     x->f16 = h->cfg.net_dtype == AZR_NET_F16;
     if (x->f16) HIPCHK(h, hipMalloc((void**)&x->fold16, (14 + (size_t)2 * B * 2 * NF) * sizeof(float)));
     HIPCHK(h, hipMalloc((void**)&x->stem_wp, STEM_HALFS * 2));
-    HIPCHK(h, hipMalloc((void**)&x->tower_wp, ((size_t)2 * B * TOWER_LAYER_HALFS + MAX_RING * KSTRIDE * 8) * 2));  // + ring run-off
-    HIPCHK(h, hipMemsetAsync(x->tower_wp, 0, ((size_t)2 * B * TOWER_LAYER_HALFS + MAX_RING * KSTRIDE * 8) * 2, h->stream));
+    HIPCHK(h, hipMalloc((void**)&x->tower_wp, tower_stream_bytes(B)));  // + ring run-off
+    HIPCHK(h, hipMemsetAsync(x->tower_wp, 0, tower_stream_bytes(B), h->stream));
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_tower_bf16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_tower_bf16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     // test hooks (libazr_hip_test.so only, azr_internal.hpp; read ONCE, here, never in the launch path): AZR_TOWER_SB = 0: k_tower_bf16<1>

@@ -1,10 +1,11 @@
-// azr_rowclass.hpp — border-class row order of the board cells of a workgroup tile (shared by the inference tower,
-// azr_tower_sb.hip, and the training conv kernels, azr_train.hip).
+// azr_rowclass.hpp — border-class row order of the board cells of a workgroup tile and the row tables built from it (shared by
+// the multi-board inference towers, azr_tower_sb / _sc / _fx.hip, and the training conv kernel t_conv_rs, azr_train_conv.hpp).
 //
 // A 3x3 SAME conv on the 6x7 board is an implicit GEMM whose M rows are board cells; a tap (dy, dx) has no in-board source
 // for the cells of one board edge.  If the rows of a workgroup's tile are ordered so that whole 16-row MFMA tiles lie on one
 // edge, the (tile, tap) pairs without any source are skipped altogether — exact zeros left out, results unchanged.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace azr {
@@ -61,6 +62,46 @@ __host__ __device__ constexpr int pad_from(int mt)
     if (NB == 4) return (mt == 2 || mt == 3) ? 12 : 16;
     if (NB == 3) return mt == 7 ? 14 : 16;
     return mt < 2 ? 14 : mt == 2 ? 8 : 16;
+}
+
+// ---- the row tables a kernel builds in LDS once per launch: rowof[board * 42 + pos] = row_of, rowcell[row] = cell_code of the
+// row's cell (PAD_CELL for a pad row), taprow[tap][row] = the row a 3x3 tap reads for that row (the zero row ZR where there is none).
+// The two rules, per element (host side: tests/helpers/rowclass_probe.hip):
+constexpr int PAD_CELL = 0xffff;
+__host__ __device__ __forceinline__ constexpr int cell_code(int b, int pos) { return (pos / 6) | ((pos % 6) << 4) | (b << 8); }   // y | x << 4 | board << 8
+// the row a row with cell code `ci` reads under tap t: the row of the neighbouring cell of the same board, or the zero row `zr` for a
+// pad row, a tap that leaves the board and tap 9 ("no tap", the second half of the stem's last k-step; TAPS = 9: t is a tap)
+template <int TAPS, class Row>
+__host__ __device__ __forceinline__ constexpr int tap_source_row(int t, int ci, int zr, const Row* rowof)
+{
+    int src = zr;
+    if ((TAPS <= 9 || t < 9) && ci != PAD_CELL) {
+        const int y = (ci & 15) + t / 3 - 1, x = ((ci >> 4) & 15) + t % 3 - 1;
+        if ((unsigned)y < 7u && (unsigned)x < 6u) src = rowof[(ci >> 8) * 42 + y * 6 + x];
+    }
+    return src;
+}
+
+// The builder (k_tower_sb, k_tower_sc; k_tower_fx and t_conv_rs apply the two rules in loops of their own, profiles/tower_common_isa.txt):
+// TAPS = 10 for a tower (tap 9 = all zero row), 9 for a plain 3x3 conv.  Two barriers: the pad marks are visible | the cell codes and
+// rowof are visible; taprow is visible behind the CALLER's next barrier.
+template <int NB, int THREADS, int TAPS>
+__device__ __forceinline__ void build_row_tables(uint8_t* rowof, uint8_t* taprow, uint16_t* rowcell)
+{
+    const int tid = threadIdx.x;
+    constexpr int ROWS = 42 * NB, ZR = (ROWS + 15) / 16 * 16;
+    for (int i = tid; i < ZR; i += THREADS) rowcell[i] = 0xffffu;
+    __syncthreads();
+    for (int i = tid; i < ROWS; i += THREADS) {
+        const int b = i / 42, pos = i - b * 42, r = row_of<NB>(b, pos);
+        rowof[i] = (uint8_t)r;
+        rowcell[r] = (uint16_t)cell_code(b, pos);
+    }
+    __syncthreads();
+    for (int i = tid; i < TAPS * ZR; i += THREADS) {
+        const int t = i / ZR, r = i - t * ZR;
+        taprow[i] = (uint8_t)tap_source_row<TAPS>(t, rowcell[r], ZR, rowof);
+    }
 }
 
 }  // namespace azr

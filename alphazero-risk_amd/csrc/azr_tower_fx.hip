@@ -22,7 +22,7 @@
 // The stem (K = 9 x 13) runs on the fp32-input MFMA v_mfma_f32_16x16x4_f32 from fp32 planes and fp32 weights: exact fp32.
 // The heads read the reconstructed fp32 activations (hi + lo is exact in fp32) and run the fp32 fma chains of k_heads.
 //
-// Structure = k_tower_sb (azr_tower_sb.hip): one workgroup of 4 waves (one per SIMD) owns NB boards for the whole net, the
+// Structure = k_tower_sb's (azr_tower_sb.hip; the launch prologue and the LDS table region are the shared ones of azr_tower_common.hpp): one workgroup of 4 waves (one per SIMD) owns NB boards for the whole net, the
 // activations never leave LDS (two planes: hi image, lo' image), waves split the 256 output channels (4 tiles of 16 each), weight
 // fragments stream global -> registers through a ring that never drains, border-class row order with skipped (tile, tap)
 // pairs, a layer's 72 k-steps fully unrolled.  Packed weights: per layer and k-step [16 column tiles of wh | 16 of wl], one
@@ -33,28 +33,12 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <string>
 #include <vector>
 
 #include "azr_internal.hpp"
-#include "azr_bf16_common.hpp"
-#include "azr_rowclass.hpp"
+#include "azr_tower_common.hpp"
 
 using namespace azr;
-
-#define HIPCHK(h, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError(); /* the runtime's last-error slot is sticky: clear it */    \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return AZR_E_HIP;                                                                   \
-        }                                                                                       \
-    } while (0)
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 
 #ifndef FX_DROP
 #define FX_DROP 0     /* diagnostics: 1 / 2 = leave out the wh x al' / wl' x ah cross term */
@@ -77,16 +61,13 @@ struct FX {
     static constexpr int PLANE = (ZR + 1) * ROWB;            // one activation image (hi, or lo') incl. its zero row
     static constexpr int FEAT_OFF = 2 * PLANE;               // stem features, fp32 [(ZR + 1)][16]
     static constexpr int HEAD_OFF = FEAT_OFF + (ZR + 1) * 64;
-    static constexpr int IN88_OFF = HEAD_OFF + NB * 448 * 4;
-    static constexpr int ROWOF_OFF = IN88_OFF + NB * 96;     // u8 [ZR]: cell (board * 42 + pos) -> row
-    static constexpr int TAPROW_OFF = ROWOF_OFF + ZR;        // u8 [10][ZR]: source row of (tap, row); tap 9 = all zero row
-    static constexpr int ROWCELL_OFF = TAPROW_OFF + 10 * ZR; // u16 [ZR]: row -> y | x << 4 | board << 8, 0xffff = pad row
-    static constexpr int FOLD_OFF = (ROWCELL_OFF + 2 * ZR + 15) / 16 * 16;   // float [2][256]: the layer's folded BN scale | shift
+    using TAB = TowerTables<NB, ZR, HEAD_OFF + NB * 448 * 4>;   // NNInputData images and row tables
+    static constexpr int FOLD_OFF = TAB::END;                // float [2][256]: the layer's folded BN scale | shift
     static constexpr int LDS_BYTES = FOLD_OFF + 2 * NF * 4;
     static_assert(NB == 2, "tile shapes (the row order of azr_rowclass.hpp)");
     static_assert(STEPS % RING == 0, "ring depth");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-    static_assert(PLANE % 16 == 0 && FEAT_OFF % 16 == 0 && HEAD_OFF % 16 == 0 && TAPROW_OFF % 4 == 0 && ROWCELL_OFF % 2 == 0, "alignment");
+    static_assert(PLANE % 16 == 0 && FEAT_OFF % 16 == 0 && HEAD_OFF % 16 == 0 && FOLD_OFF % 16 == 0, "alignment");
     static_assert(3 * NF * 4 <= (ZR + 1) * 64, "the heads stage 3 x 256 floats in the stem feature image");
 };
 
@@ -222,10 +203,10 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_fx(const uint8_t* __restri
     uint8_t* bufH = lds;
     uint8_t* bufL = lds + G::PLANE;
     float* featF = reinterpret_cast<float*>(lds + G::FEAT_OFF);
-    uint8_t* in_l = lds + G::IN88_OFF;
-    uint8_t* rowof = lds + G::ROWOF_OFF;
-    uint8_t* taprow = lds + G::TAPROW_OFF;
-    uint16_t* rowcell = reinterpret_cast<uint16_t*>(lds + G::ROWCELL_OFF);
+    uint8_t* in_l = lds + G::TAB::IN88_OFF;
+    uint8_t* rowof = lds + G::TAB::ROWOF_OFF;
+    uint8_t* taprow = lds + G::TAB::TAPROW_OFF;
+    uint16_t* rowcell = reinterpret_cast<uint16_t*>(lds + G::TAB::ROWCELL_OFF);
     float* foldl = reinterpret_cast<float*>(lds + G::FOLD_OFF);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;        // MFMA fragment coordinates: board cell (column) c of a tile, k-group g
@@ -242,42 +223,24 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_fx(const uint8_t* __restri
         for (int q = 0; q < 2 * NT; q++)
             bq[ks][q] = __builtin_amdgcn_raw_buffer_load_b128(wsrc, loff + (q & 3) * 1024, (int)((uint32_t)ks * STEP_BYTES + (q >> 2) * (uint32_t)KBYTES), 0);
 
-    // ---- stage the NNInputData images, build the row tables
-    for (int i = tid; i < NB * 96; i += THREADS) {
-        const int b = i / 96, o = i % 96;
-        const int slot = (board0 + b < n) ? (slot_map ? slot_map[board0 + b] : board0 + b) : 0;
-        in_l[i] = (board0 + b < n && o < 88) ? in88[(size_t)slot * in_stride + o] : (uint8_t)0;
-    }
-    for (int i = tid; i < ROWB / 4; i += THREADS) {
-        reinterpret_cast<uint32_t*>(bufH + ZR * ROWB)[i] = 0;
-        reinterpret_cast<uint32_t*>(bufL + ZR * ROWB)[i] = 0;
-    }
+    // ---- stage the NNInputData images, build the row tables and the stem features in fp32 (featF: row ZR = zero row)
+    stage_inputs<NB, THREADS>(in_l, in88, in_stride, board0, n, slot_map);
+    clear_zero_rows<THREADS>(bufH + ZR * ROWB, bufL + ZR * ROWB);
+    // (build_row_tables of azr_rowclass.hpp, written out with the same two rules: through the helper this kernel's register numbers
+    //  change up to the end of its text — profiles/tower_common_isa.txt)
     for (int i = tid; i < ZR; i += THREADS) rowcell[i] = 0xffffu;
     __syncthreads();
     for (int i = tid; i < ROWS; i += THREADS) {
         const int b = i / 42, pos = i - b * 42, r = row_of<NB>(b, pos);
         rowof[i] = (uint8_t)r;
-        rowcell[r] = (uint16_t)((pos / 6) | ((pos % 6) << 4) | (b << 8));
+        rowcell[r] = (uint16_t)cell_code(b, pos);
     }
     __syncthreads();
-    for (int i = tid; i < 10 * ZR; i += THREADS) {   // source row of row r under tap t (pad rows and out-of-board taps: the zero row)
+    for (int i = tid; i < 10 * ZR; i += THREADS) {
         const int t = i / ZR, r = i - t * ZR;
-        const int ci = rowcell[r];
-        int src = ZR;
-        if (t < 9 && ci != 0xffff) {
-            const int y = (ci & 15) + t / 3 - 1, x = ((ci >> 4) & 15) + t % 3 - 1;
-            if ((unsigned)y < 7u && (unsigned)x < 6u) src = rowof[(ci >> 8) * 42 + y * 6 + x];
-        }
-        taprow[i] = (uint8_t)src;
+        taprow[i] = (uint8_t)tap_source_row<10>(t, rowcell[r], ZR, rowof);
     }
-    // stem features in fp32: featF as [ZR + 1][16] (row ZR = zero row); planes 13..15 are zero
-    for (int i = tid; i < (ZR + 1) * 16; i += THREADS) {
-        const int r = i >> 4, ch = i & 15;
-        float v = 0.0f;
-        const int ci = r < ZR ? rowcell[r] : 0xffff;
-        if (ci != 0xffff) v = plane_value(in_l + (ci >> 8) * 96, (ci & 15) * 6 + ((ci >> 4) & 15), ch);
-        featF[i] = v;
-    }
+    stem_features<ZR, THREADS>(in_l, rowcell, featF, [](float v) { return v; });
     __syncthreads();
 
     f32x4 acc[MT][NT];

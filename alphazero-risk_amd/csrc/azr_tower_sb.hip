@@ -23,28 +23,14 @@
 // (tile, tap) pairs are entirely out of board and are skipped.
 // Arithmetic is the k_tower_bf16 arithmetic — same k order, same fp32 epilogue, same RNE points — so results are
 // bit-identical across tile shapes (tests/test_gpu_net.py checks it).
+// The launch prologue, the table region of the LDS map and the layer epilogue are the ones of azr_tower_common.hpp.
 #include <stdlib.h>
 #include <string.h>
 
-#include <string>
-
 #include "azr_internal.hpp"
-#include "azr_bf16_common.hpp"
-#include "azr_rowclass.hpp"
+#include "azr_tower_common.hpp"
 
 using namespace azr;
-
-#define HIPCHK(h, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError(); /* the runtime's last-error slot is sticky: clear it */    \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return AZR_E_HIP;                                                                   \
-        }                                                                                       \
-    } while (0)
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 namespace {
 constexpr int NT = 4;                  // 16-channel column tiles per wave (4 waves x 64 channels)
@@ -62,16 +48,13 @@ struct SB {
     static constexpr int BUF = (ZR + 1) * ROWB;                 // the activation image incl. its zero row     96 288 B at NB = 4
     static constexpr int FEAT_OFF = BUF;                        // stem features [(ZR + 1)][16 bf16]             5 664 B
     static constexpr int HEAD_OFF = FEAT_OFF + (ZR + 1) * FROWB;  // heads scratch: NB x (128 + 256 + 64) floats 7 168 B
-    static constexpr int IN88_OFF = HEAD_OFF + NB * 448 * 4;    // NB x 96 B NNInputData images
-    static constexpr int ROWOF_OFF = IN88_OFF + NB * 96;        // u8 [ZR]: cell (board * 42 + pos) -> row
-    static constexpr int TAPROW_OFF = ROWOF_OFF + ZR;           // u8 [10][ZR]: source row of (tap, row); tap 9 = all zero row
-    static constexpr int ROWCELL_OFF = TAPROW_OFF + 10 * ZR;    // u16 [ZR]: row -> y | x << 4 | board << 8, 0xffff = pad row
-    static constexpr int FOLD_OFF = (ROWCELL_OFF + 2 * ZR + 15) / 16 * 16;   // float [2][256]: the current layer's folded BN scale | shift
+    using TAB = TowerTables<NB, ZR, HEAD_OFF + NB * 448 * 4>;   // NNInputData images and row tables
+    static constexpr int FOLD_OFF = TAB::END;                   // float [2][256]: the current layer's folded BN scale | shift
     static constexpr int LDS_BYTES = FOLD_OFF + 2 * NF * 4;
     static_assert(NB >= 2 && NB <= 4, "tile shapes");
     static_assert(72 % RING == 0 && RING <= MAX_RING, "ring depth");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-    static_assert(BUF % 16 == 0 && FEAT_OFF % 16 == 0 && HEAD_OFF % 16 == 0 && FOLD_OFF % 16 == 0 && TAPROW_OFF % 4 == 0 && ROWCELL_OFF % 2 == 0, "alignment");
+    static_assert(BUF % 16 == 0 && FEAT_OFF % 16 == 0 && HEAD_OFF % 16 == 0 && FOLD_OFF % 16 == 0, "alignment");
     static_assert(3 * NF * 4 <= (ZR + 1) * FROWB, "the heads stage 3 x 256 floats in the stem feature image");
 };
 
@@ -80,31 +63,6 @@ template <int N>
 __device__ __forceinline__ void wait_lgkm()
 {
     if constexpr (N >= 0 && N <= 14) __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));
-}
-
-__device__ __forceinline__ s16x8 lds16(const uint8_t* p) { return *reinterpret_cast<const s16x8*>(p); }
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-
-// Layer epilogue for 4 consecutive channels of one board cell: folded BN (fp32 fma), optional shortcut add (the packed
-// bf16 block input), ReLU, round-to-nearest-even to bf16.  Packed forms: v_pk_fma_f32 / v_pk_add_f32 / v_cvt_pk_bf16_f32 /
-// v_pk_max_i16 — ReLU is applied to the ROUNDED value as a signed 16-bit max with 0 (rounding is monotonic and odd, so
-// relu(rne(v)) == rne(relu(v)); -0 becomes +0 like `v > 0 ? v : 0`).
-template <bool SHORTCUT, bool F16>
-__device__ __forceinline__ uint2 bn_relu_pack(const f32x4& acc, const float4& s, const float4& h, const uint2& x)
-{
-    // (the two instantiations are kept apart on purpose: merged by the optimiser, the common fma of all 44 tiles is hoisted
-    //  above the parity branch and 176 intermediate values have to be parked)
-    f32x4 t = acc;
-    if (SHORTCUT) asm volatile("; epilogue with shortcut" : "+v"(t));
-    else asm volatile("; epilogue" : "+v"(t));
-    f32x2 lo = __builtin_elementwise_fma(f32x2{t[0], t[1]}, f32x2{s.x, s.y}, f32x2{h.x, h.y});
-    f32x2 hi = __builtin_elementwise_fma(f32x2{t[2], t[3]}, f32x2{s.z, s.w}, f32x2{h.z, h.w});
-    if (SHORTCUT) {
-        lo += f32x2{El<F16>::lo_of(x.x), El<F16>::hi_of(x.x)};
-        hi += f32x2{El<F16>::lo_of(x.y), El<F16>::hi_of(x.y)};
-    }
-    return uint2{El<F16>::pack_relu(lo), El<F16>::pack_relu(hi)};
 }
 
 // One tap (8 k-steps of 32 input channels) of a 3x3 conv layer for the 11 row tiles x 4 column tiles of a wave.  Everything
@@ -180,10 +138,10 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_sb(const uint8_t* __restri
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint8_t* bufX = lds;
     uint8_t* bufF = lds + G::FEAT_OFF;
-    uint8_t* in_l = lds + G::IN88_OFF;
-    uint8_t* rowof = lds + G::ROWOF_OFF;
-    uint8_t* taprow = lds + G::TAPROW_OFF;
-    uint16_t* rowcell = reinterpret_cast<uint16_t*>(lds + G::ROWCELL_OFF);
+    uint8_t* in_l = lds + G::TAB::IN88_OFF;
+    uint8_t* rowof = lds + G::TAB::ROWOF_OFF;
+    uint8_t* taprow = lds + G::TAB::TAPROW_OFF;
+    uint16_t* rowcell = reinterpret_cast<uint16_t*>(lds + G::TAB::ROWCELL_OFF);
     float* foldl = reinterpret_cast<float*>(lds + G::FOLD_OFF);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;        // MFMA fragment coordinates: board cell (column) c of a tile, k-group g
@@ -208,39 +166,11 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_sb(const uint8_t* __restri
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) bq[ks][nt] = __builtin_amdgcn_raw_buffer_load_b128(wsrc, loff + nt * 1024, ks * (int)KBYTES, 0);
 
-    // ---- stage the NNInputData images, build the row tables
-    for (int i = tid; i < NB * 96; i += THREADS) {
-        const int b = i / 96, o = i % 96;
-        const int slot = (board0 + b < n) ? (slot_map ? slot_map[board0 + b] : board0 + b) : 0;
-        in_l[i] = (board0 + b < n && o < 88) ? in88[(size_t)slot * in_stride + o] : (uint8_t)0;
-    }
-    for (int i = tid; i < ROWB / 4; i += THREADS) reinterpret_cast<uint32_t*>(bufX + ZR * ROWB)[i] = 0;
-    for (int i = tid; i < ZR; i += THREADS) rowcell[i] = 0xffffu;
-    __syncthreads();
-    for (int i = tid; i < ROWS; i += THREADS) {
-        const int b = i / 42, pos = i - b * 42, r = row_of<NB>(b, pos);
-        rowof[i] = (uint8_t)r;
-        rowcell[r] = (uint16_t)((pos / 6) | ((pos % 6) << 4) | (b << 8));
-    }
-    __syncthreads();
-    for (int i = tid; i < 10 * ZR; i += THREADS) {   // source row of row r under tap t (pad rows and out-of-board taps: the zero row)
-        const int t = i / ZR, r = i - t * ZR;
-        const int ci = rowcell[r];
-        int src = ZR;
-        if (t < 9 && ci != 0xffff) {
-            const int y = (ci & 15) + t / 3 - 1, x = ((ci >> 4) & 15) + t % 3 - 1;
-            if ((unsigned)y < 7u && (unsigned)x < 6u) src = rowof[(ci >> 8) * 42 + y * 6 + x];
-        }
-        taprow[i] = (uint8_t)src;
-    }
-    // stem features: bufF as [ZR + 1][16] bf16 (row ZR = zero row); planes 13..15 are zero
-    for (int i = tid; i < (ZR + 1) * 16; i += THREADS) {
-        const int r = i >> 4, ch = i & 15;
-        float v = 0.0f;
-        const int ci = r < ZR ? rowcell[r] : 0xffff;
-        if (ci != 0xffff) v = plane_value(in_l + (ci >> 8) * 96, (ci & 15) * 6 + ((ci >> 4) & 15), ch);
-        reinterpret_cast<uint16_t*>(bufF)[i] = El<F16>::rne(v);
-    }
+    // ---- stage the NNInputData images, build the row tables and the stem features (bufF: row ZR = zero row)
+    stage_inputs<NB, THREADS>(in_l, in88, in_stride, board0, n, slot_map);
+    clear_zero_rows<THREADS>(bufX + ZR * ROWB);
+    build_row_tables<NB, THREADS, 10>(rowof, taprow, rowcell);
+    stem_features<ZR, THREADS>(in_l, rowcell, reinterpret_cast<uint16_t*>(bufF), [](float v) { return El<F16>::rne(v); });
     __syncthreads();
 
     f32x4 acc[MT][NT];
@@ -368,39 +298,41 @@ __global__ __launch_bounds__(THREADS, 1) void k_tower_sb(const uint8_t* __restri
 
 namespace azr {
 
-template <int NB, bool F16>
-static int sb_attr(azr_engine* h)
+// the one <NB, F16> ladder: f(tile shape) for the handle's element type and nb = 2, 3 or 4 boards per workgroup
+template <int NB, bool F16> struct Shape { static constexpr int nb = NB; static constexpr bool f16 = F16; };
+template <class Fn>
+static int sb_dispatch(azr_engine* h, int nb, Fn f)
 {
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_tower_sb<NB, F16>), hipFuncAttributeMaxDynamicSharedMemorySize, SB<NB>::LDS_BYTES));
-    return AZR_OK;
-}
-int tower_sb_init(azr_engine* h)
-{
-    int rc = bf16net(h)->f16 ? (sb_attr<4, true>(h) || sb_attr<3, true>(h) || sb_attr<2, true>(h)) : (sb_attr<4, false>(h) || sb_attr<3, false>(h) || sb_attr<2, false>(h));
-    return rc ? AZR_E_HIP : AZR_OK;
+    if (bf16net(h)->f16) return nb == 4 ? f(Shape<4, true>{}) : nb == 3 ? f(Shape<3, true>{}) : f(Shape<2, true>{});
+    return nb == 4 ? f(Shape<4, false>{}) : nb == 3 ? f(Shape<3, false>{}) : f(Shape<2, false>{});
 }
 
-template <int NB, bool F16>
-static void sb_go(azr_engine* h, int wgs, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
+int tower_sb_init(azr_engine* h)
 {
-    Bf16Net* x = bf16net(h);
-    hipLaunchKernelGGL((k_tower_sb<NB, F16>), dim3(wgs), dim3(THREADS), SB<NB>::LDS_BYTES, st, d_in88, in_stride, n, x->stem_wp, x->tower_wp,
-                       F16 ? (const float*)x->fold16 : net_fold(h), h->net.blocks, net_head_params(h), d_pi, d_v, x->diag, d_map);
+    for (int nb = 4; nb >= 2; nb--) {
+        const int rc = sb_dispatch(h, nb, [&](auto s) -> int {
+            constexpr int NB = decltype(s)::nb;
+            constexpr bool F16 = decltype(s)::f16;
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_tower_sb<NB, F16>), hipFuncAttributeMaxDynamicSharedMemorySize, SB<NB>::LDS_BYTES));
+            return AZR_OK;
+        });
+        if (rc) return rc;
+    }
+    return AZR_OK;
 }
 
 // `wgs` workgroups of nb (2, 3 or 4) boards: boards [0, n) of the launch (the last workgroup may be partly filled)
 int tower_sb_launch(azr_engine* h, int nb, int wgs, const uint8_t* d_in88, int in_stride, int n, float* d_pi, float* d_v, const int* d_map, hipStream_t st)
 {
     if (nb < 2 || nb > 4 || wgs < 1 || (long long)wgs * nb < n) { h->err = "tower_sb_launch: bad tiling"; return AZR_E_INVALID_ARGUMENT; }
-    if (bf16net(h)->f16) {
-        if (nb == 4) sb_go<4, true>(h, wgs, d_in88, in_stride, n, d_pi, d_v, d_map, st);
-        else if (nb == 3) sb_go<3, true>(h, wgs, d_in88, in_stride, n, d_pi, d_v, d_map, st);
-        else sb_go<2, true>(h, wgs, d_in88, in_stride, n, d_pi, d_v, d_map, st);
-    } else {
-        if (nb == 4) sb_go<4, false>(h, wgs, d_in88, in_stride, n, d_pi, d_v, d_map, st);
-        else if (nb == 3) sb_go<3, false>(h, wgs, d_in88, in_stride, n, d_pi, d_v, d_map, st);
-        else sb_go<2, false>(h, wgs, d_in88, in_stride, n, d_pi, d_v, d_map, st);
-    }
+    Bf16Net* x = bf16net(h);
+    sb_dispatch(h, nb, [&](auto s) {
+        constexpr int NB = decltype(s)::nb;
+        constexpr bool F16 = decltype(s)::f16;
+        hipLaunchKernelGGL((k_tower_sb<NB, F16>), dim3(wgs), dim3(THREADS), SB<NB>::LDS_BYTES, st, d_in88, in_stride, n, x->stem_wp, x->tower_wp,
+                           F16 ? (const float*)x->fold16 : net_fold(h), h->net.blocks, net_head_params(h), d_pi, d_v, x->diag, d_map);
+        return 0;
+    });
     HIPCHK(h, hipGetLastError());
     return AZR_OK;
 }

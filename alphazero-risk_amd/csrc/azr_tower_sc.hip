@@ -35,31 +35,14 @@
 // Block ids are laid out so that a pair's workgroups are 8 ids apart (same XCD under round-robin dispatch:
 // speed only).  Arithmetic = k_tower_sb<2>'s: same packed weights, row order, skipped (tile, tap) pairs, k order, fp32 epilogue and
 // RNE points — bit-identical results (tests/test_gpu_net.py::test_tile_shapes_agree_bit_for_bit).
+// The launch prologue, the table region of the LDS map and the layer epilogue are the ones of azr_tower_common.hpp.
 #include <stdlib.h>
 #include <string.h>
 
-#include <string>
-
 #include "azr_internal.hpp"
-#include "azr_bf16_common.hpp"
-#include "azr_rowclass.hpp"
+#include "azr_tower_common.hpp"
 
 using namespace azr;
-
-#define HIPCHK(h, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (void)hipGetLastError(); /* the runtime's last-error slot is sticky: clear it */    \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return AZR_E_HIP;                                                                   \
-        }                                                                                       \
-    } while (0)
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
 
 namespace {
 constexpr int NB = 2, ROWS = 84, MT = 6, ZR = 96, THREADS = 256;
@@ -77,31 +60,10 @@ constexpr int W_FALLBACKS = 2 * MAX_PAIRS + 1;        // ... launches the guarde
 
 // LDS map (dynamic): image | stem features | NNInputData images | tables | heads scratch
 constexpr int FEAT_OFF = IMG;
-constexpr int IN88_OFF = FEAT_OFF + (ZR + 1) * FROWB;
-constexpr int ROWOF_OFF = IN88_OFF + NB * 96;
-constexpr int TAPROW_OFF = ROWOF_OFF + ZR;
-constexpr int ROWCELL_OFF = TAPROW_OFF + 10 * ZR;
-constexpr int HEAD_OFF = (ROWCELL_OFF + 2 * ZR + 15) / 16 * 16;
+using TAB = TowerTables<NB, ZR, FEAT_OFF + (ZR + 1) * FROWB>;
+constexpr int HEAD_OFF = TAB::END;
 constexpr int LDS_BYTES = HEAD_OFF + (3 * NF + NB * 128 + NB * 256 + NB * 64) * 4;
 static_assert(LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-
-__device__ __forceinline__ s16x8 lds16(const uint8_t* p) { return *reinterpret_cast<const s16x8*>(p); }
-
-// k_tower_sb's epilogue, verbatim: folded BN (fp32 fma), optional shortcut add (packed bf16 block input), ReLU on the rounded value
-template <bool SHORTCUT, bool F16>
-__device__ __forceinline__ uint2 bn_relu_pack(const f32x4& acc, const float4& s, const float4& h, const uint2& x)
-{
-    f32x4 t = acc;
-    if (SHORTCUT) asm volatile("; epilogue with shortcut" : "+v"(t));
-    else asm volatile("; epilogue" : "+v"(t));
-    f32x2 lo = __builtin_elementwise_fma(f32x2{t[0], t[1]}, f32x2{s.x, s.y}, f32x2{h.x, h.y});
-    f32x2 hi = __builtin_elementwise_fma(f32x2{t[2], t[3]}, f32x2{s.z, s.w}, f32x2{h.z, h.w});
-    if (SHORTCUT) {
-        lo += f32x2{El<F16>::lo_of(x.x), El<F16>::hi_of(x.x)};
-        hi += f32x2{El<F16>::lo_of(x.y), El<F16>::hi_of(x.y)};
-    }
-    return uint2{El<F16>::pack_relu(lo), El<F16>::pack_relu(hi)};
-}
 
 // the row tiles of a wave half: 0 - 2 (the board-edge tiles, which skip 3 of their 9 taps each) and 3 - 5.  Uneven on purpose: dealing
 // the edge tiles over both halves (24 and 21 tile-taps instead of 18 and 27) measured 3 - 5 % slower — a k-step is bound by the
@@ -325,8 +287,8 @@ __device__ __forceinline__ bool sc_run(uint8_t* lds, int pair, int cg, int block
     if (threadIdx.x == 0) __hip_atomic_fetch_add(xccw, 1u << (3u * xcc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint8_t* bufX = lds;
     const uint8_t* bufF = lds + FEAT_OFF;
-    const uint8_t* taprow = lds + TAPROW_OFF;
-    const uint16_t* rowcell = reinterpret_cast<const uint16_t*>(lds + ROWCELL_OFF);
+    const uint8_t* taprow = lds + TAB::TAPROW_OFF;
+    const uint16_t* rowcell = reinterpret_cast<const uint16_t*>(lds + TAB::ROWCELL_OFF);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
     const bool mh = (wave >> 1) != 0;                   // wave-uniform: this wave's row half
     const int ct0 = cg * 4 + (wave & 1) * NTW;          // this wave's first 16-channel column tile
@@ -432,45 +394,24 @@ __global__ __launch_bounds__(THREADS) void k_tower_sc(const uint8_t* __restrict_
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint8_t* bufX = lds;
     uint8_t* bufF = lds + FEAT_OFF;
-    uint8_t* in_l = lds + IN88_OFF;
-    uint8_t* rowof = lds + ROWOF_OFF;
-    uint8_t* taprow = lds + TAPROW_OFF;
-    uint16_t* rowcell = reinterpret_cast<uint16_t*>(lds + ROWCELL_OFF);
+    uint8_t* in_l = lds + TAB::IN88_OFF;
+    uint8_t* rowof = lds + TAB::ROWOF_OFF;
+    uint8_t* taprow = lds + TAB::TAPROW_OFF;
+    uint16_t* rowcell = reinterpret_cast<uint16_t*>(lds + TAB::ROWCELL_OFF);
     const int tid = threadIdx.x;
     const int board0 = pair * NB;
 
-    // ---- NNInputData images, zero row, row tables, stem features (as k_tower_sb)
+    // ---- NNInputData images, zero row, row tables, stem features.  (The staging loop is stage_inputs of azr_tower_common.hpp, written out:
+    // through the helper its guard `tid < 192` swaps operands with an equal test of gather(), inside the layer loop —
+    // profiles/tower_common_isa.txt.)
     for (int i = tid; i < NB * 96; i += THREADS) {
         const int b = i / 96, o = i % 96;
         const int slot = (board0 + b < n) ? (slot_map ? slot_map[board0 + b] : board0 + b) : 0;
         in_l[i] = (board0 + b < n && o < 88) ? in88[(size_t)slot * in_stride + o] : (uint8_t)0;
     }
-    for (int i = tid; i < ROWB / 4; i += THREADS) reinterpret_cast<uint32_t*>(bufX + ZR * ROWB)[i] = 0;
-    for (int i = tid; i < ZR; i += THREADS) rowcell[i] = 0xffffu;
-    __syncthreads();
-    for (int i = tid; i < ROWS; i += THREADS) {
-        const int b = i / 42, pos = i - b * 42, rr = row_of<NB>(b, pos);
-        rowof[i] = (uint8_t)rr;
-        rowcell[rr] = (uint16_t)((pos / 6) | ((pos % 6) << 4) | (b << 8));
-    }
-    __syncthreads();
-    for (int i = tid; i < 10 * ZR; i += THREADS) {
-        const int t = i / ZR, rr = i - t * ZR;
-        const int ci = rowcell[rr];
-        int src = ZR;
-        if (t < 9 && ci != 0xffff) {
-            const int y = (ci & 15) + t / 3 - 1, x = ((ci >> 4) & 15) + t % 3 - 1;
-            if ((unsigned)y < 7u && (unsigned)x < 6u) src = rowof[(ci >> 8) * 42 + y * 6 + x];
-        }
-        taprow[i] = (uint8_t)src;
-    }
-    for (int i = tid; i < (ZR + 1) * 16; i += THREADS) {
-        const int rr = i >> 4, ch = i & 15;
-        float v = 0.0f;
-        const int ci = rr < ZR ? rowcell[rr] : 0xffff;
-        if (ci != 0xffff) v = plane_value(in_l + (ci >> 8) * 96, (ci & 15) * 6 + ((ci >> 4) & 15), ch);
-        reinterpret_cast<uint16_t*>(bufF)[i] = El<F16>::rne(v);
-    }
+    clear_zero_rows<THREADS>(bufX + ZR * ROWB);
+    build_row_tables<NB, THREADS, 10>(rowof, taprow, rowcell);
+    stem_features<ZR, THREADS>(in_l, rowcell, reinterpret_cast<uint16_t*>(bufF), [](float v) { return El<F16>::rne(v); });
     // pad rows of the image are MFMA operands of nobody (their tile rows read the zero row) but the image is also fetched whole:
     // keep them defined
     for (int i = tid; i < ZR * (ROWB / 4); i += THREADS) reinterpret_cast<uint32_t*>(bufX)[i] = 0;
@@ -535,7 +476,7 @@ int tower_sc_launch(azr_engine* h, const uint8_t* d_in88, int in_stride, int n, 
     Bf16Net* x = bf16net(h);
     const int pairs = (n + 1) / 2, B = h->net.blocks;
     const int wgs = ((pairs + 7) / 8) * 8 * CGN;     // whole groups of 8 pairs (ids of a pair's workgroups are 8 apart)
-    const uint32_t tower_bytes = (uint32_t)(((size_t)2 * B * TOWER_LAYER_HALFS + MAX_RING * KSTRIDE * 8) * 2);
+    const uint32_t tower_bytes = (uint32_t)tower_stream_bytes(B);
     const uint32_t ex_bytes = (uint32_t)((size_t)2 * MAX_PAIRS * EX_PAIR_BYTES);
     // The pairs' words count within ONE launch: the guarded launch the caller queues behind this one zeroes them again (workgroup 0, before
     // anything else) — no memset in front of a launch.  The give-up word carries the launch's serial number in its upper 30 bits: what an

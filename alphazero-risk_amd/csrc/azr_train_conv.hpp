@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "azr_bf16_common.hpp"   // the vector register types
 #include "azr_rowclass.hpp"
 #include "azr_train_common.hpp"
 
@@ -19,9 +20,6 @@ namespace {
 // (80-byte stride: an MFMA fragment's ds_read_b128 is conflict-free).  Operand views as in gt_load (MODE 0..3); a
 // mn-contiguous operand is transposed in registers (8 dword loads down k, v_perm, two 16-byte LDS writes).
 // =====================================================================================================================
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 constexpr int K3 = 32, KP3 = 40;
 struct Parts { const uint16_t* p[3]; };
 
@@ -33,11 +31,9 @@ __device__ __forceinline__ uint32_t bf_rne_bits(float f)
 // two floats -> two bf16 (round to nearest even) packed low | high: ONE v_cvt_pk_bf16_f32 where bf_rne_bits spends three integer
 // operations per value and two more to pack — the same bits for every finite input (the staging paths of the fused convs run this for
 // every element of every layer: profiles/r04_train_step.txt)
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 __device__ __forceinline__ uint32_t bf_rne_pk(float a, float b)
 {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
 // hi and mid bf16 parts of a pair of floats (hi = rne(v), mid = rne(v - hi)), packed
 __device__ __forceinline__ void bf_split2(float a, float b, uint32_t& hi, uint32_t& mid)
@@ -70,12 +66,11 @@ __device__ __forceinline__ void split_store4(const float (&v)[4], size_t i4, uin
 
 // the fp16 pair of 4 consecutive values: hi = rne16(v), lo = rne16(v - hi) (unscaled: the matrix core takes fp16 subnormals),
 // 22 significand bits — the operand format of the 3-pass forward conv (t_conv_rs<1, 2, 0, true>)
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 __device__ __forceinline__ void f16_pair4(const float (&v)[4], uint2& hi, uint2& lo)
 {   // two values per conversion (v_cvt_pk_f16_f32, RNE: the bits of the scalar conversions)
-    const f16x2_t h01 = __builtin_convertvector(f32x2_t{v[0], v[1]}, f16x2_t), h23 = __builtin_convertvector(f32x2_t{v[2], v[3]}, f16x2_t);
-    const f16x2_t l01 = __builtin_convertvector(f32x2_t{v[0] - (float)h01[0], v[1] - (float)h01[1]}, f16x2_t);
-    const f16x2_t l23 = __builtin_convertvector(f32x2_t{v[2] - (float)h23[0], v[3] - (float)h23[1]}, f16x2_t);
+    const f16x2 h01 = __builtin_convertvector(f32x2{v[0], v[1]}, f16x2), h23 = __builtin_convertvector(f32x2{v[2], v[3]}, f16x2);
+    const f16x2 l01 = __builtin_convertvector(f32x2{v[0] - (float)h01[0], v[1] - (float)h01[1]}, f16x2);
+    const f16x2 l23 = __builtin_convertvector(f32x2{v[2] - (float)h23[0], v[3] - (float)h23[1]}, f16x2);
     hi = make_uint2(__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23));
     lo = make_uint2(__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23));
 }
@@ -199,8 +194,6 @@ __global__ __launch_bounds__(256) void t_pack_w(const float* __restrict__ flat, 
 // AMODE 1: C[row] = sum_tap A[row + tap] W[tap]; AMODE 2 (backward-data): negated taps, i.e. loop index t reads the
 // geometric tap 8 - t, with the transposed kernel view.  `boards` = rows / 42 (the last block may hold one board).
 // ---------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 template <int NP> struct RsPass;
 template <> struct RsPass<3> { static constexpr int N = 6; static constexpr int QA[6] = {2, 0, 1, 1, 0, 0}, QB[6] = {0, 2, 1, 0, 1, 0}; };
 template <> struct RsPass<2> { static constexpr int N = 3; static constexpr int QA[3] = {1, 0, 0}, QB[3] = {0, 1, 0}; };
@@ -213,12 +206,11 @@ struct Rs {
     static constexpr uint32_t KB = 16 * 64 * 16;         // bytes of one k-step of packed weights (16 column tiles x 64 lanes x 16 B)
 };
 
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 // one MFMA of the conv kernels: packed weight fragment x activation fragment, fp16 pairs (F16) or bf16 parts
 template <bool F16>
 __device__ __forceinline__ f32x4 mfma_part(const u32x4& b, const s16x8& a, const f32x4& acc)
 {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, b), __builtin_bit_cast(f16x8_t, a), acc, 0, 0, 0);
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b), __builtin_bit_cast(f16x8, a), acc, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, a), acc, 0, 0, 0);
 }
 
@@ -383,7 +375,8 @@ __global__ __launch_bounds__(256, 1) void t_conv_rs(Parts A, Parts Bp, float* __
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) bq[s2][q][nt] = __builtin_amdgcn_raw_buffer_load_b128(wsrc[q], loff + nt * 1024, (int)((s2 * 8) * KB), 0);
 
-    // ---- tables
+    // ---- tables (the rules of build_row_tables, azr_rowclass.hpp, in this kernel's own loops: through the helper its register numbers
+    // change up to the end of its text — profiles/tower_common_isa.txt)
     for (int i = tid; i < ZR; i += 256) rowcell[i] = 0xffffu;
     for (int i = tid; i < 2 * NP * (CHB / 4); i += 256) {   // the zero rows of both buffers
         const int bp = i / (CHB / 4), w4 = i % (CHB / 4);
@@ -393,17 +386,12 @@ __global__ __launch_bounds__(256, 1) void t_conv_rs(Parts A, Parts Bp, float* __
     for (int i = tid; i < ROWS; i += 256) {
         const int b = i / NPOS, pos = i - b * NPOS, r = row_of<NB>(b, pos);
         rowof[i] = (uint8_t)r;
-        rowcell[r] = (uint16_t)((pos / 6) | ((pos % 6) << 4) | (b << 8));
+        rowcell[r] = (uint16_t)cell_code(b, pos);
     }
     __syncthreads();
     for (int i = tid; i < 9 * ZR; i += 256) {
-        const int t = i / ZR, r = i - t * ZR, ci = rowcell[r];
-        int src = ZR;
-        if (ci != 0xffff) {
-            const int y = (ci & 15) + t / 3 - 1, x = ((ci >> 4) & 15) + t % 3 - 1;
-            if ((unsigned)y < 7u && (unsigned)x < 6u) src = rowof[(ci >> 8) * NPOS + y * 6 + x];
-        }
-        taprow[i] = (uint8_t)src;
+        const int t = i / ZR, r = i - t * ZR;
+        taprow[i] = (uint8_t)tap_source_row<9>(t, rowcell[r], ZR, rowof);
     }
     // this thread's units of a slice.  PRO = 0: (part, cell, 16-byte segment of 8 halfs) -> global element offset (chunk 0) and LDS
     // byte offset.  PRO != 0: (cell, 4 channels): the fp32 sources are fetched, the operand is computed when the slice is stashed.

@@ -80,6 +80,52 @@ def test_a_rename_is_followed():
     assert not ok
 
 
+def test_template_arguments_survive_an_anonymous_namespace():
+    # the argument list is the bracket that closes at the end, whatever stands in front of the name or inside the list
+    assert isa.short_name("void (anonymous namespace)::k_tower_sb<4, true>(unsigned char const*, int)") == "k_tower_sb<4, true>"
+    assert isa.short_name("void (anonymous namespace)::k_tower_sb<4, false>(unsigned char const*, int)") == "k_tower_sb<4, false>"
+    assert isa.short_name("void k_noise<true, false>()") == "k_noise<true, false>"
+    assert isa.short_name("k_foo(int (*)(), int)") == "k_foo" and isa.short_name("_Zunknown") == "_Zunknown"
+    # two mangled names that differ only in a template argument are two kernels, with or without a demangler on the machine
+    a, b = "_ZN12_GLOBAL__N_110k_tower_sbILi4ELb1EEEvPKhi", "_ZN12_GLOBAL__N_110k_tower_sbILi4ELb0EEEvPKhi"
+    names = isa.demangle([a, b])
+    assert names[a] != names[b]
+    assert (names[a], names[b]) in ((a, b), ("k_tower_sb<4, true>", "k_tower_sb<4, false>"))
+    both = isa.kernels_of("".join(_kernel(n, i, 1, "0x10", "")[0] for i, n in enumerate((a, b))), "")
+    assert sorted(both) == sorted(names.values())
+
+
+def _with_mfma(kernel, head, tail):
+    """the snippet's loop body gets an MFMA; `head` / `tail` = immediates in front of it (line 1) and behind it"""
+    res, text = kernel
+    at = text.index("v_add_u32_e32 v0, 1, v0")
+    return res, ["s_load_dwordx2 s[0:1], s[0:1], %s" % head] + text[1:at] + ["v_mfma_f32_16x16x32_bf16 a[0:3], v[0:3], v[4:7], a[0:3]",
+                                                                              "v_add_u32_e32 v0, %s, v0" % tail] + text[at + 1:]
+
+
+def test_from_the_first_mfma_on():
+    base = _build(_kernel("k_a", 0, 1, "0x10", ""))["k_a"]
+    old = {"k_a": _with_mfma(base, "0x10", 1), "k_b": _with_mfma(base, "0x10", 1)}
+    new = {"k_a": _with_mfma(base, "0x18", 1), "k_b": _with_mfma(base, "0x10", 2)}   # k_a differs in front of the MFMA, k_b behind it
+    assert isa.first_mfma(old["k_a"][1]) == 5 and isa.first_mfma(base[1]) == 0
+    assert isa.line_diff(old["k_a"][1], new["k_a"][1]) == (2, 1, 1) and isa.line_diff(old["k_b"][1], new["k_b"][1]) == (2, 6, 6)
+    rows, ok = isa.compare(old, new, from_mfma=["k_a"])
+    assert ok and "parent's last differing line 1, its first v_mfma 5: 2 differing lines" in _row(rows, "k_a")
+    assert "parent's last differing line 6, its first v_mfma 5" in _row(rows, "k_b")
+    rows, ok = isa.compare(old, new, from_mfma=["k_a", "k_b"])
+    assert not ok and "MUST MATCH FROM THE FIRST MFMA" in _row(rows, "k_b") and "MUST MATCH" not in _row(rows, "k_a")
+    # a line that only the new text has, behind ITS first MFMA, counts as well; so does the MFMA line itself
+    longer = {"k_a": (base[0], new["k_a"][1] + ["s_nop 0"])}
+    assert not isa.compare(old, longer, from_mfma=["k_a"])[1]
+    moved = {"k_a": (base[0], [l.replace("a[0:3], v[0:3]", "a[0:3], v[8:11]") for l in old["k_a"][1]])}
+    assert not isa.compare(old, moved, from_mfma=["k_a"])[1]
+    # identical text passes; a kernel without an MFMA has to match as a whole; a missing kernel fails
+    assert isa.compare(old, old, from_mfma=["k_a", "k_b"])[1]
+    plain_old, plain_new = _build(_kernel("k_a", 0, 1, "0x10", "")), _build(_kernel("k_a", 0, 1, "0x18", ""))
+    assert not isa.compare(plain_old, plain_new, from_mfma=["k_a"])[1] and isa.compare(plain_old, plain_old, from_mfma=["k_a"])[1]
+    assert not isa.compare(old, new, from_mfma=["k_c"])[1]
+
+
 def test_a_resource_number_or_a_vgpr_spill_fails():
     old = _build(_kernel("k_a", 0, 1, "0x10", ""))
     rows, ok = isa.compare(old, _build(_kernel("k_a", 0, 1, "0x10", "", vgprs=7)))

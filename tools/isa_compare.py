@@ -2,15 +2,19 @@
 """Device code of two source trees (or two git revisions) side by side, without a GPU: the check behind "no change to the kernels".
 
     tools/isa_compare.py OLD NEW [--file azr_engine.hip ...] [--rename 'k_old = k_new<true, false>' ...] [--must-match KERNEL ...]
+                         [--must-match-from-mfma KERNEL ...]
 
 OLD and NEW are directories holding a checkout, or git revisions, which are exported to temporary directories.  The named .hip files
 of alphazero-risk_amd/csrc are cross-compiled for gfx950 with that tree's own Makefile CXXFLAGS plus `--cuda-device-only -S
 -Rpass-analysis=kernel-resource-usage`, once as the product build and once with -DAZR_TEST_HOOKS.  Per kernel the resource remarks are
 compared, and the instruction text with comments dropped and block labels renumbered in order of appearance; "differing lines" counts
-the lines of a line diff, "opcode sequence" compares the mnemonics alone.  A compile, not a run.
+the lines of a line diff, "opcode sequence" compares the mnemonics alone.  For a kernel that differs, the last differing line of the
+parent's text and the parent's first v_mfma line are printed too: code in front of a kernel's first MFMA runs once per launch.  Kernels
+are named as the demangler prints them, without the argument list and without `(anonymous namespace)::`.  A compile, not a run.
 
-Exit status 1 if a --must-match kernel differs in instruction text (or is missing), a kernel of both trees differs in a resource
-number, or any kernel spills a VGPR.
+Exit status 1 if a --must-match kernel differs in instruction text (or is missing), a --must-match-from-mfma kernel differs at or
+behind the first v_mfma line of either text (or anywhere, if it has no MFMA; or is missing), a kernel of both trees differs in a
+resource number, or any kernel spills a VGPR.
 """
 import argparse, difflib, os, re, shlex, subprocess, sys, tarfile, tempfile
 
@@ -40,9 +44,16 @@ def opcodes(lines):
     return [l.split()[0] for l in lines if not l.endswith(":")]
 
 
-def differing_lines(a, b):
-    sm = difflib.SequenceMatcher(None, a, b, autojunk=False)
-    return sum((i2 - i1) + (j2 - j1) for tag, i1, i2, j1, j2 in sm.get_opcodes() if tag != "equal")
+def line_diff(a, b):
+    """(differing lines of the line diff, 1-based number of the last differing line of `a`, of `b`) — 0 where a text has none"""
+    ops = [o for o in difflib.SequenceMatcher(None, a, b, autojunk=False).get_opcodes() if o[0] != "equal"]
+    return (sum((i2 - i1) + (j2 - j1) for _, i1, i2, j1, j2 in ops), max([i2 for _, i1, i2, _, _ in ops if i2 > i1], default=0),
+            max([j2 for _, _, _, j1, j2 in ops if j2 > j1], default=0))
+
+
+def first_mfma(lines):
+    """1-based number of the first line starting with v_mfma, 0 if there is none"""
+    return next((i + 1 for i, l in enumerate(lines) if l.startswith("v_mfma")), 0)
 
 
 def resources(remarks):
@@ -56,6 +67,20 @@ def resources(remarks):
     return out
 
 
+def short_name(demangled):
+    """`void (anonymous namespace)::k_name<4, true>(unsigned char const*, int)` -> `k_name<4, true>`: the argument list is the
+    bracket that closes at the end of the name, not everything from the first bracket on"""
+    d = demangled.strip()
+    if d.endswith(")"):
+        depth = 0
+        for i in range(len(d) - 1, -1, -1):
+            depth += (d[i] == ")") - (d[i] == "(")
+            if depth == 0:
+                d = d[:i]
+                break
+    return re.sub(r"^void ", "", d).replace("(anonymous namespace)::", "")
+
+
 def demangle(names):
     """mangled -> `k_name<args>` if a demangler is on the machine, else the mangled name"""
     for tool in ("c++filt", "llvm-cxxfilt", "/opt/rocm/llvm/bin/llvm-cxxfilt"):
@@ -63,7 +88,7 @@ def demangle(names):
             res = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
         except (OSError, subprocess.CalledProcessError):
             continue
-        return {n: re.sub(r"^void ", "", re.sub(r"\(.*\)$", "", d)) for n, d in zip(names, res)}
+        return {n: short_name(d) for n, d in zip(names, res)}
     return {n: n for n in names}
 
 
@@ -74,7 +99,7 @@ def kernels_of(asm, remarks, names=demangle):
     return {nm[k]: (res.get(k, {}), normalise(v)) for k, v in text.items()}
 
 
-def compare(old, new, renames=None, must_match=()):
+def compare(old, new, renames=None, must_match=(), from_mfma=()):
     """(report lines, ok) for two kernels_of() dictionaries; `renames` maps a name of `old` to its name in `new`"""
     old = {(renames or {}).get(k, k): v for k, v in old.items()}
     ok, rows = True, []
@@ -90,12 +115,15 @@ def compare(old, new, renames=None, must_match=()):
             ok, row = False, row + "RESOURCES DIFFER (parent: %s); " % ", ".join("%s %s" % (s, ores.get(r, "?")) for r, s in RES if ores.get(r) != res.get(r))
         if otext == text: row += "identical"
         else:
-            row += "%d differing lines (parent: %d lines); opcode sequence: %s" % (differing_lines(otext, text), len(otext),
-                                                                                 "identical" if opcodes(otext) == opcodes(text) else "differs")
+            n, olast, last = line_diff(otext, text)
+            omfma, mfma = first_mfma(otext), first_mfma(text)
+            row += "parent's last differing line %d, its first v_mfma %s: %d differing lines (parent: %d lines); opcode sequence: %s" % (
+                olast, omfma or "none", n, len(otext), "identical" if opcodes(otext) == opcodes(text) else "differs")
             if k in must_match: ok, row = False, row + "; MUST MATCH"
+            if k in from_mfma and (not omfma or not mfma or olast >= omfma or last >= mfma): ok, row = False, row + "; MUST MATCH FROM THE FIRST MFMA"
         rows.append(row)
     gone = sorted(set(old) - set(new))
-    for k in must_match:
+    for k in list(must_match) + list(from_mfma):
         if k not in new or k not in old: ok = False; rows.append("%s | must match, but is not in both trees" % k)
     head = "%d kernels in the parent, %d in the new build; only in parent: %s; only in new: %s" % (
         len(old), len(new), ", ".join(gone) or "none", ", ".join(sorted(set(new) - set(old))) or "none")
@@ -141,6 +169,8 @@ def main():
     ap.add_argument("--file", action="append", help="a .hip file of alphazero-risk_amd/csrc (default: azr_engine.hip)")
     ap.add_argument("--rename", action="append", default=[], metavar="'OLD = NEW'", help="a parent kernel's name in the new tree")
     ap.add_argument("--must-match", action="append", default=[], metavar="KERNEL", help="new-tree name of a kernel that has to be instruction-identical")
+    ap.add_argument("--must-match-from-mfma", action="append", default=[], metavar="KERNEL",
+                    help="new-tree name of a kernel that may differ only in front of its first v_mfma line")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     a = ap.parse_args()
     renames = dict(tuple(s.strip() for s in r.split("=", 1)) for r in a.rename)
@@ -148,11 +178,11 @@ def main():
     old, new = tree_of(a.old, keep), tree_of(a.new, keep)
     for hooks, title in ((False, "product build (libazr_hip.so)"), (True, "hook build (libazr_hip_test.so, -DAZR_TEST_HOOKS)")):
         rows, good = compare(compile_tree(old, a.file or ["azr_engine.hip"], hooks, a.hipcc),
-                             compile_tree(new, a.file or ["azr_engine.hip"], hooks, a.hipcc), renames, a.must_match)
+                             compile_tree(new, a.file or ["azr_engine.hip"], hooks, a.hipcc), renames, a.must_match, a.must_match_from_mfma)
         ok = ok and good
         print("# %s: %s" % (title, rows[0]))
         print("\n".join(rows[1:]))
-        print("# conditions (must-match kernels identical, the parent's kernels keep their resource numbers, no VGPR spill): %s\n" % ("hold" if good else "VIOLATED"))
+        print("# conditions (must-match kernels identical, from-mfma kernels identical from their first MFMA on, the parent's kernels keep their resource numbers, no VGPR spill): %s\n" % ("hold" if good else "VIOLATED"))
     return 0 if ok else 1
 
 
