@@ -222,7 +222,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                 mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
                 if (FORCED && E.prune && (!CAP || full)) {   // the record's pi from N'; the move above is N's
                     const uint32_t rkd = ws_record_dword(root);
-                    pi = root_policy(root_pruned_counts(E, S, t, tree_lookup(t, rkd, key_hash(rkd)), N, valid, eta, E.forced_k), valid);
+                    pi = root_policy(root_pruned_counts(E, S, t, tree_lookup(t, rkd, key_hash(t, rkd)), N, valid, eta, E.forced_k), valid);
                 }
                 if (SURPRISE && (!CAP || full)) stage_surprise(E, g, c, pi, P, valid);
                 if (!CAP || full) stage_sample(E, g, c, root, pi, k);
@@ -563,10 +563,14 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     d.G = s->games;
     d.T = s->mcts_threads;
     int C = s->node_capacity > 0 ? s->node_capacity : 16 * (s->mcts_simulations + 1);
-    if (C < 64) C = 64;
+    if (C < 8) C = 8;   // H >= 16: one probe round (16 slots) never reads a slot twice
     d.C = C;
     d.H = next_pow2(2 * C);
     d.DMAX = std::min(C, 1024);
+#ifdef AZR_TEST_HOOKS
+    d.hash_and = hook_env("AZR_TREE_HASH_AND") ? (uint32_t)strtoul(hook_env("AZR_TREE_HASH_AND"), nullptr, 0) : 0xffffffffu;
+    d.hash_or = hook_env("AZR_TREE_HASH_OR") ? (uint32_t)strtoul(hook_env("AZR_TREE_HASH_OR"), nullptr, 0) : 0u;
+#endif
     d.SCAP = s->sample_capacity > 0 ? s->sample_capacity : 4096;
     d.rules = Rules{s->allow_yield, s->limit_reinforcement, s->limit_attack, s->max_game_rounds, s->min_unit_move};
     // count = MCTS_SIMULATIONS - MCTS_SIMULATIONS % THREADS_PER_MCTS (alphazero_mcts.cpp:265)

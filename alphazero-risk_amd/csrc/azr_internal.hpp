@@ -132,6 +132,10 @@ struct Dev {
     float psw_share;           // the share of a game's record weight handed out by surprise (0 = off)
     float psw_max;             // the cap on one record's weight
     uint32_t psw_seed;         // the copy coin is keyed by (psw_seed, game seed, record)
+#ifdef AZR_TEST_HOOKS
+    // AZR_TREE_HASH_AND / AZR_TREE_HASH_OR, read when the engine is created: key_hash returns (h & hash_and) | hash_or (azr_tree.hpp)
+    uint32_t hash_and, hash_or;
+#endif
 };
 constexpr int ALOG = 16;
 

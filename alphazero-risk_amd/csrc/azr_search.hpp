@@ -12,6 +12,9 @@ __device__ __forceinline__ Tree tree_of(const Dev& E, int g)
 {
     Tree t;
     t.C = E.C; t.H = E.H; t.DMAX = E.DMAX;
+#ifdef AZR_TEST_HOOKS
+    t.hash_and = E.hash_and; t.hash_or = E.hash_or;
+#endif
     t.nodes = E.nodes + (size_t)g * E.C * NODE_BYTES;
     t.touch = E.touch + (size_t)g * E.C;
     t.nhash = E.nhash + (size_t)g * E.C;
@@ -205,6 +208,13 @@ __device__ __forceinline__ void consume_pending(const Dev& E, int g, const Tree&
             TP(2);
             float prior = normalize_prior(pi, valid);
             TP(3);
+            // The ROOT finds the pool full (every pooled node survived the trim and the new root is none of them).  Dropping it would have
+            // the next pass ask for it again, for ever: the search could not start.  The tree is emptied for it, as by clearNodes, and
+            // the evicted nodes are counted.  No path is in flight: the threads start after the root.
+            if (plen_get(c, th) == 0 && c.nfree == 0 && (int)c.hiwater >= t.C) {
+                k.drop += c.hiwater;
+                tree_clear(t, c);
+            }
             if (tree_expand(t, c, kd, h, valid, prior) == NO_NODE) k.drop++;
         }
         TP(4);
@@ -258,7 +268,7 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
             TP(8);
             if (valid == 0) { fail = true; s.err = E_INVALID_ARGUMENT; break; }
             uint32_t kd = ws_record_dword(s);
-            uint32_t h = key_hash(kd);
+            uint32_t h = key_hash(t, kd);
             TP(9);
             NodeRegs nr;
             uint32_t idx = tree_lookup_node(t, kd, h, nr);
@@ -321,7 +331,7 @@ __device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g
 __device__ __forceinline__ uint32_t root_node(const Tree& t, const WS& root, uint32_t& N, uint64_t& valid, float* Q = nullptr, float* P = nullptr)
 {
     uint32_t rkd = ws_record_dword(root);
-    uint32_t ridx = tree_lookup(t, rkd, key_hash(rkd));
+    uint32_t ridx = tree_lookup(t, rkd, key_hash(t, rkd));
     N = 0; valid = 0;
     if (ridx != NO_NODE) {
         const uint8_t* n = node_ptr(t, ridx);

@@ -74,6 +74,9 @@ struct Tree {  // this game's slices of the engine's HBM arrays
     uint16_t* freel;     // [C]   free-slot stack
     uint32_t* path;      // [DMAX] node | move << 16 | flip << 24   (the current search thread's stack)
     int C, H, DMAX;
+#ifdef AZR_TEST_HOOKS
+    uint32_t hash_and, hash_or;   // key_hash returns (h & hash_and) | hash_or: placement chosen by a test, never what a search returns
+#endif
 };
 
 // global counters (one per engine), bumped with one atomic per wave per event
@@ -89,7 +92,9 @@ __device__ __forceinline__ void wave_mem_sync() { __builtin_amdgcn_fence(__ATOMI
 __device__ __forceinline__ uint8_t* node_ptr(const Tree& t, uint32_t idx) { return t.nodes + (size_t)idx * NODE_BYTES; }
 
 // 32-bit hash of the 64-byte record held as one dword per lane (lanes 0..15 significant)
-__device__ __forceinline__ uint32_t key_hash(uint32_t kd)
+// (libazr_hip_test.so: the tree's hash_and / hash_or squeeze the value first — colliding tags, one start slot, chains that wrap —
+//  so that the table's probing is exercised; placement must never change what a search returns)
+__device__ __forceinline__ uint32_t key_hash(const Tree& t, uint32_t kd)
 {
     uint32_t l = lane_id() & 15u;
     uint32_t x = kd * 0x9E3779B1u + (l + 1u) * 0x85EBCA77u;
@@ -99,6 +104,11 @@ __device__ __forceinline__ uint32_t key_hash(uint32_t kd)
     // the butterfly above is order-sensitive per lane; fold to one uniform value
     uint32_t h = rfl(x);
     h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+#ifdef AZR_TEST_HOOKS
+    h = (h & t.hash_and) | t.hash_or;
+#else
+    (void)t;
+#endif
     return h == 0 ? 1u : h;
 }
 

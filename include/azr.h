@@ -70,7 +70,10 @@ typedef struct azr_settings {
     float hp_exploration;          /* HP_EXPLORATION (--hp) */
     float dir_noise_value;         /* DIR_NOISE_VALUE (--dnv) */
     float dir_noise_epsi;          /* DIR_NOISE_EPSI (--dne) */
-    int32_t node_capacity;         /* tree nodes per game; 0 = 16 * (mcts_simulations + 1) */
+    int32_t node_capacity;         /* tree nodes per game; 0 = 16 * (mcts_simulations + 1); at least 8 are allocated.  A full pool
+                                      never stops a search: a leaf that finds it full is not stored (its value is still backed up,
+                                      and a later descent asks for it again); a ROOT that finds it full after the trim empties the
+                                      tree, as clearNodes does, and is placed.  Both are counted in nodes_dropped. */
     int32_t sample_capacity;       /* (s,pi,z) records buffered per game before a drain; 0 = 4096 */
 } azr_settings;
 
@@ -375,7 +378,8 @@ typedef struct azr_counters {
     uint64_t decisions;     /* moves played */
     uint64_t games_finished;
     uint64_t samples;       /* records produced */
-    uint64_t nodes_dropped; /* expansions skipped because the node pool was full (should be 0) */
+    uint64_t nodes_dropped; /* expansions skipped because the node pool was full, plus the nodes evicted when a root expansion found
+                               it full and emptied the tree (should be 0) */
     uint64_t errors;        /* games stopped on a rules error (should be 0) */
     uint64_t records_dropped; /* records lost because a game outgrew sample_capacity or the ring was full (should be 0;
                                  `samples` counts them too) */

@@ -1240,7 +1240,9 @@ struct orc_mcts {
     orc_settings cfg;
     orc_node* nodes;
     int count, cap;
+    int limit;            /* orc_mcts_set_node_limit: nodes the store may hold (0 = unbounded) */
     uint64_t sims, evals, levels, dup_dropped;
+    uint64_t node_dropped, evictions; /* nodes not stored or evicted under the limit; times a full store was emptied for a root */
     orc_thread* th;
 };
 
@@ -1262,6 +1264,9 @@ int orc_mcts_node_count(const orc_mcts* m) { return m->count; }
 uint64_t orc_mcts_sim_count(const orc_mcts* m) { return m->sims; }
 uint64_t orc_mcts_eval_count(const orc_mcts* m) { return m->evals; }
 uint64_t orc_mcts_level_count(const orc_mcts* m) { return m->levels; }
+void orc_mcts_set_node_limit(orc_mcts* m, int limit) { m->limit = limit > 0 ? limit : 0; }
+uint64_t orc_mcts_node_dropped(const orc_mcts* m) { return m->node_dropped; }
+uint64_t orc_mcts_eviction_count(const orc_mcts* m) { return m->evictions; }
 
 /* StateSimulationsStorage::trimNodes (:229-245) */
 void orc_mcts_trim(orc_mcts* m)
@@ -1288,6 +1293,10 @@ static int find_node(const orc_mcts* m, const orc_state* s)
 /* StateSimulations ctor (:26-42) + store.add (:203-215) */
 static int add_node(orc_mcts* m, const orc_state* s, const float* pi, float value, uint64_t valid)
 {
+    if (m->limit && m->count >= m->limit) { /* node limit (a): nothing is stored, the caller still backs the value up */
+        m->node_dropped++;
+        return -1;
+    }
     if (m->count == m->cap) {
         m->cap *= 2;
         m->nodes = (orc_node*)realloc(m->nodes, sizeof(orc_node) * (size_t)m->cap);
@@ -1408,6 +1417,11 @@ int orc_mcts_simulate(orc_mcts* m, const orc_state* root, orc_rng* r, orc_eval_f
     orc_mcts_trim(m);
     if (find_node(m, root) < 0) {
         float v;
+        if (m->limit && m->count >= m->limit) { /* node limit (b): a full store is emptied for the root, as by clearNodes */
+            m->node_dropped += (uint64_t)m->count;
+            m->evictions++;
+            m->count = 0;
+        }
         expand_leaf(m, root, orc_valid_moves(root, &m->cfg), eval, ctx, &v);
     }
     const int count = m->cfg.mcts_simulations - m->cfg.mcts_simulations % T;

@@ -140,6 +140,15 @@ uint64_t orc_mcts_sim_count(const orc_mcts* m);   /* completed search() descents
 uint64_t orc_mcts_eval_count(const orc_mcts* m);  /* net evaluations (leaf + root) */
 uint64_t orc_mcts_level_count(const orc_mcts* m); /* inner-node levels visited (for mean depth) */
 uint64_t orc_mcts_dup_count(const orc_mcts* m);   /* duplicatedStatesDropped (T > 1 only) */
+/* A bounded store, the engine's node pool (include/azr.h node_capacity / nodes_dropped) restated.  limit = 0: unbounded (the default).
+ *   (a) A leaf that would become node limit + 1 is not stored and counts 1; its value is still backed up along the path, and a later
+ *       descent that reaches the state finds it missing and asks for it again.
+ *   (b) In orc_mcts_simulate, after the trim: a root that is missing while the store holds `limit` survivors drops all of them as
+ *       orc_mcts_clear does, counts each, and is then expanded into the empty store.
+ * A limit that is never reached changes nothing. */
+void orc_mcts_set_node_limit(orc_mcts* m, int limit);
+uint64_t orc_mcts_node_dropped(const orc_mcts* m);    /* nodes not stored (a) or evicted (b) */
+uint64_t orc_mcts_eviction_count(const orc_mcts* m);  /* how many times (b) happened */
 
 /* one self-play game as alphazero_trainer.cpp:80-119; records are the 265-byte on-disk layout.
  * Returns number of records written (<= cap) or -1 on error. */

@@ -95,7 +95,10 @@ def oracle():
         L.orc_mcts_policy.argtypes = [C.c_void_p] * 3
         L.orc_pick_highest.argtypes = [C.c_void_p]
         L.orc_pick_random.argtypes = [C.c_void_p, C.c_void_p]
-        for f in ("orc_mcts_sim_count", "orc_mcts_eval_count", "orc_mcts_level_count"):
+        L.orc_mcts_set_node_limit.argtypes = [C.c_void_p, C.c_int]
+        L.orc_mcts_set_node_limit.restype = None
+        for f in ("orc_mcts_sim_count", "orc_mcts_eval_count", "orc_mcts_level_count", "orc_mcts_node_dropped",
+                  "orc_mcts_eviction_count"):
             getattr(L, f).restype = C.c_uint64
             getattr(L, f).argtypes = [C.c_void_p]
         L.orc_selfplay_game.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -321,3 +324,131 @@ def ref_play_games(kind0, kind1, games, mirror, seed):
     rc = L.ref_play_games(kind0, kind1, games, int(mirror), seed, r6, ptr(st), ptr(fin), ptr(rd), C.byref(rs))
     assert rc == 0, L.ref_last_error()
     return tuple(r6), st, rd, fin, rs.value
+
+
+# ---- tree storage: recorded oracle searches over the golden roots, and the host-stepped engine compared with them --------------------
+TREE_DECISIONS = 6
+
+
+def tree_roots(stride=1):
+    """every 29th golden state (all phases), or every `stride`-th of those, with the tests' RNG seeds"""
+    gold = np.load(os.path.join(GOLDEN, "rules_games.npz"))
+    states = gold["states"][::29][:96][::stride].copy()
+    return states, np.arange(500, 500 + len(states), dtype=np.uint32)
+
+
+def lowest_unvisited(valid, n):
+    """the lowest legal move the search never tried, or None"""
+    for i in range(43):
+        if (int(valid) >> i) & 1 and n[i] == 0:
+            return i
+    return None
+
+
+_tree_runs = {}
+
+
+def orc_tree_run(sims, threads, limit=0, unvisited=False, stride=1):
+    """TREE_DECISIONS decisions per golden root in the oracle (orc_hash_eval, sampling on odd steps) with a node limit (0 = none),
+    recorded per decision: N, Q, P, policy, the picked move, the move played, the next state and the RNG.  `unvisited`: the move
+    played is the lowest legal one with N == 0 where there is one (its outcome is a root the search never expanded).  Computed once
+    per setting and shared; callers must not write into it."""
+    key = (sims, threads, limit, unvisited, stride)
+    if key in _tree_runs:
+        return _tree_runs[key]
+    L = oracle()
+    states, seeds = tree_roots(stride)
+    G = len(states)
+    cfg = default_settings(mcts_simulations=sims, mcts_threads=threads)
+    evalfn = C.cast(L.orc_hash_eval, C.c_void_p)
+    D = TREE_DECISIONS
+    run = dict(sims=sims, threads=threads, limit=limit, unvisited=unvisited, stride=stride, G=G,
+               alive=np.zeros((D, G), bool), n=np.zeros((D, G, 43), np.uint32), q=np.zeros((D, G, 43), np.float32),
+               p=np.zeros((D, G, 43), np.float32), pi=np.zeros((D, G, 43), np.float32), picked=np.full((D, G), 255, np.uint8),
+               played=np.full((D, G), 255, np.uint8), after=np.zeros((D, G, 160), np.uint8), rng=np.zeros((D, G), np.uint32),
+               peak=0, dropped=0, evictions=0, sims_per_search=set())
+    for g in range(G):
+        s, r = OrcState(), OrcRng()
+        L.orc_state_unpack(C.byref(s), ptr(states[g]))
+        r.x = int(seeds[g])
+        m = L.orc_mcts_create(C.byref(cfg))
+        L.orc_mcts_set_node_limit(m, limit)
+        for step in range(D):
+            if L.orc_game_status(C.byref(s), C.byref(cfg)) == -1:
+                run["alive"][step, g] = True
+                before = L.orc_mcts_sim_count(m)
+                assert L.orc_mcts_simulate(m, C.byref(s), C.byref(r), evalfn, None) == 0
+                run["sims_per_search"].add(L.orc_mcts_sim_count(m) - before)
+                run["peak"] = max(run["peak"], L.orc_mcts_node_count(m))
+                assert L.orc_mcts_root_stats(m, C.byref(s), ptr(run["n"][step, g]), ptr(run["q"][step, g]), ptr(run["p"][step, g]), None) == 0
+                assert L.orc_mcts_policy(m, C.byref(s), ptr(run["pi"][step, g])) == 0
+                pi = run["pi"][step, g]
+                mv = L.orc_pick_random(ptr(pi), C.byref(r)) if step % 2 == 1 else L.orc_pick_highest(ptr(pi))
+                run["picked"][step, g] = mv
+                if unvisited:
+                    u = lowest_unvisited(L.orc_valid_moves(C.byref(s), C.byref(cfg)), run["n"][step, g])
+                    mv = mv if u is None else u
+                run["played"][step, g] = mv
+                assert L.orc_make_move(C.byref(s), mv, C.byref(r), C.byref(cfg)) == 0
+            L.orc_state_pack(C.byref(s), ptr(run["after"][step, g]))
+            run["rng"][step, g] = r.x
+        run["dropped"] += L.orc_mcts_node_dropped(m)
+        run["evictions"] += L.orc_mcts_eviction_count(m)
+        L.orc_mcts_destroy(m)
+    _tree_runs[key] = run
+    return run
+
+
+def engine_stub_search(eng, stub, max_passes):
+    """one host-stepped search with the NN seam served by an oracle stub net; at most max_passes passes (a pass retires at least one
+    claimed descent, or the root expansion, per live game: a search that needs more is stuck)"""
+    eng.mcts_begin()
+    pi = np.zeros((eng.G * eng.T, 43), np.float32)     # leaf slot = game * T + search thread
+    v = np.zeros(eng.G * eng.T, np.float32)
+    vv = C.c_float(0)
+    for _ in range(max_passes + 1):
+        x, need, active = eng.mcts_leaves()
+        if active == 0:
+            return
+        for g in np.nonzero(need)[0]:
+            stub(None, x[g].ctypes.data_as(u8p), pi[g].ctypes.data_as(f32p), C.byref(vv))
+            v[g] = vv.value
+        eng.mcts_apply(pi, v)
+    raise AssertionError(f"the search did not finish in {max_passes} passes")
+
+
+def engine_matches_tree_run(eng, run):
+    """plays the recorded decisions on the engine (host-stepped, orc_hash_eval) and compares N, Q, P, the policy, the picked move, the
+    next state and the RNG with the oracle's, bit for bit, per decision and game"""
+    L = oracle()
+    stub = L.orc_hash_eval
+    stub.argtypes = [C.c_void_p, u8p, f32p, C.c_void_p]
+    states, seeds = tree_roots(run["stride"])
+    G = run["G"]
+    assert eng.G == G and eng.T == run["threads"]
+    eng.set_states(states)
+    eng.set_rng(seeds)
+    for step in range(TREE_DECISIONS):
+        status = eng.status()
+        assert ((status == -1) == run["alive"][step]).all(), step
+        engine_stub_search(eng, stub, run["sims"] + 8)
+        n_gpu, q_gpu, p_gpu = eng.root_stats()
+        pi_gpu = eng.policy()
+        valid = eng.valid_moves()
+        moves = eng.pick(sample=step % 2 == 1)
+        for g in np.nonzero(status == -1)[0]:
+            assert (run["n"][step, g] == n_gpu[g]).all(), (step, g, run["n"][step, g], n_gpu[g])
+            assert (run["q"][step, g].view(np.uint32) == q_gpu[g].view(np.uint32)).all(), (step, g)
+            assert (run["p"][step, g].view(np.uint32) == p_gpu[g].view(np.uint32)).all(), (step, g)
+            assert (run["pi"][step, g].view(np.uint32) == pi_gpu[g].view(np.uint32)).all(), (step, g)
+            assert run["picked"][step, g] == moves[g], (step, g)
+            if run["unvisited"]:
+                u = lowest_unvisited(valid[g], n_gpu[g])
+                moves[g] = moves[g] if u is None else u
+            assert run["played"][step, g] == moves[g], (step, g)
+        moves[status != -1] = 255
+        assert (eng.make_moves(moves) == 0).all()
+        after, rng_after = eng.get_states(), eng.get_rng()
+        for g in np.nonzero(status == -1)[0]:
+            assert (run["after"][step, g] == after[g]).all(), (step, g)
+            assert run["rng"][step, g] == rng_after[g], (step, g)

@@ -137,6 +137,9 @@ def test_node_pool_exhaustion_is_counted_not_fatal():
     c = eng.counters()
     assert c["nodes_dropped"] > 0 and c["errors"] == 0
     assert c["decisions"] >= G
+    # at T = 1 a pass is one evaluation per slot, and an evaluation that is not a simulation is a root expansion: at most one per
+    # decision taken plus the one in progress.  A slot whose root expansion is dropped pass after pass adds one per pass.
+    assert c["evaluations"] - c["simulations"] <= c["decisions"] + G, c
     eng.close()
 
 
