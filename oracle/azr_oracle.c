@@ -1803,8 +1803,25 @@ static int pick_random_move(orc_rng* r, uint64_t moves, uint64_t* out)
     return ORC_OK;
 }
 
+/* optional (s, pi, player) log of the running game's decisions: AlphaZeroPlayer's (alphazero_player.cpp:15-18) and, with `scripted`
+ * set, RandomPlayer's one-hot ones at its addTrainingSample sites (player/base/player.cpp:9-17) */
+typedef struct { uint8_t* rec; int cap, n, game_start, scripted; } orc_reclog;
+
+static void log_one_hot(orc_reclog* log, const orc_state* s, int move)
+{
+    if (!log || !log->rec || !log->scripted || log->n >= log->cap) return;
+    uint8_t* d = log->rec + (size_t)log->n * 265;
+    float pi[ORC_MOVES] = {0};
+    pi[move] = 1.0f;
+    d[0] = (uint8_t)s->cur;
+    orc_encode(s, d + 1);
+    memset(d + 89, 0, 4);
+    memcpy(d + 93, pi, sizeof pi);
+    log->n++;
+}
+
 /* RandomPlayer::takeTurn (random_player.cpp:22-111) */
-int orc_random_take_turn(orc_state* s, int me, orc_rng* r, const orc_settings* cfg)
+static int random_take_turn(orc_state* s, int me, orc_rng* r, const orc_settings* cfg, orc_reclog* log)
 {
     while (orc_game_status(s, cfg) == ORC_NOT_ENDED && s->cur == me) {
         const orc_player* ps = &s->ps[s->cur];
@@ -1812,16 +1829,20 @@ int orc_random_take_turn(orc_state* s, int me, orc_rng* r, const orc_settings* c
         uint64_t mv;
         if (s->phase == ORC_SETUP) {
             TRY(pick_random_move(r, ps->owned, &mv));
+            log_one_hot(log, s, ctz(mv)); /* :29 */
             TRY(setup_reinforcement_move(s, ctz(mv)));
         } else if (s->phase == ORC_SETUP_NEUTRAL) {
             TRY(pick_random_move(r, ALL_LANDS & ~ps->owned & ~eps->owned, &mv));
+            log_one_hot(log, s, ctz(mv)); /* :35 */
             TRY(setup_reinforcement_neutral_move(s, ctz(mv)));
         } else if (s->phase == ORC_REINFORCEMENT) {
             play_cards(s);
             TRY(pick_random_move(r, ps->owned & ~ps->owned_full, &mv));
+            log_one_hot(log, s, ctz(mv)); /* :43 */
             TRY(reinforcement_move(s, 1, ctz(mv)));
         } else if (s->phase == ORC_ATTACK) {
             TRY(pick_random_move(r, ps->attack_army | SKIP_MASK, &mv));
+            log_one_hot(log, s, ctz(mv)); /* :49 (the attack-from pick is not recorded) */
             if ((SKIP_MASK & mv) > 0) { TRY(goto_fortify(s)); }
             else {
                 int to = ctz(mv);
@@ -1833,10 +1854,15 @@ int orc_random_take_turn(orc_state* s, int me, orc_rng* r, const orc_settings* c
             if (orc_rng_float(r) > 0.5f) {
                 int v = (int)s->army[s->mob_from] - 1;
                 uint8_t amount = (uint8_t)(v < cfg->min_unit_move ? v : cfg->min_unit_move);
+                log_one_hot(log, s, s->mob_to); /* :68 */
                 TRY(attack_reinforcement_move(s, amount));
-            } else { TRY(goto_attack(s)); }
+            } else {
+                log_one_hot(log, s, s->mob_from); /* :73 */
+                TRY(goto_attack(s));
+            }
         } else if (s->phase == ORC_FORTIFY) {
             TRY(pick_random_move(r, (ps->owned & ~ps->owned_full) | SKIP_MASK, &mv));
+            log_one_hot(log, s, ctz(mv)); /* :82 */
             if (mv != SKIP_MASK) {
                 int to = ctz(mv);
                 orc_lsm comps[ORC_LANDS];
@@ -1864,10 +1890,9 @@ int orc_random_take_turn(orc_state* s, int me, orc_rng* r, const orc_settings* c
     return ORC_OK;
 }
 
-/* AlphaZeroPlayer::takeTurn (alphazero_player.cpp:3-21) at one search thread */
-/* optional (s, pi, player) log of the AlphaZero decisions of the running game (alphazero_player.cpp:15-18) */
-typedef struct { uint8_t* rec; int cap, n, game_start; } orc_reclog;
+int orc_random_take_turn(orc_state* s, int me, orc_rng* r, const orc_settings* cfg) { return random_take_turn(s, me, r, cfg, NULL); }
 
+/* AlphaZeroPlayer::takeTurn (alphazero_player.cpp:3-21) at one search thread */
 static int az_take_turn(orc_mcts* m, orc_state* s, int me, orc_rng* r, const orc_settings* cfg, orc_eval_fn eval, void* ctx,
                         orc_reclog* log)
 {
@@ -1925,7 +1950,7 @@ static int play_out(orc_table* t, orc_state* s, orc_rng* r, int player_start, in
         int cur = s->cur;
         int setup = s->phase == ORC_SETUP;
         if (t->kind[cur] == 1) rc = orc_script_take_turn(&t->sp[cur], s, r, cfg);
-        else if (t->kind[cur] == 2) rc = orc_random_take_turn(s, cur, r, cfg);
+        else if (t->kind[cur] == 2) rc = random_take_turn(s, cur, r, cfg, &t->log);
         else if (t->kind[cur] == 3) rc = az_take_turn(t->mc[cur], s, cur, r, cfg, t->eval_b, t->ctx_b, &t->log);
         else rc = az_take_turn(t->mc[cur], s, cur, r, cfg, t->eval, t->ctx, &t->log);
         if (rc) break;
@@ -1955,7 +1980,7 @@ static void table_open(orc_table* t, const orc_settings* cfg, int kind0, int kin
     t->cfg = cfg;
     t->kind[0] = kind0; t->kind[1] = kind1;
     t->eval = eval; t->ctx = ctx; t->eval_b = eval_b; t->ctx_b = ctx_b;
-    t->log.rec = rec265; t->log.cap = rec_cap; t->log.n = 0; t->log.game_start = 0;
+    t->log.rec = rec265; t->log.cap = rec_cap; t->log.n = 0; t->log.game_start = 0; t->log.scripted = 0;
     for (int p = 0; p < 2; p++) {
         orc_script_init(&t->sp[p]);
         t->mc[p] = (t->kind[p] == 0 || t->kind[p] == 3) ? orc_mcts_create(cfg) : NULL;
@@ -1968,22 +1993,32 @@ static void table_close(orc_table* t)
         if (t->mc[p]) orc_mcts_destroy(t->mc[p]);
 }
 
-/* the same with kind 3 = an AlphaZero player on a second network (eval_b) — GameGroup::playGames(trainAZPG,
- * generateAZPG, ...) of the trainer — and optionally the 265-byte (s, pi, z) records of the AlphaZero decisions, game
- * by game in decision order, z filled in when the game ends (NNTrainDataStorage::updateValues) */
-int orc_play_games2(const orc_settings* cfg, int kind0, int kind1, int games, int mirror, uint32_t seed,
-                    orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
-                    uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end)
+/* What a series does with a game that stopped (rc != ORC_OK out of play_out).  drop == NULL: the reference's way, the exception
+ * leaves GameGroup and the series ends with its error class.  drop != NULL: the engine's way (azr_oracle.h, "a stopped game"). */
+static void drop_game(orc_table* t, orc_drop* d, int rc)
+{
+    d->stops++;
+    d->last_error = rc;
+    t->log.n = t->log.game_start; /* the stopped game's staged records go with it */
+}
+
+static int series_sequential(const orc_settings* cfg, int kind0, int kind1, int games, int mirror, uint32_t seed,
+                             orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
+                             uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end,
+                             int out_cap, orc_drop* drop)
 {
     orc_table t;
     table_open(&t, cfg, kind0, kind1, eval, ctx, eval_b, ctx_b, rec265, rec_cap);
+    t.log.scripted = drop && drop->scripted;
     orc_rng r;
     orc_rng_seed(&r, seed);
     memset(res, 0, sizeof *res);
     orc_state s, prev_start;
     orc_state_blank(&prev_start);
-    int player_start = 0, rc = ORC_OK;
-    for (int gi = 0; gi < games && rc == ORC_OK; gi++) {
+    int player_start = 0, pair_phase = 0, rc = ORC_OK, gi = 0;
+    for (;;) {
+        /* without drops: `games` games; with them the engine's test, the per-slot cap looked at before a pair only */
+        if (drop ? (pair_phase == 0 && gi >= games) : gi >= games) break;
         if (mirror && player_start != 0) {
             s = prev_start;
             orc_invert_players(&s);
@@ -1993,27 +2028,36 @@ int orc_play_games2(const orc_settings* cfg, int kind0, int kind1, int games, in
             s.cur = (int8_t)player_start;
             prev_start = s;
         }
-        rc = play_out(&t, &s, &r, player_start, gi, res, status_out, finals160, rounds_out, rec_game_end);
+        const int keep = gi < out_cap;
+        rc = play_out(&t, &s, &r, player_start, gi, res, keep ? status_out : NULL, keep ? finals160 : NULL, keep ? rounds_out : NULL,
+                      keep ? rec_game_end : NULL);
+        if (rc) {
+            if (!drop) break;
+            drop_game(&t, drop, rc);
+            rc = ORC_OK;
+            player_start = 0; pair_phase = 0; /* a fresh pair: a new deal, player 0 starts */
+            if (drop->stops >= drop->max_stops) { rc = ORC_LOGIC_ERROR; break; }
+            continue;
+        }
+        gi++;
         player_start = (player_start + 1) % 2;
+        pair_phase ^= 1;
     }
     table_close(&t);
     res->rng_state = r.x;
     if (rec_n) *rec_n = t.log.n;
+    if (drop) drop->games = gi;
     return rc;
 }
 
-/* One SLOT of the concurrent-halves form of a mirrored arena (include/azr.h, AZR_MIRROR_CONCURRENT): the two games of a pair are
- * played at the same time by two tables — nothing in Game orders them (game.cpp:238-254), they only share the deal
- * (game.cpp:170-191).  This slot plays half `half` of the pairs pair_seed0, pair_seed0 + pair_stride, ...: the deal of pair seed q
- * comes from minstd_rand0(q); half 0 (player 0 starts) goes on with that stream, half 1 plays invertPlayers of the deal with
- * player 1 starting and draws from minstd_rand0(q + 2^30).  Players (and a ScriptPlayer's memory) persist over the slot's games
- * as they do over a reference thread's. */
-int orc_play_half_games(const orc_settings* cfg, int kind0, int kind1, int games, int half, uint32_t pair_seed0, uint32_t pair_stride,
-                        orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
-                        uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end)
+static int series_halves(const orc_settings* cfg, int kind0, int kind1, int games, int half, uint32_t pair_seed0, uint32_t pair_stride,
+                         orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
+                         uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end,
+                         orc_drop* drop)
 {
     orc_table t;
     table_open(&t, cfg, kind0, kind1, eval, ctx, eval_b, ctx_b, rec265, rec_cap);
+    t.log.scripted = drop && drop->scripted;
     memset(res, 0, sizeof *res);
     orc_rng r;
     r.x = 0;
@@ -2029,9 +2073,61 @@ int orc_play_half_games(const orc_settings* cfg, int kind0, int kind1, int games
         }
         s.cur = (int8_t)half;
         rc = play_out(&t, &s, &r, half, gi, res, status_out, finals160, rounds_out, rec_game_end);
+        if (rc && drop) { /* the slot goes on with its next pair; the log keeps the pair's place */
+            drop_game(&t, drop, rc);
+            rc = ORC_OK;
+            if (status_out) status_out[gi] = ORC_STOPPED;
+            if (rec_game_end) rec_game_end[gi] = t.log.n;
+        }
     }
     table_close(&t);
     res->rng_state = r.x;
     if (rec_n) *rec_n = t.log.n;
+    if (drop) drop->games = games;
     return rc;
+}
+
+/* the same with kind 3 = an AlphaZero player on a second network (eval_b) — GameGroup::playGames(trainAZPG,
+ * generateAZPG, ...) of the trainer — and optionally the 265-byte (s, pi, z) records of the AlphaZero decisions, game
+ * by game in decision order, z filled in when the game ends (NNTrainDataStorage::updateValues) */
+int orc_play_games2(const orc_settings* cfg, int kind0, int kind1, int games, int mirror, uint32_t seed,
+                    orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
+                    uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end)
+{
+    return series_sequential(cfg, kind0, kind1, games, mirror, seed, eval, ctx, eval_b, ctx_b, res, status_out, finals160, rounds_out,
+                             rec265, rec_cap, rec_n, rec_game_end, games, NULL);
+}
+
+int orc_play_games2_drop(const orc_settings* cfg, int kind0, int kind1, int slot_cap, int mirror, uint32_t seed,
+                         orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
+                         uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end,
+                         int out_cap, orc_drop* drop)
+{
+    drop->stops = 0; drop->last_error = ORC_OK; drop->games = 0;
+    return series_sequential(cfg, kind0, kind1, slot_cap, mirror, seed, eval, ctx, eval_b, ctx_b, res, status_out, finals160, rounds_out,
+                             rec265, rec_cap, rec_n, rec_game_end, out_cap, drop);
+}
+
+/* One SLOT of the concurrent-halves form of a mirrored arena (include/azr.h, AZR_MIRROR_CONCURRENT): the two games of a pair are
+ * played at the same time by two tables — nothing in Game orders them (game.cpp:238-254), they only share the deal
+ * (game.cpp:170-191).  This slot plays half `half` of the pairs pair_seed0, pair_seed0 + pair_stride, ...: the deal of pair seed q
+ * comes from minstd_rand0(q); half 0 (player 0 starts) goes on with that stream, half 1 plays invertPlayers of the deal with
+ * player 1 starting and draws from minstd_rand0(q + 2^30).  Players (and a ScriptPlayer's memory) persist over the slot's games
+ * as they do over a reference thread's. */
+int orc_play_half_games(const orc_settings* cfg, int kind0, int kind1, int games, int half, uint32_t pair_seed0, uint32_t pair_stride,
+                        orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
+                        uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end)
+{
+    return series_halves(cfg, kind0, kind1, games, half, pair_seed0, pair_stride, eval, ctx, eval_b, ctx_b, res, status_out, finals160,
+                         rounds_out, rec265, rec_cap, rec_n, rec_game_end, NULL);
+}
+
+int orc_play_half_games_drop(const orc_settings* cfg, int kind0, int kind1, int games, int half, uint32_t pair_seed0,
+                             uint32_t pair_stride, orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res,
+                             int8_t* status_out, uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n,
+                             int* rec_game_end, orc_drop* drop)
+{
+    drop->stops = 0; drop->last_error = ORC_OK; drop->games = 0;
+    return series_halves(cfg, kind0, kind1, games, half, pair_seed0, pair_stride, eval, ctx, eval_b, ctx_b, res, status_out, finals160,
+                         rounds_out, rec265, rec_cap, rec_n, rec_game_end, drop);
 }

@@ -186,6 +186,36 @@ int orc_play_half_games(const orc_settings* cfg, int kind0, int kind1, int games
                         orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
                         uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end);
 
+/* ---- a stopped game ----
+ * A game stops when a player's turn ends in an error class (the reference throws out of GameGroup::playGames and the whole run ends;
+ * e.g. RandomPlayer::pickRandomMove on the empty set: reinforcement with every owned land full).  orc_play_games2 and
+ * orc_play_half_games end there and return the class.  The engine's arena drops the game and goes on (azr_arena.hpp, `if (fail)`), and
+ * the _drop forms restate exactly that:
+ *   - the stopped game is counted in no result number and gets no entry in the per-slot log; drop->stops counts it and
+ *     drop->last_error holds its error class;
+ *   - the slot's RNG stream goes on from where the stop left it (every draw of the broken turn stays drawn);
+ *   - the players persist: a ScriptPlayer keeps its memory, an AlphaZero player's tree is cleared by the next game's newGame;
+ *   - the records the stopped game had staged are gone (rec_n and rec_game_end count finished games' records only);
+ *   - sequential form: the next game is a fresh deal from the slot's stream with player 0 starting, also where the stopped game was
+ *     the mirrored second of a pair.  The slot's count of finished games is compared with slot_cap before a pair only, so a slot whose
+ *     second game stopped ends with slot_cap + 1 games.  At most out_cap games are written to the per-game outputs; drop->games is the
+ *     number finished.  A slot whose every game stops never ends: after drop->max_stops stops the call returns ORC_LOGIC_ERROR;
+ *   - concurrent form: pairs are assigned statically, so the slot moves on to its next pair and the stopped pair's place in the
+ *     per-game outputs stays unused: status_out[k] = ORC_STOPPED, finals and rounds untouched, rec_game_end[k] = the count before it.
+ *     drop->games = games. */
+enum { ORC_STOPPED = -100 };
+/* in: max_stops; scripted != 0: a RandomPlayer's decisions are logged too, one-hot, at the reference's addTrainingSample sites
+ * (player/base/player.cpp:9-17; a ScriptPlayer's are not restated here).  out: stops, last_error, games */
+typedef struct { int max_stops, scripted; int stops, last_error, games; } orc_drop;
+int orc_play_games2_drop(const orc_settings* cfg, int kind0, int kind1, int slot_cap, int mirror, uint32_t seed,
+                         orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res, int8_t* status_out,
+                         uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n, int* rec_game_end,
+                         int out_cap, orc_drop* drop);
+int orc_play_half_games_drop(const orc_settings* cfg, int kind0, int kind1, int games, int half, uint32_t pair_seed0,
+                             uint32_t pair_stride, orc_eval_fn eval, void* ctx, orc_eval_fn eval_b, void* ctx_b, orc_results* res,
+                             int8_t* status_out, uint8_t* finals160, uint16_t* rounds_out, uint8_t* rec265, int rec_cap, int* rec_n,
+                             int* rec_game_end, orc_drop* drop);
+
 /* bench.py cpu_baseline: `threads` games in parallel, `decisions` decisions each, fp32 CPU net */
 int orc_bench_selfplay(const orc_settings* cfg, const orc_net* net, uint32_t base_seed, int threads, int decisions,
                        uint64_t* sims, uint64_t* evals, double* seconds);

@@ -125,6 +125,7 @@ def ref():
     if _ref is None:
         L = C.CDLL(REF_SO)
         L.ref_last_error.restype = C.c_char_p
+        L.ref_seed.argtypes = [C.c_uint32]
         L.ref_rng_float.restype = C.c_float
         L.ref_rng_state.restype = C.c_uint32
         L.ref_random_mask.restype = C.c_uint64
@@ -314,6 +315,63 @@ def orc_play_half_games(kind0, kind1, games, half, pair_seed0, pair_stride, cfg=
     return res.as_tuple(), st, rd, fin, [rec[a:b].copy() for a, b in zip([0] + list(ends[:-1]), ends)]
 
 
+class OrcDrop(C.Structure):
+    _fields_ = [("max_stops", C.c_int), ("scripted", C.c_int), ("stops", C.c_int), ("last_error", C.c_int), ("games", C.c_int)]
+
+
+ORC_STOPPED = -100
+LOG_GAMES = 16   # games per slot that the engine's arena log keeps (Engine.arena_log)
+
+
+def _drop_result(rc, res, st, rd, fin, rec, ends, d, games):
+    return dict(rc=rc, results=res.as_tuple(), rng=res.rng_state, status=st, rounds=rd, finals=fin, stops=d.stops,
+                last_error=d.last_error, games=d.games,
+                records=[rec[a:b].copy() for a, b in zip([0] + list(ends[:games - 1]), ends[:games])])
+
+
+def orc_play_games_drop(kind0, kind1, slot_cap, mirror, seed, cfg=None, scripted=False, max_stops=64, rec_cap=0):
+    """one sequential slot that goes on after a stopped game as the engine's arena does (oracle/azr_oracle.h, "a stopped game");
+    rc != 0: the slot met max_stops stops.  records: per finished game (the first LOG_GAMES), with rec_cap > 0"""
+    L = oracle()
+    cfg = cfg or default_settings()
+    res, d = OrcResults(), OrcDrop(max_stops=max_stops, scripted=int(scripted))
+    st = np.zeros(LOG_GAMES, np.int8)
+    fin = np.zeros((LOG_GAMES, 160), np.uint8)
+    rd = np.zeros(LOG_GAMES, np.uint16)
+    rec = np.zeros((max(rec_cap, 1), 265), np.uint8)
+    n = C.c_int(0)
+    ends = np.zeros(LOG_GAMES, np.int32)
+    L.orc_play_games2_drop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32] + [C.c_void_p] * 9 + [
+        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    rc = L.orc_play_games2_drop(C.byref(cfg), kind0, kind1, slot_cap, int(mirror), seed, None, None, None, None, C.byref(res), ptr(st),
+                                ptr(fin), ptr(rd), ptr(rec) if rec_cap else None, rec_cap, C.byref(n), ptr(ends), LOG_GAMES, C.byref(d))
+    out = _drop_result(rc, res, st, rd, fin, rec, ends, d, min(d.games, LOG_GAMES))
+    out["nrec"] = n.value
+    return out
+
+
+def orc_play_half_games_drop(kind0, kind1, games, half, pair_seed0, pair_stride, cfg=None, scripted=False, rec_cap=0):
+    """one slot of the concurrent-halves arena that goes on after a stopped game: status[k] = ORC_STOPPED marks a stopped pair, whose
+    place in rounds / finals stays unused and whose record list is empty"""
+    L = oracle()
+    cfg = cfg or default_settings()
+    res, d = OrcResults(), OrcDrop(max_stops=0, scripted=int(scripted))
+    st = np.zeros(games, np.int8)
+    fin = np.zeros((games, 160), np.uint8)
+    rd = np.zeros(games, np.uint16)
+    rec = np.zeros((max(rec_cap, 1), 265), np.uint8)
+    n = C.c_int(0)
+    ends = np.zeros(games, np.int32)
+    L.orc_play_half_games_drop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 9 + [
+        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.orc_play_half_games_drop(C.byref(cfg), kind0, kind1, games, half, pair_seed0, pair_stride, None, None, None, None,
+                                    C.byref(res), ptr(st), ptr(fin), ptr(rd), ptr(rec) if rec_cap else None, rec_cap, C.byref(n),
+                                    ptr(ends), C.byref(d))
+    out = _drop_result(rc, res, st, rd, fin, rec, ends, d, games)
+    out["nrec"] = n.value
+    return out
+
+
 def ref_play_games(kind0, kind1, games, mirror, seed):
     L = ref()
     r6 = (C.c_int * 6)()
@@ -452,3 +510,18 @@ def engine_matches_tree_run(eng, run):
         for g in np.nonzero(status == -1)[0]:
             assert (run["after"][step, g] == after[g]).all(), (step, g)
             assert run["rng"][step, g] == rng_after[g], (step, g)
+
+
+# ---- RNG states that play does not reach --------------------------------------------------------------------------------------------
+RNG_M, RNG_A = 2147483647, 16807
+
+
+def rng_step_back(x):
+    """the minstd_rand0 state before x"""
+    return x * pow(RNG_A, -1, RNG_M) % RNG_M
+
+
+# the raw values a die throws away (the top of the range, past the last multiple of 6) and the ones rng_float rounds up to 1.0f and
+# clamps, as the states whose NEXT draw is that value
+RNG_DIE_REJECT = [rng_step_back(y) for y in range(2147483641, 2147483647)]
+RNG_FLOAT_CLAMP = [rng_step_back(y) for y in range(2147483585, 2147483647)]

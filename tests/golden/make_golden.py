@@ -3,14 +3,15 @@
 
 Run in the build container only (needs /root/reference to have been compiled by `make -C oracle ref`):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [fixture.npz ...]      (no argument: all of them)
 
 The fixtures are data only: inputs (seeds, state byte images, masks, priors) and the reference's
 outputs for them.  Struct padding bytes of the 160-byte `Data` image are zeroed so the files are
 deterministic.  What each file pins:
 
   tables.npz        a1/a6   adjacency lists (order!), neighbour masks, continent masks, bonuses
-  rng_kat.npz       a11     minstd_rand0 + libstdc++ distributions: dice / int / float streams, randomMask
+  rng_kat.npz       a11     minstd_rand0 + libstdc++ distributions: dice / int / float streams, randomMask, and one die and one
+                            float from each state whose next raw value a die rejects (6) or a float clamps below 1 (62)
   rules_games.npz   a2-a10  seeded random-legal-policy games: state before each move, legal mask, move, outcome
   moves_all.npz     a5,a8,a9  every policy index 0..43 (legal AND illegal) applied to sampled states with a
                             fixed dice seed: error class (0 ok / 1 invalid_argument / 2 logic_error) + next state
@@ -28,6 +29,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import azr_testlib as T  # noqa: E402
 import ctypes as C  # noqa: E402
+
+
+def save(name, **arrays):
+    if len(sys.argv) < 2 or name in sys.argv[1:]:
+        np.savez_compressed(os.path.join(HERE, name), **arrays)
 
 
 def main():
@@ -50,8 +56,8 @@ def main():
     rng = np.random.default_rng(7)
     reinf_in = np.concatenate([reinf_in, rng.integers(0, 1 << 42, 200, dtype=np.uint64)])
     reinf_out = np.array([R.ref_reinforcement_value(int(x)) for x in reinf_in], np.int8)
-    np.savez_compressed(os.path.join(HERE, "tables.npz"), neighbours=nb, neighbour_count=nbn, neighbour_mask=nbm,
-                        continent_mask=cont, reinf_in=reinf_in, reinf_out=reinf_out)
+    save("tables.npz", neighbours=nb, neighbour_count=nbn, neighbour_mask=nbm,
+         continent_mask=cont, reinf_in=reinf_in, reinf_out=reinf_out)
 
     # ---- rng known answers
     seeds = np.array([1, 1234, 20260001, 2147483646, 2147483647, 0, 4294967295], np.uint32)
@@ -73,8 +79,20 @@ def main():
     rm_masks = rng.integers(1, 1 << 43, 300, dtype=np.uint64)
     R.ref_seed(99)
     rm_out = np.array([R.ref_random_mask(int(m)) for m in rm_masks], np.uint64)
-    np.savez_compressed(os.path.join(HERE, "rng_kat.npz"), seeds=seeds, dice=dice, ints=ints, floats=flts,
-                        mixed_state=mixed_state, rm_seed=np.uint32(99), rm_masks=rm_masks, rm_out=rm_out)
+    # states that no stream above reaches: the next raw value is one a die throws away / a float rounds up to 1.0f and clamps
+    edge = np.array(T.RNG_DIE_REJECT + T.RNG_FLOAT_CLAMP, np.uint32)
+    edge_dice, edge_dice_after = np.zeros(len(edge), np.uint8), np.zeros(len(edge), np.uint32)
+    edge_floats, edge_floats_after = np.zeros(len(edge), np.float32), np.zeros(len(edge), np.uint32)
+    for k, x in enumerate(edge):
+        R.ref_seed(int(x))   # minstd_rand0: a seed below the modulus is the state
+        edge_dice[k] = R.ref_rng_dice()
+        edge_dice_after[k] = R.ref_rng_state()
+        R.ref_seed(int(x))
+        edge_floats[k] = R.ref_rng_float()
+        edge_floats_after[k] = R.ref_rng_state()
+    save("rng_kat.npz", seeds=seeds, dice=dice, ints=ints, floats=flts,
+         mixed_state=mixed_state, rm_seed=np.uint32(99), rm_masks=rm_masks, rm_out=rm_out, edge_states=edge,
+         edge_dice=edge_dice, edge_dice_after=edge_dice_after, edge_floats=edge_floats, edge_floats_after=edge_floats_after)
 
     # ---- seeded random-policy games
     game_seeds = np.array(list(range(1, 17)) + [1234, 20260001, 20260002, 20260003], np.uint32)
@@ -88,10 +106,10 @@ def main():
         status.append(g["status"])
         f = g["final"].copy(); f[~fm] = 0
         finals.append(f)
-    np.savez_compressed(os.path.join(HERE, "rules_games.npz"), seeds=game_seeds,
-                        states=np.concatenate(states), masks=np.concatenate(masks), moves=np.concatenate(moves),
-                        starts=np.array(starts, np.int64), status=np.array(status, np.int8),
-                        finals=np.stack(finals))
+    save("rules_games.npz", seeds=game_seeds,
+         states=np.concatenate(states), masks=np.concatenate(masks), moves=np.concatenate(moves),
+         starts=np.array(starts, np.int64), status=np.array(status, np.int8),
+         finals=np.stack(finals))
     allstates = np.concatenate(states)
 
     # ---- every move index on sampled states
@@ -106,8 +124,8 @@ def main():
             if rc[i, mv] == 0:
                 d[~fm] = 0
                 nxt[i, mv] = d
-    np.savez_compressed(os.path.join(HERE, "moves_all.npz"), states=sel, dice_seed_base=np.uint32(777), rc=rc,
-                        next=nxt)
+    save("moves_all.npz", states=sel, dice_seed_base=np.uint32(777), rc=rc,
+         next=nxt)
 
     # ---- encode
     sel = allstates[::5]
@@ -116,7 +134,7 @@ def main():
     for i, st in enumerate(sel):
         R.ref_encode(T.ptr(st), T.ptr(enc[i]))
         gstat[i] = R.ref_game_status(T.ptr(st))
-    np.savez_compressed(os.path.join(HERE, "encode.npz"), states=sel, in88=enc, status=gstat)
+    save("encode.npz", states=sel, in88=enc, status=gstat)
 
     # ---- normalize
     pri = rng.uniform(0.0, 1.0, (400, 43)).astype(np.float32)
@@ -125,7 +143,7 @@ def main():
     out = pri.copy()
     for i in range(len(out)):
         R.ref_normalize(T.ptr(out[i]), int(vm[i]))
-    np.savez_compressed(os.path.join(HERE, "normalize.npz"), priors=pri, valid=vm, out=out)
+    save("normalize.npz", priors=pri, valid=vm, out=out)
 
     # ---- update values
     pl = rng.integers(0, 2, 64).astype(np.int8)
@@ -134,8 +152,8 @@ def main():
         z = np.zeros(64, np.float32)
         R.ref_update_values(T.ptr(pl), 64, gs, 80, T.ptr(z))
         zs[f"z_{gs}"] = z
-    np.savez_compressed(os.path.join(HERE, "update_values.npz"), players=pl, z_p0=zs["z_0"], z_p1=zs["z_1"],
-                        z_draw=zs["z_-2"])
+    save("update_values.npz", players=pl, z_p0=zs["z_0"], z_p1=zs["z_1"],
+         z_draw=zs["z_-2"])
     # ---- opponents + host game driver (ScriptPlayer / RandomPlayer / Game mirrored pairs): f-1, f-3
     rows = []
     for (k0, k1) in ((1, 2), (2, 1), (1, 1), (2, 2)):
@@ -144,11 +162,11 @@ def main():
                 r6, st, rd, fin, rs = T.ref_play_games(k0, k1, 6, mirror, seed)
                 fin = fin.copy(); fin[:, ~fm] = 0
                 rows.append((k0, k1, mirror, seed, r6, st, rd, fin, rs))
-    np.savez_compressed(os.path.join(HERE, "players_games.npz"),
-                        kinds=np.array([[r[0], r[1]] for r in rows], np.int8), mirror=np.array([r[2] for r in rows], np.int8),
-                        seeds=np.array([r[3] for r in rows], np.uint32), results=np.array([r[4] for r in rows], np.int32),
-                        status=np.stack([r[5] for r in rows]), rounds=np.stack([r[6] for r in rows]),
-                        finals=np.stack([r[7] for r in rows]), rng_state=np.array([r[8] for r in rows], np.uint32))
+    save("players_games.npz",
+         kinds=np.array([[r[0], r[1]] for r in rows], np.int8), mirror=np.array([r[2] for r in rows], np.int8),
+         seeds=np.array([r[3] for r in rows], np.uint32), results=np.array([r[4] for r in rows], np.int32),
+         status=np.stack([r[5] for r in rows]), rounds=np.stack([r[6] for r in rows]),
+         finals=np.stack([r[7] for r in rows]), rng_state=np.array([r[8] for r in rows], np.uint32))
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

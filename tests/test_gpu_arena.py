@@ -7,33 +7,42 @@ import numpy as np
 import pytest
 
 import azr_testlib as T
-from gpu_common import pkg
+from gpu_common import half_slot as _half_slot, pkg, run_arena
 
 pytestmark = pytest.mark.gpu
 FM = T.data_field_mask()
 
 
-def run_arena(eng, k0, k1, total, cap, mirror, base):
-    eng.arena_start(k0, k1, total, per_slot_cap=cap, mirror=mirror, base_seed=base)
-    for _ in range(2000):
-        if eng.arena_run(64):
-            break
-    else:
-        raise AssertionError("arena did not finish")
-    return eng.arena_results(), eng.arena_log()
-
-
 @pytest.mark.parametrize("kinds", [(1, 2), (2, 1), (1, 1), (2, 2)])
 @pytest.mark.parametrize("mirror", [True, False])
 def test_script_and_random_players_arena_bit_exact(orc, kinds, mirror):
+    script_and_random_arena(kinds, mirror, 96, 6, 555)
+
+
+OFF_DEFAULTS = [dict(min_unit_move=1), dict(min_unit_move=5), dict(allow_yield=0, max_game_rounds=150)]
+
+
+@pytest.mark.parametrize("kinds", [(1, 2), (2, 1), (1, 1)])
+@pytest.mark.parametrize("kw", OFF_DEFAULTS, ids=lambda kw: ",".join(f"{k}={v}" for k, v in kw.items()))
+def test_script_and_random_players_arena_off_the_defaults(orc, kinds, kw):
+    """The same comparison under the settings these two players read: MIN_UNIT_MOVE in ScriptPlayer's reinforcement and mobilisation
+    steps and in RandomPlayer's mobilisation, and the game status of the arena loop without yield over 150 rounds.  32 slots x 4 games,
+    mirrored and not; the oracle finishes all of them without a stop.  LIMIT_REINFORCEMENT_MOVES and LIMIT_ATTACK_MOVES are left out:
+    they only shape UtilityNN::getValidMoves, which neither player calls, and the oracle's results are the same with and without them.
+    On an MI355X under 0.2 s a case."""
+    for mirror in (True, False):
+        script_and_random_arena(kinds, mirror, 32, 4, 555, **kw)
+
+
+def script_and_random_arena(kinds, mirror, G, per_slot, base, **kw):
     P = pkg()
-    G, per_slot, base = 96, 6, 555
-    eng = P.Engine(G, blocks=1, sims=1, dtype=P.NET_F32, node_capacity=64)
+    cfg = T.default_settings(**kw)
+    eng = P.Engine(G, blocks=1, sims=1, dtype=P.NET_F32, node_capacity=64, **kw)
     res, (n, st, rd, fin) = run_arena(eng, kinds[0], kinds[1], 10 ** 6, per_slot, mirror, base)
     assert (n == per_slot).all() and eng.counters()["errors"] == 0
     tot = np.zeros(6, np.int64)
     for g in range(G):
-        r6, ost, ord_, ofin, _ = T.orc_play_games(kinds[0], kinds[1], per_slot, mirror, base + g)
+        r6, ost, ord_, ofin, _ = T.orc_play_games(kinds[0], kinds[1], per_slot, mirror, base + g, cfg=cfg)
         assert (st[g, :per_slot] == ost).all(), g
         assert (rd[g, :per_slot] == ord_).all(), g
         assert (fin[g, :per_slot][:, FM] == ofin[:, FM]).all(), g
@@ -159,11 +168,6 @@ def test_two_net_arena_bit_exact_with_samples(orc, monkeypatch, threads, b_first
 
 
 # ---- AZR_MIRROR_CONCURRENT: the two games of a mirrored pair at the same time on slots 2j and 2j + 1 (include/azr.h) -------------
-def _half_slot(g, G, base):
-    """slot g of a G-slot concurrent arena = (half, first pair seed, pair stride) of tests/azr_testlib.orc_play_half_games"""
-    return g & 1, base + (g >> 1), G // 2
-
-
 @pytest.mark.parametrize("kinds", [(1, 2), (2, 1), (1, 1)])
 def test_concurrent_pair_halves_script_and_random_bit_exact(orc, kinds):
     """every slot against the oracle's slot of the same (half, pair seeds) — whose half 0 is anchored on the real reference

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import azr_testlib as T
+import rules_settings as RS
 from gpu_common import pkg
 
 pytestmark = pytest.mark.gpu
@@ -42,14 +43,28 @@ def host_stub_search(eng, orc, stub):
                                                     ("orc_hash_eval", 102, 4), ("orc_uniform_eval", 23, 3)])
 def test_search_tree_reuse_and_moves_bit_exact(orc, stub_name, sims, threads):
     """several consecutive decisions per game (tree reuse through trimNodes), positions from all phases"""
-    stub = getattr(orc, stub_name)
-    stub.argtypes = [C.c_void_p, T.u8p, T.f32p, C.c_void_p]
     gold = np.load(os.path.join(T.GOLDEN, "rules_games.npz"))
     # starting positions: every 29th golden state (setup, reinforcement, attack, mobilisation, fortify, late game)
-    states = gold["states"][::29][:96]
+    search_decisions(orc, stub_name, sims, threads, gold["states"][::29][:96], 6 if sims <= 24 else 3)
+
+
+@pytest.mark.parametrize("threads", [1, 2])
+def test_search_off_the_defaults_bit_exact(orc, threads):
+    """the same comparison with all five rule switches off their defaults (tests/rules_settings.py FIVE): the in-tree moves of the
+    tree step under them.  Roots: 48 states of the oracle's 120-round games, all phases but the setup, half of them with a full land of
+    the player to move; orc_hash_eval, 24 simulations, 4 decisions.
+    On an MI355X 0.1 s."""
+    roots = RS.search_roots(48)
+    assert len(roots) == 48 and len(set(roots[:, 149])) == 4
+    search_decisions(orc, "orc_hash_eval", 24, threads, roots, 4, **RS.FIVE)
+
+
+def search_decisions(orc, stub_name, sims, threads, states, decisions, **kw):
+    stub = getattr(orc, stub_name)
+    stub.argtypes = [C.c_void_p, T.u8p, T.f32p, C.c_void_p]
     G = len(states)
-    cfg = T.default_settings(mcts_simulations=sims, mcts_threads=threads)
-    eng = pkg().Engine(G, blocks=1, sims=sims, dtype=pkg().NET_F32, threads=threads)
+    cfg = T.default_settings(mcts_simulations=sims, mcts_threads=threads, **kw)
+    eng = pkg().Engine(G, blocks=1, sims=sims, dtype=pkg().NET_F32, threads=threads, **kw)
     eng.set_states(states)
     seeds = np.arange(500, 500 + G, dtype=np.uint32)
     eng.set_rng(seeds)
@@ -61,7 +76,6 @@ def test_search_tree_reuse_and_moves_bit_exact(orc, stub_name, sims, threads):
         S.append(s); R.append(r); M.append(orc.orc_mcts_create(C.byref(cfg)))
     evalfn = C.cast(stub, C.c_void_p)
     d = np.zeros(160, np.uint8)
-    decisions = 6 if sims <= 24 else 3
     for step in range(decisions):
         status = eng.status()
         host_stub_search(eng, orc, stub)
@@ -122,9 +136,19 @@ def test_full_selfplay_games_device_resident_vs_oracle(orc, threads):
     """the device-resident trainer loop (azr_selfplay_run: search, temperature pick, record, move, z back-fill,
     restart) against orc_selfplay_game with the DEVICE net called back for every evaluation: identical record
     streams (265-byte layout), move for move."""
-    G, sims, B = 6, 6, 1
+    selfplay_games(orc, threads, max_game_rounds=36)
+
+
+def test_full_selfplay_games_off_the_defaults_vs_oracle(orc):
+    """the same with every rule switch off its default, one search thread; without yield every game runs its 36 rounds, so two games
+    (six take 13.6 s).  On an MI355X 5.8 s; the default test beside it takes 12 s."""
+    selfplay_games(orc, 1, G=2, limit_attack=1, limit_reinforcement=0, min_unit_move=1, allow_yield=0, max_game_rounds=36)
+
+
+def selfplay_games(orc, threads, G=6, **kw):
+    sims, B = 6, 1
     P = pkg()
-    eng = P.Engine(G, blocks=B, sims=sims, dtype=P.NET_F32, max_game_rounds=36, threads=threads)
+    eng = P.Engine(G, blocks=B, sims=sims, dtype=P.NET_F32, threads=threads, **kw)
     flat = T.make_net_flat(B, seed=11, perturb_bn=True)
     eng.set_weights(flat)
     base = 4242
@@ -147,7 +171,7 @@ def test_full_selfplay_games_device_resident_vs_oracle(orc, threads):
         C.memmove(pi, p.ctypes.data, 43 * 4)
         v[0] = float(vv[0])
 
-    cfg = T.default_settings(mcts_simulations=sims, max_game_rounds=36, mcts_threads=threads)
+    cfg = T.default_settings(mcts_simulations=sims, mcts_threads=threads, **kw)
     # records of one game are contiguous in the ring; games finish in any order: match by content
     want = {}
     for g in range(G):

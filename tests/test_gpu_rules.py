@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import azr_testlib as T
+import rules_settings as RS
 from gpu_common import pkg
 
 pytestmark = pytest.mark.gpu
@@ -34,14 +35,14 @@ def test_new_games_bit_exact(orc):
     eng.close()
 
 
-def test_lockstep_random_games_vs_oracle_and_golden(orc):
-    """G games stepped to the end in lock-step; move choice = the oracle's randomMask on its own stream (exactly the
-    golden generator's policy), dice = the device's per-game minstd_rand0 stream kept aligned with the oracle's."""
-    gold = load("rules_games.npz")
-    cfg = T.default_settings()
-    seeds = np.concatenate([gold["seeds"], np.arange(3000, 3000 + 236, dtype=np.uint32)])
+def lockstep(orc, seeds, on_move=None, **kw):
+    """G games stepped to the end in lock-step under the settings kw; move choice = the oracle's randomMask on its own stream (exactly
+    the golden generator's policy), dice = the device's per-game minstd_rand0 stream kept aligned with the oracle's.  Every state
+    image, mask, status and RNG word is compared after every move.  on_move(OrcState, mask, move) sees each move before it is played.
+    Returns (move lists, final statuses, final state images, the oracle's final states)."""
+    cfg = T.default_settings(**kw)
     G = len(seeds)
-    eng = pkg().Engine(G, blocks=1, sims=1, dtype=pkg().NET_F32, node_capacity=64)
+    eng = pkg().Engine(G, blocks=1, sims=1, dtype=pkg().NET_F32, node_capacity=64, **kw)
     eng.new_games(seeds)
     S = [T.OrcState() for _ in range(G)]
     R = [T.OrcRng() for _ in range(G)]
@@ -70,6 +71,8 @@ def test_lockstep_random_games_vs_oracle_and_golden(orc):
             m = orc.orc_valid_moves(C.byref(S[g]), C.byref(cfg))
             assert m == int(vm[g]), (g, steps, hex(m), hex(int(vm[g])))
             mv = int(orc.orc_random_mask(C.byref(R[g]), m)).bit_length() - 1
+            if on_move:
+                on_move(S[g], m, mv)
             moves[g] = mv
             traj[g].append(mv)
             rng[g] = R[g].x
@@ -84,14 +87,46 @@ def test_lockstep_random_games_vs_oracle_and_golden(orc):
         assert (eng.get_rng()[moves != 255] == np.array([R[g].x for g in range(G)], np.uint32)[moves != 255]).all(), steps
         steps += 1
         assert steps < 5000
+    out = traj, eng.status(), eng.get_states(), S
+    eng.close()
+    return out
+
+
+def test_lockstep_random_games_vs_oracle_and_golden(orc):
+    """the default settings, 256 games: the golden games and 236 more"""
+    gold = load("rules_games.npz")
+    seeds = np.concatenate([gold["seeds"], np.arange(3000, 3000 + 236, dtype=np.uint32)])
+    traj, status, final, _ = lockstep(orc, seeds)
     # the first len(gold seeds) games are the golden ones: same move lists and outcomes as the REFERENCE produced
-    final = eng.get_states()
     for k in range(len(gold["seeds"])):
         lo, hi = gold["starts"][k], gold["starts"][k + 1]
         assert traj[k] == list(gold["moves"][lo:hi])
-        assert eng.status()[k] == gold["status"][k]
+        assert status[k] == gold["status"][k]
         assert (final[k][FM] == gold["finals"][k][FM]).all()
-    eng.close()
+
+
+@pytest.mark.parametrize("kw", RS.SETTINGS, ids=RS.setting_id)
+def test_lockstep_random_games_under_settings(orc, kw):
+    """The same lock-step comparison off the defaults (the oracle is pinned to the reference on these very games by
+    tests/test_oracle_vs_ref.py::test_lockstep_settings): make_move, valid_moves, status and the dice under each run-time setting, 32 games
+    from seed 3000 and the setting's extra seeds (tests/rules_settings.py).  The census of what these inputs reach is taken here, on the
+    oracle's states, and has to hold what tests/test_rules_census.py requires of the setting: a lock-step run that never met a full
+    land compares nothing of the clamps.
+    On an MI355X 0.3 to 1.7 s a setting (the default test: 0.6 s)."""
+    count = dict.fromkeys(RS.SITUATIONS, 0)
+
+    def on_move(s, mask, mv):
+        for k in RS.classify(s, mask, mv, kw):
+            count[k] += 1
+
+    traj, status, final, S = lockstep(orc, RS.seeds(kw), on_move, **kw)
+    for g, game in enumerate(RS.oracle_games(kw)):   # the games the census test counted
+        assert traj[g] == list(game["moves"]) and status[g] == game["status"], g
+        for k in RS.classify_end(S[g], int(status[g]), kw):
+            count[k] += 1
+    assert count == RS.census(kw)
+    short = {k: count[k] for k in RS.required(kw) if count[k] < RS.CENSUS_MIN}
+    assert not short, short
 
 
 def test_every_move_index_error_class_and_next_state():
@@ -143,3 +178,102 @@ def test_rule_switches_masks(orc):
             assert orc.orc_valid_moves(C.byref(s), C.byref(cfg)) == int(vm[i])
             assert orc.orc_game_status(C.byref(s), C.byref(cfg)) == st[i]
         eng.close()
+
+
+@pytest.mark.parametrize("mum", [1, 5])
+def test_every_move_index_off_the_defaults_vs_oracle(orc, mum):
+    """test_every_move_index_error_class_and_next_state with MIN_UNIT_MOVE 1 and 5, against the oracle (pinned for exactly this sweep
+    by tests/test_oracle_vs_ref.py::test_every_move_index_under_min_unit_move): each of the 44 indices on about 100 states of all six
+    phases from the 150- and 120-round games of tests/rules_settings.py, saturated ones among them — return class, next state, RNG
+    word; a refused move leaves the stored game untouched.
+    On an MI355X 0.03 s."""
+    base = RS.sweep_states()
+    assert set(base[:, 149]) == set(range(6)) and len(base) >= 96
+    states = np.repeat(base, 44, axis=0)
+    moves = np.tile(np.arange(44, dtype=np.uint8), len(base))
+    G = len(states)
+    seeds = (7000 + 13 * np.arange(G, dtype=np.uint32)) % 2147483647
+    eng = pkg().Engine(G, blocks=1, sims=1, dtype=pkg().NET_F32, node_capacity=64, min_unit_move=mum)
+    eng.set_states(states)
+    eng.set_rng(seeds)
+    rc = eng.make_moves(moves)
+    after, rng = eng.get_states(), eng.get_rng()
+    eng.close()
+    cfg = T.default_settings(min_unit_move=mum)
+    s, r, d = T.OrcState(), T.OrcRng(), np.zeros(160, np.uint8)
+    classes = set()
+    for i in range(G):
+        orc.orc_state_unpack(C.byref(s), T.ptr(states[i]))
+        r.x = int(seeds[i])
+        want = orc.orc_make_move(C.byref(s), int(moves[i]), C.byref(r), C.byref(cfg))
+        classes.add(want)
+        assert rc[i] == want, (i // 44, int(moves[i]), int(rc[i]), want)
+        if want == 0:
+            orc.orc_state_pack(C.byref(s), T.ptr(d))
+            assert (after[i] == d).all() and rng[i] == r.x, (i // 44, int(moves[i]))
+        else:
+            assert (after[i][FM] == states[i][FM]).all(), (i // 44, int(moves[i]))
+    assert classes == {0, 1, 2}
+
+
+# ---- the two RNG branches that play does not reach (azr_wave.hpp rng_downscale / rng_float) ------------------------------------------
+def test_die_rejection_in_attack_moves(orc):
+    """libstdc++'s uniform_int_distribution scales minstd_rand0's raw value down by (2^31 - 3) / 6 and draws again when the raw value
+    is one of the six largest: 6 states in 2^31, which no game and no known-answer stream reaches.  Golden attack positions (phase
+    attack, move not SKIP) with the stream placed on each of those states (azr_testlib.RNG_DIE_REJECT), and one step before each (the
+    rejection then meets the second die), against orc_make_move: state and RNG word.
+    On an MI355X 0.01 s."""
+    g = load("rules_games.npz")
+    idx = np.nonzero((g["states"][:, 149] == 3) & (g["moves"] != 42))[0]
+    start = np.array(T.RNG_DIE_REJECT + [T.rng_step_back(x) for x in T.RNG_DIE_REJECT], np.uint32)
+    idx = idx[:: len(idx) // (4 * len(start))][: 4 * len(start)]
+    G = len(idx)
+    states, moves, rng0 = g["states"][idx], g["moves"][idx], np.tile(start, 4)
+    eng = pkg().Engine(G, blocks=1, sims=1, dtype=pkg().NET_F32, node_capacity=64)
+    eng.set_states(states)
+    eng.set_rng(rng0)
+    assert (eng.make_moves(moves) == 0).all()
+    after, rng = eng.get_states(), eng.get_rng()
+    eng.close()
+    cfg = T.default_settings()
+    s, r, d = T.OrcState(), T.OrcRng(), np.zeros(160, np.uint8)
+    for i in range(G):
+        orc.orc_state_unpack(C.byref(s), T.ptr(states[i]))
+        r.x = int(rng0[i])
+        assert orc.orc_make_move(C.byref(s), int(moves[i]), C.byref(r), C.byref(cfg)) == 0
+        orc.orc_state_pack(C.byref(s), T.ptr(d))
+        assert (after[i][FM] == d[FM]).all() and rng[i] == r.x, i
+
+
+def test_float_clamp_in_sampled_pick(orc):
+    """rng_float rounds the 62 largest raw values up to 1.0f and clamps them to nextafterf(1, 0) (libstdc++'s generate_canonical):
+    after a short host-stepped search (orc_hash_eval, 8 simulations) the stream is placed on clamp states and pick(sample=True) is
+    compared with orc_pick_random on the same policy and state: move and RNG word.
+    What this pins is that the branch takes one draw and picks the oracle's move.  It does not pin the clamped VALUE: the pick returns
+    the first index whose running sum reaches sum * u, and for a search policy (entries k / N) u = 1.0f and u = nextafterf(1, 0) stop at
+    the same index, the last non-zero entry; they would part only on an entry below one ulp of the sum, which no visit count gives.
+    No call of the C-ABI hands rng_float's value out or takes a policy in, so the value itself is pinned on the oracle's side only
+    (tests/test_oracle_golden.py::test_rng_states_that_play_does_not_reach, against the reference).
+    On an MI355X 0.01 s."""
+    stub = orc.orc_hash_eval
+    stub.argtypes = [C.c_void_p, T.u8p, T.f32p, C.c_void_p]
+    clamp = [T.RNG_FLOAT_CLAMP[i] for i in (0, 1, 17, 30, 44, 61)]
+    states = np.load(os.path.join(T.GOLDEN, "rules_games.npz"))["states"][40::331][: len(clamp)].copy()
+    G = len(states)
+    eng = pkg().Engine(G, blocks=1, sims=8, dtype=pkg().NET_F32)
+    eng.set_states(states)
+    eng.set_rng(np.arange(900, 900 + G, dtype=np.uint32))
+    assert (eng.status() == -1).all()
+    T.engine_stub_search(eng, stub, 16)
+    pi = eng.policy()
+    eng.set_rng(np.array(clamp, np.uint32))
+    moves = eng.pick(sample=True)
+    rng = eng.get_rng()
+    eng.close()
+    r = T.OrcRng()
+    for g in range(G):
+        r.x = clamp[g]
+        assert orc.orc_rng_float(C.byref(r)) == np.nextafter(np.float32(1), np.float32(0))
+        r.x = clamp[g]
+        assert orc.orc_pick_random(T.ptr(pi[g]), C.byref(r)) == moves[g], g
+        assert r.x == rng[g], g

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import azr_testlib as T
-from gpu_common import pkg
+from gpu_common import arena_play as play, assert_one_hot, pi_of, pkg
 
 pytestmark = pytest.mark.gpu
 FM = T.data_field_mask()
@@ -20,45 +20,8 @@ def digests(rec):
     return np.array([np.frombuffer(hashlib.blake2b(r.tobytes(), digest_size=8).digest(), np.uint64)[0] for r in rec], np.uint64)
 
 
-def play(eng, k0, k1, total, cap, mirror, base, script=False, az=False, chunk=None, sink=None):
-    """the whole arena, draining after every run (in pieces of `chunk` records, each handed to `sink` instead of kept when
-    given); returns (results, log, records, runs that came back unfinished)"""
-    eng.arena_collect_scripted_samples(script)
-    eng.arena_collect_samples(az)
-    eng.arena_start(k0, k1, total, per_slot_cap=cap, mirror=mirror, base_seed=base)
-    out, waits = [], 0
-    for _ in range(2000):
-        fin = eng.arena_run(64)
-        if script or az:
-            while True:
-                r = eng.drain(chunk) if chunk else eng.drain()
-                if len(r):
-                    if sink:
-                        sink(r)
-                    else:
-                        out.append(r)
-                if not chunk or len(r) < chunk:
-                    break
-        if fin:
-            break
-        waits += 1
-    else:
-        raise AssertionError("arena did not finish")
-    rec = np.concatenate(out) if out else np.zeros((0, 265), np.uint8)
-    return eng.arena_results(), eng.arena_log(), rec, waits
-
-
-def pi_of(rec):
-    return rec[:, 93:265].copy().view(np.float32)
-
-
 def z_of(rec):
     return rec[:, 89:93].copy().view(np.float32)[:, 0]
-
-
-def assert_one_hot(rec):
-    pi = pi_of(rec)
-    assert ((pi == 1.0).sum(1) == 1).all() and ((pi != 0.0).sum(1) == 1).all()
 
 
 def game_blocks(rec):

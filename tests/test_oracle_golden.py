@@ -50,6 +50,24 @@ def test_rng_known_answers(orc):
     assert out == [int(x) for x in g["rm_out"]]
 
 
+def test_rng_states_that_play_does_not_reach(orc):
+    """the die's rejection loop and the float's clamp to nextafterf(1, 0): from each state whose next raw value triggers one of them,
+    the reference's value and the stream's position afterwards"""
+    g = load("rng_kat.npz")
+    assert list(g["edge_states"]) == T.RNG_DIE_REJECT + T.RNG_FLOAT_CLAMP
+    r = T.OrcRng()
+    for k, x in enumerate(g["edge_states"]):
+        r.x = int(x)
+        assert orc.orc_rng_dice(C.byref(r)) == g["edge_dice"][k] and r.x == g["edge_dice_after"][k], k
+        r.x = int(x)
+        f = np.float32(orc.orc_rng_float(C.byref(r)))
+        assert f.view(np.uint32) == g["edge_floats"][k].view(np.uint32) and r.x == g["edge_floats_after"][k], k
+    raw = [x * T.RNG_A % T.RNG_M for x in g["edge_states"].tolist()]
+    # a rejected die took two draws, every other value one; every clamped float is the largest float below 1
+    assert [int(a) != y for a, y in zip(g["edge_dice_after"], raw)] == [True] * 6 + [False] * 56 + [True] * 6   # (the six are the top of the 62)
+    assert (g["edge_floats"] == np.nextafter(np.float32(1), np.float32(0))).all() and (g["edge_floats"] < 1).all()
+
+
 def test_rules_games(orc):
     g = load("rules_games.npz")
     for k, seed in enumerate(g["seeds"]):
