@@ -88,6 +88,7 @@ EXPORTS = [
     "azr_mcts_set_forced_playouts", "azr_mcts_pruned_policy", "azr_selfplay_set_forced_playouts", "azr_mcts_set_simulations",
     "azr_selfplay_start_games_from_states",
     "azr_selfplay_set_surprise_weighting", "azr_debug_surprise_weights",
+    "azr_selfplay_set_value_mix", "azr_mcts_root_value", "azr_debug_value_mix",
 ]
 
 
@@ -169,6 +170,10 @@ def load_library(test_hooks=False):
         L.azr_selfplay_set_surprise_weighting.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32]
         L.azr_debug_surprise_weights.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_selfplay_set_value_mix.argtypes = [C.c_void_p, C.c_float]
+        L.azr_mcts_root_value.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_debug_value_mix.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[test_hooks] = L
         if not test_hooks:
             _lib = L
@@ -523,6 +528,30 @@ class Engine:
         self._chk(self.L.azr_debug_surprise_weights(self.h, float(share), float(max_weight), int(seed), _p(pi), _p(prior), _p(v), _p(n), _p(s),
                                                     len(n), _p(kl), _p(w), _p(c)))
         return kl, w, c
+
+    # ---- value mix of the records (this engine's own; off = every record carries the bare game outcome z)
+    def selfplay_set_value_mix(self, q_share):
+        """device self-play: a finished game's records carry z' = (1 - q_share) * z + q_share * q, q the visit-weighted mean of the
+        root's Q at the recorded decision; q_share <= 0 = off; read by selfplay_start*"""
+        self._chk(self.L.azr_selfplay_set_value_mix(self.h, float(q_share)))
+
+    def root_value(self):
+        """(q [G] float32, has_q [G] bool) of the last search's roots, by the device function the self-play step uses"""
+        q, has = np.zeros(self.G, np.float32), np.zeros(self.G, np.uint8)
+        self._chk(self.L.azr_mcts_root_value(self.h, _p(q), _p(has)))
+        return q, has.astype(bool)
+
+    def debug_value_mix(self, q_share, N, Q, valid, z):
+        """the rule alone, on the device: N, Q [rows, 43], valid, z [rows] -> (q, has_q, z'), each [rows]"""
+        N = np.ascontiguousarray(N, np.uint32)
+        Q = np.ascontiguousarray(Q, np.float32)
+        v = np.ascontiguousarray(valid, np.uint64)
+        z = np.ascontiguousarray(z, np.float32)
+        rows = len(z)
+        assert N.shape == Q.shape == (rows, MOVES) and v.shape == (rows,)
+        q, has, zz = np.zeros(rows, np.float32), np.zeros(rows, np.uint8), np.zeros(rows, np.float32)
+        self._chk(self.L.azr_debug_value_mix(self.h, float(q_share), _p(N), _p(Q), _p(v), _p(z), rows, _p(q), _p(has), _p(zz)))
+        return q, has.astype(bool), zz
 
     # ---- self-play
     def selfplay_start(self, base_seed=20260001):

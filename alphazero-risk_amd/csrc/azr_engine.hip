@@ -179,11 +179,14 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // SURPRISE (self-play only): policy surprise weighting of the records (azr_surprise.hpp) — KL(pi || P) of every staged record is kept
 // beside it, and a finished game's records are written floor(w) or ceil(w) times each by flush_samples_weighted.  The search, the moves
 // and the staged records are the ones without it.
-template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false>
+// QMIX (self-play only): the value mix of the records (azr_valuemix.hpp) — the root value q of every staged record, from the root's
+// unpruned N and its Q, is kept beside it, and both flush paths write z' = (1 - q_share) z + q_share q in place of z.  The search, the
+// moves, pi, the copies and every counter are the ones without it.
+template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false, bool QMIX = false>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
-    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED) && (SELFPLAY || !SURPRISE),
-                  "CAP and SURPRISE need SELFPLAY, FORCED implies NOISE: launch_tree_step lists the fifteen");
+    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED) && (SELFPLAY || !SURPRISE) && (SELFPLAY || !QMIX),
+                  "CAP, SURPRISE and QMIX need SELFPLAY, FORCED implies NOISE: launch_tree_step lists the twenty-seven");
     __shared__ int8_t scratch[128];
     const int g = blockIdx.x;
     TP_BEGIN();
@@ -217,7 +220,8 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             uint32_t N; uint64_t valid;
             uint32_t mv = NONE;
             float P = 0.0f;   // SURPRISE: the root's stored prior row
-            if (root_node(t, root, N, valid, nullptr, SURPRISE ? &P : nullptr) != NO_NODE) {
+            float Q = 0.0f;   // QMIX: the root's mean values
+            if (root_node(t, root, N, valid, QMIX ? &Q : nullptr, SURPRISE ? &P : nullptr) != NO_NODE) {
                 float pi = root_policy(N, valid);
                 mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
                 if (FORCED && E.prune && (!CAP || full)) {   // the record's pi from N'; the move above is N's
@@ -225,6 +229,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                     pi = root_policy(root_pruned_counts(E, S, t, tree_lookup(t, rkd, key_hash(t, rkd)), N, valid, eta, E.forced_k), valid);
                 }
                 if (SURPRISE && (!CAP || full)) stage_surprise(E, g, c, pi, P, valid);
+                if (QMIX && (!CAP || full)) stage_root_value(E, g, c, N, Q, valid);   // N is the unpruned count
                 if (!CAP || full) stage_sample(E, g, c, root, pi, k);
             }
             TP(16);
@@ -239,9 +244,9 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                 if (root.err) { k.err++; c.error = root.err; }
                 else {
                     wave_mem_sync();
-                    if (SURPRISE) k.samples += flush_samples_weighted(E, g, c.nsamples, st, c.seed, k.ringdrop);
+                    if (SURPRISE) k.samples += flush_samples_weighted<QMIX>(E, g, c.nsamples, st, c.seed, k.ringdrop);
                     else {
-                        flush_samples(E, g, c.nsamples, st, k.ringdrop);
+                        flush_samples<QMIX>(E, g, c.nsamples, st, k.ringdrop);
                         k.samples += c.nsamples;
                     }
                     k.games++;
@@ -342,6 +347,40 @@ __global__ __launch_bounds__(64) void k_root_stats(Dev E, uint32_t* n_out, float
         if (q_out) q_out[(size_t)g * MOVES + l] = Q;
         if (p_out) p_out[(size_t)g * MOVES + l] = P;
         if (pi_out) pi_out[(size_t)g * MOVES + l] = pi;
+    }
+}
+
+// azr_mcts_root_value: q of the last search's roots by the self-play step's root_value (0 and has_q 0 for a root that is not in the tree)
+__global__ __launch_bounds__(64) void k_root_value(Dev E, float* q_out, uint8_t* has_q_out)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    Tree t = tree_of(E, g);
+    WS root;
+    ws_load(root, E.state + (size_t)g * GREC);
+    uint32_t N; uint64_t valid; float Q = 0.0f, q = 0.0f;
+    bool has_q = false;
+    if (root_node(t, root, N, valid, &Q) != NO_NODE) q = root_value(N, Q, valid, has_q);
+    if (lane_id() == 0) {
+        q_out[g] = q;
+        if (has_q_out) has_q_out[g] = has_q ? 1 : 0;
+    }
+}
+
+// azr_debug_value_mix: the rule alone, one wave per row, through the device functions of the step and its flushes
+__global__ __launch_bounds__(64) void k_debug_value_mix(float q_share, const uint32_t* N, const float* Q, const uint64_t* valid, const float* z,
+                                                        float* q_out, uint8_t* has_q_out, float* z_out)
+{
+    const size_t i = blockIdx.x;
+    const uint32_t l = lane_id(), ll = l < MOVES ? l : 0;
+    bool has_q;
+    const float q = root_value(N[i * MOVES + ll], Q[i * MOVES + ll], rfl64(valid[i]), has_q);
+    const float zz = blend_z(rdlf(z[i], 0), q, has_q, __fsub_rn(1.0f, q_share), q_share);
+    if (l == 0) {
+        q_out[i] = q;
+        has_q_out[i] = has_q ? 1 : 0;
+        z_out[i] = zz;
     }
 }
 
@@ -649,7 +688,8 @@ extern "C" int azr_engine_destroy(azr_engine* h)
     Dev& d = h->d;
     void* ptrs[] = {d.sp_started, d.state, d.ctl, d.nodes, d.touch, d.nhash, d.table, d.freel, d.path, d.leaf_in, d.leaf_key,
                     d.leaf_valid, d.leaf_hash, d.net_pi, d.net_v, d.stage, d.ring, d.ring_count, d.counters, d.active,
-                    d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final, d.root_eta, d.stage_kl};
+                    d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final, d.root_eta, d.stage_kl,
+                    d.stage_q};
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : h->tree2) if (p) hipFree(p);
     if (d.leaf_list) hipFree(d.leaf_list);
@@ -860,23 +900,32 @@ extern "C" int azr_mcts_begin(azr_engine* h)
     return AZR_OK;
 }
 
-// The fifteen k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
-// self-play also under a CAP, which doubles its three, and each of those six with SURPRISE.  CAP and SURPRISE need SELFPLAY and FORCED
-// implies NOISE (k_tree_step asserts all three).
+// The twenty-seven k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
+// self-play also under a CAP, which doubles its three, each of those six with SURPRISE, and each of those twelve with QMIX.  CAP,
+// SURPRISE and QMIX need SELFPLAY and FORCED implies NOISE (k_tree_step asserts all four).
 // Callers say what is in force; forced playouts without root noise run the NOISE instantiation, on the constant vector.
 static int launch_tree_step(azr_engine* h, const Dev& d, bool selfplay, const StepOpts& o)
 {
     void (*step)(Dev) = nullptr;
-#define AZR_STEP(SP, N, C, F, W) case (W) << 4 | (SP) << 3 | (N) << 2 | (C) << 1 | (F): step = k_tree_step<SP, N, C, F, W>; break
-    switch (o.surprise << 4 | selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
-        AZR_STEP(0, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 0, 0); AZR_STEP(0, 1, 0, 1, 0);
-        AZR_STEP(1, 0, 0, 0, 0); AZR_STEP(1, 1, 0, 0, 0); AZR_STEP(1, 1, 0, 1, 0);
-        AZR_STEP(1, 0, 1, 0, 0); AZR_STEP(1, 1, 1, 0, 0); AZR_STEP(1, 1, 1, 1, 0);
-        AZR_STEP(1, 0, 0, 0, 1); AZR_STEP(1, 1, 0, 0, 1); AZR_STEP(1, 1, 0, 1, 1);
-        AZR_STEP(1, 0, 1, 0, 1); AZR_STEP(1, 1, 1, 0, 1); AZR_STEP(1, 1, 1, 1, 1);
+#define AZR_STEP(SP, N, C, F, W, M) \
+    case (M) << 5 | (W) << 4 | (SP) << 3 | (N) << 2 | (C) << 1 | (F): step = k_tree_step<SP, N, C, F, W, M>; break
+#define AZR_STEP_SP(W, M) \
+    AZR_STEP(1, 0, 0, 0, W, M); AZR_STEP(1, 1, 0, 0, W, M); AZR_STEP(1, 1, 0, 1, W, M); \
+    AZR_STEP(1, 0, 1, 0, W, M); AZR_STEP(1, 1, 1, 0, W, M); AZR_STEP(1, 1, 1, 1, W, M)
+    // (the fifteen without QMIX first, in the order they always had, then their self-play twelve again with QMIX)
+    switch (o.qmix << 5 | o.surprise << 4 | selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
+        AZR_STEP(0, 0, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 1, 0, 0);
+        AZR_STEP_SP(0, 0);
+        AZR_STEP_SP(1, 0);
+        AZR_STEP_SP(0, 1);
+        AZR_STEP_SP(1, 1);
     }
+#undef AZR_STEP_SP
 #undef AZR_STEP
-    if (!step) { h->err = "launch_tree_step: a playout cap or surprise weighting on a host-stepped search: there is no such k_tree_step"; return AZR_E_LOGIC; }
+    if (!step) {
+        h->err = "launch_tree_step: a playout cap, surprise weighting or a value mix on a host-stepped search: there is no such k_tree_step";
+        return AZR_E_LOGIC;
+    }
     hipLaunchKernelGGL(step, dim3(d.G), dim3(64), 0, h->stream, d);
     HIPCHK(h, hipGetLastError());
     return AZR_OK;
@@ -888,7 +937,7 @@ static StepOpts options_in_force(const azr_engine* h, int mode)
 {
     if (mode == 2) return h->sp;
     if (mode == 3) return StepOpts{};
-    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f, false};
+    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f, false, false};
 }
 // ... and the device view a search-related launch sees with it.  eta_const: no root vector is there to read (a self-play whose steps
 // carry NOISE keeps one per root).  Outside a self-play: the handle's without a self-play's leftovers, with azr_mcts_set_forced_playouts /
@@ -982,6 +1031,20 @@ extern "C" int azr_mcts_root_stats(azr_engine* h, uint32_t* n, float* q, float* 
     return AZR_OK;
 }
 
+extern "C" int azr_mcts_root_value(azr_engine* h, float* q, uint8_t* has_q)
+{
+    ENTER(h);
+    if (!q) return AZR_E_INVALID_ARGUMENT;
+    const size_t G = (size_t)h->d.G;
+    DevBuf bq, bh;
+    HIPCHK(h, bq.alloc(G * 4)); HIPCHK(h, bh.alloc(G));
+    LAUNCH(h, k_root_value, h->d, (float*)bq.p, (uint8_t*)bh.p);
+    D2H(h, q, bq.p, G * 4);
+    if (has_q) D2H(h, has_q, bh.p, G);
+    SYNC(h);
+    return AZR_OK;
+}
+
 extern "C" int azr_mcts_policy(azr_engine* h, float* pi)
 {
     ENTER(h);
@@ -1013,7 +1076,7 @@ static void resolve_selfplay_options(azr_engine* h)
     const SelfplayOpts& o = h->sp_set;
     Dev& d = h->d;
     h->host = HostOpts{};
-    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f, o.psw_share > 0.0f};
+    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f, o.psw_share > 0.0f, o.q_share > 0.0f};
     d.noise_alpha = o.alpha;
     d.noise_seed = o.noise_seed;
     d.cap_threshold = cap_threshold_of(o.cap_prob);
@@ -1024,6 +1087,7 @@ static void resolve_selfplay_options(azr_engine* h)
     d.psw_share = o.psw_share;
     d.psw_max = o.psw_max;
     d.psw_seed = o.psw_seed;
+    d.q_share = o.q_share;
     d.eta_const = 0;
 }
 
@@ -1031,6 +1095,8 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
 {
     // the surprises' buffer, with the first self-play that weights its records: an engine that never does allocates none
     if (h->sp_set.psw_share > 0.0f && !h->d.stage_kl) HIPCHK(h, dmalloc(&h->d.stage_kl, (size_t)h->d.G * h->d.SCAP));
+    // ... and the root values' buffer, with the first self-play that blends them into z
+    if (h->sp_set.q_share > 0.0f && !h->d.stage_q) HIPCHK(h, dmalloc(&h->d.stage_q, (size_t)h->d.G * h->d.SCAP));
     h->d.base_seed = base_seed;
     h->d.sp_quota = quota;
     h->d.sp_compact = 0;
@@ -1238,6 +1304,48 @@ extern "C" int azr_debug_surprise_weights(azr_engine* h, float share, float max_
     D2H(h, kl_out, bk.p, rows * 4);
     D2H(h, w_out, bw.p, rows * 4);
     D2H(h, copies_out, bc.p, rows * 4);
+    SYNC(h);
+    return AZR_OK;
+}
+
+// ---- value mix ------------------------------------------------------------------------------------------
+// q_share: a number <= 1 (<= 0 = off)
+static int value_mix_check(azr_engine* h, const char* who, float q_share)
+{
+    if (q_share != q_share || q_share > 1.0f) return bad_argument(h, std::string(who) + ": q_share must be a number <= 1 (<= 0 = off)");
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_set_value_mix(azr_engine* h, float q_share)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (int rc = value_mix_check(h, "azr_selfplay_set_value_mix", q_share)) return rc;
+    h->sp_set.q_share = q_share > 0.0f ? q_share : 0.0f;
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_value_mix(azr_engine* h, float q_share, const uint32_t* N, const float* Q, const uint64_t* valid, const float* z,
+                                   int rows, float* q_out, uint8_t* has_q_out, float* z_out)
+{
+    ENTER(h);
+    if (int rc = value_mix_check(h, "azr_debug_value_mix", q_share)) return rc;
+    if (!(q_share > 0.0f)) return bad_argument(h, "azr_debug_value_mix: q_share must lie in (0, 1]");
+    if (rows < 0 || (rows > 0 && (!N || !Q || !valid || !z || !q_out || !has_q_out || !z_out))) return AZR_E_INVALID_ARGUMENT;
+    if (rows == 0) return AZR_OK;
+    const size_t n = (size_t)rows;
+    DevBuf bn, bq, bv, bz, oq, oh, oz;
+    HIPCHK(h, bn.alloc(n * MOVES * 4)); HIPCHK(h, bq.alloc(n * MOVES * 4)); HIPCHK(h, bv.alloc(n * 8)); HIPCHK(h, bz.alloc(n * 4));
+    HIPCHK(h, oq.alloc(n * 4)); HIPCHK(h, oh.alloc(n)); HIPCHK(h, oz.alloc(n * 4));
+    H2D(h, bn.p, N, n * MOVES * 4);
+    H2D(h, bq.p, Q, n * MOVES * 4);
+    H2D(h, bv.p, valid, n * 8);
+    H2D(h, bz.p, z, n * 4);
+    hipLaunchKernelGGL(k_debug_value_mix, dim3(rows), dim3(64), 0, h->stream, q_share, (const uint32_t*)bn.p, (const float*)bq.p,
+                       (const uint64_t*)bv.p, (const float*)bz.p, (float*)oq.p, (uint8_t*)oh.p, (float*)oz.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, q_out, oq.p, n * 4);
+    D2H(h, has_q_out, oh.p, n);
+    D2H(h, z_out, oz.p, n * 4);
     SYNC(h);
     return AZR_OK;
 }

@@ -136,12 +136,17 @@ struct Dev {
     // AZR_TREE_HASH_AND / AZR_TREE_HASH_OR, read when the engine is created: key_hash returns (h & hash_and) | hash_or (azr_tree.hpp)
     uint32_t hash_and, hash_or;
 #endif
+    // value mix of the records (this engine's own; read by the k_tree_step instantiations with QMIX only; azr_valuemix.hpp).  Behind
+    // everything else: the offsets the kernels without it read stay where they were.
+    float q_share;             // the share of the root value q in a record's z (0 = off)
+    float* stage_q;            // [G][SCAP]  q of each staged record's root, NaN = none (allocated by the first azr_selfplay_start* that blends)
 };
 constexpr int ALOG = 16;
 
 // The options of the search variants (host side).  Which of them a tree step carries: root noise, a playout cap (self-play only),
-// forced playouts, policy surprise weighting of the records (self-play only) — the template arguments of k_tree_step after SELFPLAY.
-struct StepOpts { bool noise = false, cap = false, forced = false, surprise = false; };
+// forced playouts, policy surprise weighting of the records and the value mix of their z (both self-play only) — the template
+// arguments of k_tree_step after SELFPLAY.
+struct StepOpts { bool noise = false, cap = false, forced = false, surprise = false, qmix = false; };
 // Host-stepped searches (azr_mcts_*): in force from the setter's call until the next azr_selfplay_start*.
 struct HostOpts {
     bool noise = false;        // azr_mcts_set_root_noise: a vector per game is set in d.root_eta
@@ -149,7 +154,7 @@ struct HostOpts {
     int sims = 0;              // azr_mcts_set_simulations: the budget (0 = the settings')
 };
 // Device self-play, as the azr_selfplay_set_* setters leave them.  A running self-play never sees a change: azr_selfplay_start* resolves
-// them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune and psw_*.
+// them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune, psw_* and q_share.
 struct SelfplayOpts {
     float alpha = 0.0f;        // azr_selfplay_set_dirichlet (0 = off)
     uint32_t noise_seed = 0;
@@ -161,6 +166,7 @@ struct SelfplayOpts {
     float psw_share = 0.0f;    // azr_selfplay_set_surprise_weighting (0 = off)
     float psw_max = 1.0f;
     uint32_t psw_seed = 0;
+    float q_share = 0.0f;      // azr_selfplay_set_value_mix (0 = off)
 };
 
 // folded network parameters on device

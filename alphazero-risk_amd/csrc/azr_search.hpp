@@ -95,7 +95,9 @@ __device__ __forceinline__ void ctl_store(const Ctl& c, Ctl* dst)
     if (l < 32) reinterpret_cast<uint32_t*>(dst)[l] = w;
 }
 
-// packs one finished game's staged records into the 265-byte on-disk layout (alphazero_nn_data.cpp:123-130)
+// packs one finished game's staged records into the 265-byte on-disk layout (record_byte); QMIX: their z blended with the staged
+// root values (azr_valuemix.hpp)
+template <bool QMIX = false>
 __device__ __forceinline__ void flush_samples(const Dev& E, int g, uint32_t n, int status, unsigned long long& dropped)
 {
     if (n == 0) return;
@@ -109,17 +111,8 @@ __device__ __forceinline__ void flush_samples(const Dev& E, int g, uint32_t n, i
         const uint8_t* src = st + (size_t)r * STAGE_BYTES;
         uint8_t* dst = E.ring + (size_t)slot * AZR_RECORD_BYTES;
         uint32_t player = rfl((uint32_t)src[260]);
-        // NNTrainDataStorage::updateValues (alphazero_nn_data.cpp:51-65)
-        float z = status == ST_DRAW ? 0.0f : ((int)player == status ? 1.0f : -1.0f);
-        uint32_t zb = __float_as_uint(z);
-        for (uint32_t j = lane_id(); j < AZR_RECORD_BYTES; j += 64) {
-            uint8_t b;
-            if (j == 0) b = (uint8_t)player;
-            else if (j < 89) b = src[j - 1];
-            else if (j < 93) b = (uint8_t)(zb >> (8 * (j - 89)));
-            else b = src[88 + (j - 93)];
-            dst[j] = b;
-        }
+        const uint32_t zb = record_z_bits<QMIX>(E, g, r, player, status);
+        for (uint32_t j = lane_id(); j < AZR_RECORD_BYTES; j += 64) dst[j] = record_byte(src, player, zb, j);
     }
 }
 
@@ -173,6 +166,16 @@ __device__ __forceinline__ void stage_surprise(const Dev& E, int g, const Ctl& c
     if (c.nsamples >= (uint32_t)E.SCAP) return;
     const float kl = record_surprise(pi, P, valid);
     if (lane_id() == 0) E.stage_kl[(size_t)g * E.SCAP + c.nsamples] = kl;
+}
+
+// Value mix: the root value of the record stage_sample stages next, into the float beside its staging slot, NaN for a root without a
+// completed visit (nothing for a record past the buffer's end).  N, Q: the root node's rows as the search left them, N the unpruned count.
+__device__ __forceinline__ void stage_root_value(const Dev& E, int g, const Ctl& c, uint32_t N, float Q, uint64_t valid)
+{
+    if (c.nsamples >= (uint32_t)E.SCAP) return;
+    bool has_q;
+    const float q = root_value(N, Q, valid, has_q);
+    if (lane_id() == 0) E.stage_q[(size_t)g * E.SCAP + c.nsamples] = has_q ? q : __uint_as_float(0x7FC00000u);
 }
 
 // Lists this slot's waiting leaves (leaf slot g * T + thread, in thread order) behind those of the slots that came first: one atomic per

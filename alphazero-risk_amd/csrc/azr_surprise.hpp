@@ -13,6 +13,7 @@
 #pragma once
 #include "azr_internal.hpp"
 #include "azr_noise.hpp"
+#include "azr_valuemix.hpp"
 
 namespace azr {
 
@@ -89,7 +90,9 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 
 // flush_samples under surprise weighting: the finished game's n staged records (surprises in E.stage_kl), record r written c_r times
 // in a row, in staging order, into ONE ring reservation of C = sum c_r records.  Returns C; copies past the ring's end are counted in
-// `dropped`.  Lane r of a 64-record chunk computes c_r; the copies are then written record by record in flush_samples' packing.
+// `dropped`.  Lane r of a 64-record chunk computes c_r; the copies are then written record by record in flush_samples' packing
+// (record_byte), every copy of a record with the same z — under QMIX the blended one (azr_valuemix.hpp).
+template <bool QMIX = false>
 __device__ __forceinline__ unsigned long long flush_samples_weighted(const Dev& E, int g, uint32_t n, int status, uint32_t game_seed,
                                                                      unsigned long long& dropped)
 {
@@ -115,20 +118,13 @@ __device__ __forceinline__ unsigned long long flush_samples_weighted(const Dev& 
             if (copies == 0) continue;
             const uint8_t* src = st + (size_t)(base + j) * STAGE_BYTES;
             const uint32_t player = rfl((uint32_t)src[260]);
-            // NNTrainDataStorage::updateValues (alphazero_nn_data.cpp:51-65)
-            const float z = status == ST_DRAW ? 0.0f : ((int)player == status ? 1.0f : -1.0f);
-            const uint32_t zb = __float_as_uint(z);
+            const uint32_t zb = record_z_bits<QMIX>(E, g, base + j, player, status);
             // this lane's bytes of the 265-byte record (byte i * 64 + lane), read once for all the copies
             uint8_t b[5];
 #pragma unroll
             for (uint32_t i = 0; i < 5; i++) {
                 const uint32_t q = i * 64u + lane_id();
-                uint8_t v = 0;
-                if (q == 0) v = (uint8_t)player;
-                else if (q < 89) v = src[q - 1];
-                else if (q < 93) v = (uint8_t)(zb >> (8 * (q - 89)));
-                else if (q < AZR_RECORD_BYTES) v = src[88 + (q - 93)];
-                b[i] = v;
+                b[i] = q < AZR_RECORD_BYTES ? record_byte(src, player, zb, q) : (uint8_t)0;
             }
             for (uint32_t cpy = 0; cpy < copies; cpy++, slot++) {
                 if (slot >= E.ring_cap) { dropped += 1; continue; }

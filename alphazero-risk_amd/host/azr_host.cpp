@@ -108,6 +108,7 @@ void Settings::init(int argc, char* argv[])
         {"psw-share", "[this build] self-play policy surprise weighting: share of a finished game's record weight handed out in proportion to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off: every record once; at most 1; KataGo runs 0.5)", "0", false},
         {"psw-max", "[this build] cap on one record's weight under --psw-share (within [1, 64])", "4", false},
         {"psw-seed", "[this build] seed of the coin that rounds a record's weight to its copy count (independent of --seed, --dir-seed and --cap-seed)", std::to_string(PSW_SEED), false},
+        {"q-share", "[this build] self-play value mix: share of the search's root value q in the records' value target, z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1; Lc0's q_ratio)", "0", false},
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -301,6 +302,16 @@ void Settings::init(int argc, char* argv[])
             exit(2);
         }
         PSW_SEED = (uint32_t)sd;
+    }
+    {
+        char* end = nullptr;
+        const std::string sv = get("q-share");
+        const double sh = strtod(sv.c_str(), &end);
+        if (sv.empty() || *end != '\0' || !(sh >= 0.0) || sh > 1.0) {
+            fprintf(stderr, "--q-share: '%s' is not a share (a number in [0, 1]; 0 = off)\n", sv.c_str());
+            exit(2);
+        }
+        Q_SHARE = (float)sh;
     }
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
@@ -777,6 +788,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         e.check(azr_selfplay_set_forced_playouts(e.h, SETTINGS.FORCED_K, SETTINGS.PRUNE_TARGET), "selfplay_set_forced_playouts");
         // policy surprise weighting of the generated games' records: --psw-share 0 (default) writes every record once
         e.check(azr_selfplay_set_surprise_weighting(e.h, SETTINGS.PSW_SHARE, SETTINGS.PSW_MAX, SETTINGS.PSW_SEED), "selfplay_set_surprise_weighting");
+        // value mix of the generated games' records: --q-share 0 (default) writes the bare game outcome
+        e.check(azr_selfplay_set_value_mix(e.h, SETTINGS.Q_SHARE), "selfplay_set_value_mix");
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);

@@ -25,7 +25,7 @@ namespace azrhost {
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
 // `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2,
-// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap; --forced-k, --prune-target for forced playouts and policy target pruning; --psw-share, --psw-max, --psw-seed for policy surprise weighting of its records), the others marked "[this build]" in --help.
+// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap; --forced-k, --prune-target for forced playouts and policy target pruning; --psw-share, --psw-max, --psw-seed for policy surprise weighting of its records; --q-share for the value mix of their z), the others marked "[this build]" in --help.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:
@@ -84,6 +84,7 @@ public:
     float PSW_SHARE = 0.0f;              // --psw-share: policy surprise weighting of the self-play records, the share of a game's weight handed out by KL(pi || prior) (0 = off) ...
     float PSW_MAX = 4.0f;                // --psw-max: ... the cap on one record's weight ...
     uint32_t PSW_SEED = 0;               // --psw-seed: ... and the seed of the coin that rounds a weight to a copy count (self-play generation of -m train only, like --dir-alpha)
+    float Q_SHARE = 0.0f;                // --q-share: value mix of the self-play records, the share of the root value q in z' = (1 - share) z + share q (0 = off; self-play generation of -m train only, like --dir-alpha)
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 

@@ -207,6 +207,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
             gen.selfplay_set_playout_cap(getattr(a, "cap_prob", 1.0), getattr(a, "cap_fast", 0), getattr(a, "cap_seed", 0))   # playout cap of the generated games only (1 / 0 = off)
             gen.selfplay_set_forced_playouts(getattr(a, "forced_k", 0.0), getattr(a, "prune_target", 0))   # forced playouts / target pruning of the generated games only (0 / 0 = off)
             gen.selfplay_set_surprise_weighting(getattr(a, "psw_share", 0.0), getattr(a, "psw_max", 4.0), getattr(a, "psw_seed", 0))   # surprise weighting of the generated games' records only (0 = every record once)
+            gen.selfplay_set_value_mix(getattr(a, "q_share", 0.0))   # value mix of the generated games' records only (0 = the bare game outcome)
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -356,6 +357,9 @@ def main():
                          "to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off; at most 1)")
     ap.add_argument("--psw-max", type=float, default=4.0, help="[this build] cap on one record's weight under --psw-share (within [1, 64])")
     ap.add_argument("--psw-seed", type=int, default=0, help="[this build] seed of the coin that rounds a record's weight to its copy count")
+    ap.add_argument("--q-share", type=float, default=0.0,
+                    help="[this build] self-play value mix: share of the search's root value q in the records' value target, "
+                         "z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1)")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -383,6 +387,8 @@ def main():
         ap.error(f"--psw-max: {a.psw_max} is not a weight cap (a number in [1, 64])")
     if not 0 <= a.psw_seed <= 0xFFFFFFFF:
         ap.error(f"--psw-seed: {a.psw_seed} is not a 32-bit seed")
+    if not 0.0 <= a.q_share <= 1.0:   # (a NaN fails both comparisons)
+        ap.error(f"--q-share: {a.q_share} is not a share (a number in [0, 1]; 0 = off)")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():
         learn(a)

@@ -354,6 +354,48 @@ int azr_debug_surprise_weights(azr_engine* h, float share, float max_weight, uin
                                const uint64_t* valid, const uint32_t* game_len, const uint32_t* game_seed, int games,
                                float* kl_out, float* w_out, uint32_t* copies_out);
 
+/* ---- value mix: the search's root value blended into the records' z (this engine's own; off after azr_engine_create) ----
+ * The reference writes the bare game outcome z in {-1, 0, +1} into bytes 89..92 of every record of a finished game: the first-round
+ * record and the last-move record of a game decided by dice carry the same value.  With the value mix (Lc0's q_ratio; z/q averaging
+ * in Oracle's "Lessons from AlphaZero") a record's value target is the average of the outcome and the value the search found at that
+ * root.  The 265-byte record format, the search, the moves, dice, games, pi and every counter are those of the same run without the
+ * feature; only bytes 89..92 differ.
+ * All arithmetic below is fp32, each operation rounded on its own (no fused multiply-add), in the order written.
+ *
+ * Root value of a finished search.  N[m], Q[m] = the root node's completed visits and mean values as the search left them (what
+ * azr_mcts_root_stats reports; N is the unpruned count, the low 24 bits of the node's N word); valid = the root's legal moves.
+ *     num = 0.0f;  den = 0.0f
+ *     for m = 0 .. 42 in index order, if m is legal and N[m] > 0:
+ *         num = num + (float)N[m] * Q[m]                                     (a multiply, then an add)
+ *         den = den + (float)N[m]
+ *     has_q = den > 0
+ *     q = num / den;   q = min(max(q, -1.0f), 1.0f)                           (only where has_q; q = 0 without it)
+ * Q[m] is from the root mover's perspective (the backup flips the sign once per change of player below the entry), so q has the
+ * perspective of the record's z: that of the record's player, byte 0.
+ *
+ * Blend, when the finished game's records are written.  z = the outcome for the record's player, as without the feature.
+ *     a  = 1.0f - q_share
+ *     z' = has_q ? a * z + q_share * q : z                                    (two multiplies, then an add)
+ *     z' = min(max(z', -1.0f), 1.0f)
+ * z' goes into bytes 89..92; nothing else in the record changes.  q_share = 1 gives z' = q exactly; a drawn game gives q_share * q.
+ *
+ * With the other self-play settings.  Playout cap: a fast decision stages no record, so it has nothing to blend.  Policy target pruning
+ * changes pi only: q comes from the unpruned N and Q, the search that chose the move.  Surprise weighting: every copy of a record
+ * carries the same z'; KL, weights, copy counts and `samples` are unchanged.  The arena (azr_arena_*, collected samples included),
+ * scripted collection and the host-stepped searches (azr_mcts_*) never see it.
+ *
+ * q_share <= 0 = off (default).  Read by azr_selfplay_start*; a running self-play never sees a change.  AZR_E_INVALID_ARGUMENT, with a
+ * reason in azr_last_error, for a NaN or q_share > 1. */
+int azr_selfplay_set_value_mix(azr_engine* h, float q_share);
+/* q of the last search's roots, q_host [G], computed on the device by the device function the self-play step uses; has_q_host [G]
+ * (optional) 1 where the root has a completed visit.  A root that is not in the tree reports 0 with has_q 0.  Valid wherever
+ * azr_mcts_root_stats is. */
+int azr_mcts_root_value(azr_engine* h, float* q_host /*[G]*/, uint8_t* has_q_host /*[G], optional*/);
+/* the rule alone, on the device, one wavefront per row through the device functions of the self-play step and its flushes: N, Q
+ * [rows][43], valid, z [rows] -> q_out, has_q_out, z_out [rows].  q_share in (0, 1]. */
+int azr_debug_value_mix(azr_engine* h, float q_share, const uint32_t* N, const float* Q /*[rows][43]*/, const uint64_t* valid,
+                        const float* z /*[rows]*/, int rows, float* q_out, uint8_t* has_q_out, float* z_out);
+
 /* ---- device-resident self-play (trainer move loop, alphazero_trainer.cpp:80-119) --------------------------- */
 /* (Re)start all G games: game g plays seeds base_seed + g, then base_seed + G + g, ... */
 int azr_selfplay_start(azr_engine* h, uint32_t base_seed);
