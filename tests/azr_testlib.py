@@ -395,6 +395,11 @@ def tree_roots(stride=1):
     return states, np.arange(500, 500 + len(states), dtype=np.uint32)
 
 
+def bits(mask):
+    """legal-move mask -> bool [43]"""
+    return np.array([(int(mask) >> i) & 1 for i in range(43)], bool)
+
+
 def lowest_unvisited(valid, n):
     """the lowest legal move the search never tried, or None"""
     for i in range(43):
@@ -473,6 +478,11 @@ def engine_stub_search(eng, stub, max_passes):
             v[g] = vv.value
         eng.mcts_apply(pi, v)
     raise AssertionError(f"the search did not finish in {max_passes} passes")
+
+
+def host_stub_search(eng, orc, stub):
+    """azr_mcts_simulate with the NN seam served on the host by an oracle stub net: engine_stub_search for searches of any length"""
+    engine_stub_search(eng, stub, 99999)
 
 
 def engine_matches_tree_run(eng, run):

@@ -6,12 +6,10 @@ the device's __fmul_rn / __fadd_rn / __fsqrt_rn / __fdiv_rn are.  puct_pick is t
 alone where there are any; prune_counts is the header's loop; root_policy is calculateMoveProbability(1.0f)."""
 import numpy as np
 
+from azr_testlib import bits
+
 f32 = np.float32
 MOVES = 43
-
-
-def bits(mask):
-    return np.array([(int(mask) >> i) & 1 for i in range(MOVES)], bool)
 
 
 def umap_order(orc, valid):

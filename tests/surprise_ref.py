@@ -7,6 +7,7 @@ tests/test_surprise_ref.py checks the restatement against float64 on the CPU; te
 it bit for bit."""
 import numpy as np
 
+from azr_testlib import bits
 from playout_cap_ref import M32, mix
 
 f32 = np.float32
@@ -32,11 +33,6 @@ def ln32(x):
     out = e.astype(f32) * f32(0.693147182) + (f32(2.0) * t) * p
     assert out.dtype == f32
     return out
-
-
-def bits(valid):
-    """legal-move mask -> bool [43]"""
-    return np.array([(int(valid) >> m) & 1 for m in range(MOVES)], bool)
 
 
 def record_kl(pi, prior, valid):

@@ -5,16 +5,13 @@ policy against the restatement over three decisions with tree reuse; device self
 decision through the host-stepped entry points (with and without a playout cap, with and without Dirichlet noise), and against itself
 with pruning off; argument checks.
 Engines of 8 games, one block, NET_F32."""
-import os
-
 import numpy as np
 import pytest
 
 import azr_testlib as T
 import forced_playouts_ref as F
-import playout_cap_ref as R
-from gpu_common import pkg
-from test_gpu_root_noise import _setup_engine, _stepped
+import selfplay_retrace as SR
+from gpu_common import pkg, setup_engine, stepped
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -27,7 +24,7 @@ def _bitwise(a, b):
 
 # ---- 1. the root rule, bit for bit -----------------------------------------------------------------------------------------------
 def test_root_rule_bit_for_bit(orc):
-    eng = _setup_engine(32)
+    eng = setup_engine(32)
     valid = eng.valid_moves()
     r = np.random.default_rng(5).random((G, 43))
     eta = (r / r.sum(1, keepdims=True)).astype(f32)
@@ -45,7 +42,7 @@ def test_root_rule_bit_for_bit(orc):
             assert d.sum() == 1 and d[want] == 1, (i, g, want, plain, np.nonzero(d)[0])
             differs[g] += int(want != plain)
 
-    last = _stepped(eng, eta, 32, check)
+    last = stepped(eng, eta, 32, check)
     assert (last[0].sum(1) == 32).all()
     print("passes where the forced pick is not PUCT's, per game:", differs)
     assert (differs > 0).sum() >= G // 2, differs
@@ -89,7 +86,7 @@ def test_without_a_vector_forcing_runs_on_the_constant_form():
     that holds DIR_NOISE_VALUE in every entry"""
     got = []
     for vector in (False, True):
-        eng = _setup_engine(32)
+        eng = setup_engine(32)
         if vector:
             eng.set_root_noise(np.full((G, 43), eng.settings.dir_noise_value, f32))
         eng.set_forced_playouts(2.0)
@@ -102,7 +99,7 @@ def test_without_a_vector_forcing_runs_on_the_constant_form():
     for x, y in zip(*got):
         assert _bitwise(x, y)
     # ... and it is not the unforced search
-    eng = _setup_engine(32)
+    eng = setup_engine(32)
     eng.simulate()
     assert (eng.root_stats()[0] != got[0][0]).any()
     eng.close()
@@ -138,7 +135,7 @@ def test_forcing_acts_on_the_first_selection_of_a_descent_only():
 
 # ---- 4. pruning against the restatement ----------------------------------------------------------------------------------------------
 def test_pruned_policy_against_the_restatement_over_three_decisions():
-    eng = _setup_engine(32)
+    eng = setup_engine(32)
     eps, hp, k = eng.settings.dir_noise_epsi, eng.settings.hp_exploration, 2.0
     eng.set_forced_playouts(k)
     rng = np.random.default_rng(8)
@@ -175,99 +172,28 @@ def test_pruned_policy_against_the_restatement_over_three_decisions():
 BASE, NSEED, CSEED, SIMS, FAST, ALPHA, K, QUOTA = 9100, 77, 99, 16, 4, 0.3, 2.0, 4
 
 
-def _late_positions():
-    """four running positions 20 and 10 moves before the end of golden games that reach the last rounds: the games end soon"""
-    gold = np.load(os.path.join(T.GOLDEN, "rules_games.npz"))
-    ends = gold["starts"][1:]
-    idx = [ends[3] - 20, ends[13] - 20, ends[19] - 20, ends[3] - 10]
-    states = np.concatenate([gold["states"][idx], gold["states"][idx]]).copy()   # slots 4..7 idle under the quota
-    return states, np.arange(600, 600 + G, dtype=np.uint32)
-
-
-def _selfplay(threads, cap, prune, alpha=ALPHA):
+def _run(threads, cap, prune, alpha=ALPHA):
     """alpha = 0: azr_selfplay_set_dirichlet is never called (forced playouts in force, no Dirichlet noise set)"""
-    P = pkg()
-    eng = P.Engine(G, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=threads)
-    eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
-    states, rngs = _late_positions()
-    eng.set_states(states)
-    eng.set_rng(rngs)
-    if alpha:
-        eng.selfplay_set_dirichlet(alpha, NSEED)
-    eng.selfplay_set_forced_playouts(K, prune)
-    if cap:
-        eng.selfplay_set_playout_cap(0.5, FAST, CSEED)
-    eng.selfplay_start_games_from_states(BASE, QUOTA)
-    recs = []
-    for _ in range(400):
-        eng.selfplay_run(64)
+    return SR.Run(BASE, QUOTA, threads, SIMS, fast=FAST, cap=(0.5, CSEED) if cap else None, dirichlet=(alpha, NSEED) if alpha else None,
+                  forced=(K, prune))
+
+
+def _selfplay(threads, cap, prune, alpha):
+    def no_noise(i, eng):
         assert alpha or not eng.root_noise().any()                # no Dirichlet noise in force: azr_mcts_root_noise reads zeros
-        recs.append(eng.drain())
-        c = eng.counters()
-        if c["games_finished"] + c["errors"] >= QUOTA:
-            break
-    c = eng.counters()
-    assert c["games_finished"] == QUOTA and c["errors"] == 0 and c["nodes_dropped"] == 0 and c["records_dropped"] == 0, c
-    eng.close()
-    return np.concatenate(recs), c
 
-
-def _retrace(threads, cap, alpha=ALPHA):
-    """the same four games through azr_mcts_*: per decision the kind by the cap's coin, the vector of azr_debug_root_noise (or the
-    constant: a fast decision, and every decision with alpha = 0), the factor and the budget of that kind, one search, the pruned
-    policy into the record, the unpruned pick as the move"""
-    P = pkg()
-    eng = P.Engine(G, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=threads)
-    eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
-    states, rngs = _late_positions()
-    dnv, thr = f32(eng.settings.dir_noise_value), eng.settings.temperature_threshold
-    games, tot = [], dict(decisions=0, simulations=0, samples=0)
-    for g in range(QUOTA):
-        eng.set_states(np.repeat(states[g:g + 1], G, 0))          # every slot retraces game g; slot 0 is read
-        eng.set_rng(np.full(G, rngs[g], np.uint32))
-        eng.mcts_clear()
-        recs, d = [], 0
-        while True:
-            full = R.coin(0.5, CSEED, BASE + g, d) if cap else True
-            valid = eng.valid_moves()
-            eta = eng.debug_root_noise(alpha, NSEED, [BASE + g], [d], valid[:1]) if full and alpha else np.full((1, 43), dnv, f32)
-            eng.set_root_noise(np.repeat(eta, G, 0))
-            eng.set_forced_playouts(K if full else 0.0)
-            eng.set_simulations(SIMS if full else FAST)
-            eng.simulate()
-            st = eng.get_states()[0]
-            ppi = eng.pruned_policy()[0][0]
-            mv = eng.pick(sample=not (int(st[144]) + 256 * int(st[145]) > thr))
-            if full:
-                rec = np.zeros(265, np.uint8)
-                rec[0] = st[146]
-                rec[1:89] = eng.encode()[0]
-                rec[93:265] = ppi.view(np.uint8)
-                recs.append(rec)
-            assert (eng.make_moves(mv) == 0).all()
-            budget = SIMS if full else FAST
-            d += 1; tot["decisions"] += 1; tot["simulations"] += budget - budget % threads; tot["samples"] += int(full)
-            status = int(eng.status()[0])
-            if status != -1:
-                break
-            assert d < 2000
-        for rec in recs:
-            z = 0.0 if status == -2 else (1.0 if int(rec[0]) == status else -1.0)
-            rec[89:93] = np.array([z], f32).view(np.uint8)
-        games.append(np.array(recs, np.uint8).reshape(len(recs), 265))
+    eng = SR.selfplay(_run(threads, cap, prune, alpha))
+    out = SR.play_out(eng, QUOTA, 64, 400, after_run=no_noise)
     eng.close()
-    return games, tot
+    return out
 
 
 def _check_composition(threads, cap, alpha):
     recs, c = _selfplay(threads, cap, True, alpha)
-    games, tot = _retrace(threads, cap, alpha)
-    print("decisions per game:", [len(g) for g in games], tot)
-    blob = recs.tobytes()
-    for g, want in enumerate(games):
-        assert len(want) > 0 and want.tobytes() in blob, f"game {g}: its record stream is not in the device's output"
-    assert len(recs) == sum(len(g) for g in games)
-    assert {k: c[k] for k in tot} == tot
+    games, tot = SR.retrace(_run(threads, cap, True, alpha))
+    print("decisions per game:", [len(g.records) for g in games], tot)
+    SR.assert_streams(recs, c, [(g.records, None) for g in games], tot)
+    assert c["samples"] == tot["samples"]
     # pruning off: the same games, the same records outside pi
     plain, c0 = _selfplay(threads, cap, False, alpha)
     assert c0 == c and plain.shape == recs.shape

@@ -21,23 +21,6 @@ pytestmark = pytest.mark.gpu
 FM = T.data_field_mask()
 
 
-def host_stub_search(eng, orc, stub):
-    """azr_mcts_simulate with the NN seam served on the host by an oracle stub net"""
-    eng.mcts_begin()
-    pi = np.zeros((eng.G * eng.T, 43), np.float32)     # leaf slot = game * T + search thread
-    v = np.zeros(eng.G * eng.T, np.float32)
-    vv = C.c_float(0)
-    for _ in range(100000):
-        x, need, active = eng.mcts_leaves()
-        if active == 0:
-            return
-        for g in np.nonzero(need)[0]:
-            stub(None, x[g].ctypes.data_as(T.u8p), pi[g].ctypes.data_as(T.f32p), C.byref(vv))
-            v[g] = vv.value
-        eng.mcts_apply(pi, v)
-    raise AssertionError("search did not terminate")
-
-
 @pytest.mark.parametrize("stub_name,sims,threads", [("orc_hash_eval", 24, 1), ("orc_uniform_eval", 16, 1), ("orc_hash_eval", 100, 1),
                                                     ("orc_hash_eval", 25, 2), ("orc_uniform_eval", 16, 2),
                                                     ("orc_hash_eval", 102, 4), ("orc_uniform_eval", 23, 3)])
@@ -78,7 +61,7 @@ def search_decisions(orc, stub_name, sims, threads, states, decisions, **kw):
     d = np.zeros(160, np.uint8)
     for step in range(decisions):
         status = eng.status()
-        host_stub_search(eng, orc, stub)
+        T.host_stub_search(eng, orc, stub)
         n_gpu, q_gpu, p_gpu = eng.root_stats()
         pi_gpu = eng.policy()
         sample = step % 2 == 1
@@ -118,14 +101,14 @@ def test_player_seam_extra_trim_empties_the_tree(orc):
     eng = pkg().Engine(G, blocks=1, sims=sims, dtype=pkg().NET_F32)
     seeds = np.arange(900, 900 + G, dtype=np.uint32)
     eng.new_games(seeds)
-    host_stub_search(eng, orc, stub)
+    T.host_stub_search(eng, orc, stub)
     eng.mcts_trim()              # the player's own trim; the search's trim then drops everything
     rng = eng.get_rng()
-    host_stub_search(eng, orc, stub)
+    T.host_stub_search(eng, orc, stub)
     n1, _, _ = eng.root_stats()
     eng.mcts_clear()
     eng.set_rng(rng)
-    host_stub_search(eng, orc, stub)
+    T.host_stub_search(eng, orc, stub)
     n2, _, _ = eng.root_stats()
     assert (n1 == n2).all() and (n1.sum(1) == sims).all()
     eng.close()

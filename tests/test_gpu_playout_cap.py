@@ -11,28 +11,20 @@ import pytest
 
 import azr_testlib as T
 import playout_cap_ref as R
+import selfplay_retrace as SR
 from gpu_common import pkg
 
 pytestmark = pytest.mark.gpu
 BASE = 4242
 
 
-def _play(eng, games, base=BASE, quota=None, runs=400, passes=64):
-    """self-play until `games` games are over; (records, counters)"""
+def _selfplay(eng, games, quota=None, runs=400):
+    """self-play of new games (a quota of them, or without an end) until `games` games are over; (records, counters)"""
     if quota:
-        eng.selfplay_start_games(base, quota)
+        eng.selfplay_start_games(BASE, quota)
     else:
-        eng.selfplay_start(base)
-    recs = []
-    for _ in range(runs):
-        eng.selfplay_run(passes)
-        c = eng.counters()
-        recs.append(eng.drain())
-        if c["games_finished"] >= games:
-            break
-    c = eng.counters()
-    assert c["games_finished"] >= games and c["errors"] == 0 and c["nodes_dropped"] == 0 and c["records_dropped"] == 0, c
-    r = np.concatenate(recs)
+        eng.selfplay_start(BASE)
+    r, c = SR.play_out(eng, games, 64, runs, exact=bool(quota))
     assert len(r) == c["samples"]
     return r, c
 
@@ -49,7 +41,7 @@ def test_off_is_the_engine_that_never_called_it(threads):
         eng.set_weights(flat)
         if cap:
             eng.selfplay_set_playout_cap(*cap)
-        r, c = _play(eng, G)
+        r, c = _selfplay(eng, G)
         assert eng.decision_kind().all()
         out.append((r.tobytes(), c))
         eng.close()
@@ -108,7 +100,7 @@ def test_equal_budgets_only_gate_the_records(orc, threads):
         eng = P.Engine(G, blocks=1, sims=6, dtype=P.NET_F32, max_game_rounds=36, threads=threads)
         eng.set_weights(flat)
         eng.selfplay_set_playout_cap(prob, 6, 99)
-        out.append(_play(eng, G, quota=G))      # exactly the games of seeds BASE .. BASE + 5, each played to its end
+        out.append(_selfplay(eng, G, quota=G))      # exactly the games of seeds BASE .. BASE + 5, each played to its end
         eng.close()
     (all_recs, c1), (cap_recs, c2) = out
     assert c1["games_finished"] == c2["games_finished"] == G
@@ -132,7 +124,7 @@ def test_mixed_budgets_vs_oracle(threads):
     eng = P.Engine(G, blocks=1, sims=sims, dtype=P.NET_F32, max_game_rounds=36, threads=threads)
     eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
     eng.selfplay_set_playout_cap(0.5, fast, 99)
-    recs, c = _play(eng, G, quota=G)             # exactly the games of seeds BASE .. BASE + 5, each played to its end
+    recs, c = _selfplay(eng, G, quota=G)             # exactly the games of seeds BASE .. BASE + 5, each played to its end
     assert c["games_finished"] == G
     blob = recs.tobytes()
 
@@ -165,7 +157,7 @@ def test_capped_quota_selfplay_is_a_function_of_the_seeds_alone():
         eng = P.Engine(G, blocks=2, sims=8, dtype=P.NET_BF16, threads=2, max_game_rounds=40)
         eng.init_random(5)
         eng.selfplay_set_playout_cap(0.5, 2, 7)
-        r, c = _play(eng, N, quota=N, runs=4000)
+        r, c = _selfplay(eng, N, quota=N, runs=4000)
         assert c["games_finished"] == N and 0 < c["samples"] < c["decisions"]
         out.append((r[np.lexsort(r.T[::-1])], c["decisions"], c["simulations"]))   # records sorted bytewise
         eng.close()
@@ -255,6 +247,6 @@ def test_argument_checks_and_a_running_selfplay_never_sees_a_change():
     # the next start reads the setting: every decision is full again
     eng.selfplay_start(BASE)
     assert eng.decision_kind().all()
-    r, c = _play(eng, 1, runs=400)
+    r, c = _selfplay(eng, 1, runs=400)
     assert c["samples"] > 0 and len(r) == c["samples"]
     eng.close()

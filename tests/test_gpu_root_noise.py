@@ -10,16 +10,12 @@ import numpy as np
 import pytest
 
 import azr_testlib as T
-from gpu_common import pkg
-from test_gpu_mcts import host_stub_search
+from azr_testlib import bits, host_stub_search
+from gpu_common import pkg, setup_engine, stepped
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 FULL = (1 << 43) - 1
-
-
-def bits(mask):
-    return np.array([(int(mask) >> i) & 1 for i in range(43)], bool)
 
 
 # ---- 1. the constant vector is today's search ------------------------------------------------------------------------------
@@ -106,35 +102,8 @@ def puct_pick(orc, N, Q, Pr, valid, eta, eps, hp):
     return [m for m in order[:k] if m in ties][0]
 
 
-def _stepped(eng, eta, passes, check):
-    """begin / leaves / azr_nn_predict / apply one pass at a time; check(prev stats, new stats) between consecutive passes"""
-    eng.set_root_noise(eta)
-    eng.mcts_begin()
-    x, need, act = eng.mcts_leaves()          # setRootState's root expansion
-    eng.mcts_apply(*eng.predict(x))
-    x, need, act = eng.mcts_leaves()          # the root is in the tree, descent 1 waits for the net
-    prev = eng.root_stats()
-    assert (prev[0] == 0).all()
-    for i in range(passes):
-        assert act == eng.G
-        eng.mcts_apply(*eng.predict(x))
-        x, need, act = eng.mcts_leaves()
-        cur = eng.root_stats()
-        check(i, prev, cur)
-        prev = cur
-    return prev
-
-
-def _setup_engine(sims):
-    P = pkg()
-    eng = P.Engine(8, blocks=1, sims=sims, dtype=P.NET_F32, threads=1)
-    eng.set_weights(T.make_net_flat(1, seed=23, perturb_bn=True))
-    eng.new_games(np.arange(4100, 4108, dtype=np.uint32))   # setup phase: no descent of 24 ends in a finished game
-    return eng
-
-
 def test_root_formula_bit_for_bit_random_vector(orc):
-    eng = _setup_engine(24)
+    eng = setup_engine(24)
     valid = eng.valid_moves()
     r = np.random.default_rng(5).random((8, 43))
     eta = (r / r.sum(1, keepdims=True)).astype(f32)
@@ -147,14 +116,14 @@ def test_root_formula_bit_for_bit_random_vector(orc):
             d = cur[0][g].astype(np.int64) - prev[0][g].astype(np.int64)
             assert d.sum() == 1 and d[want] == 1, (i, g, want, np.nonzero(d)[0])
 
-    last = _stepped(eng, eta, 24, check)
+    last = stepped(eng, eta, 24, check)
     assert (last[0].sum(1) == 24).all()
     assert (eng.root_noise() == eta).all()
     eng.close()
 
 
 def test_root_formula_peaked_vector_is_visited_first(orc):
-    eng = _setup_engine(8)
+    eng = setup_engine(8)
     valid = eng.valid_moves()
     # the clean priors first (one search without noise), then 0.97 on the legal move with the lowest prior
     eng.set_root_noise(None)
@@ -177,7 +146,7 @@ def test_root_formula_peaked_vector_is_visited_first(orc):
             for g in range(8):
                 assert cur[0][g][low[g]] == 1 and cur[0][g].sum() == 1, g
 
-    _stepped(eng, eta, 1, check)
+    stepped(eng, eta, 1, check)
     eng.close()
 
 

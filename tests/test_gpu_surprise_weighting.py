@@ -3,19 +3,16 @@ contract is include/azr.h's; tests/surprise_ref.py restates it in np.float32.  C
 restatement, bit for bit; device self-play against the same games retraced decision by decision through the host-stepped entry points,
 each record repeated by the restatement's copy count (plain at one and two search threads, and with a playout cap, Dirichlet noise,
 forced playouts and pruning); weighting on against off; slot independence; off is the engine that never called it; argument checks.
-Engines of 8 games, one block, NET_F32, 8 simulations, on the late golden positions of the forced-playouts test."""
+Engines of 8 games, one block, NET_F32, 8 simulations, on the late golden positions of tests/selfplay_retrace.py."""
 import numpy as np
 import pytest
 
-import azr_testlib as T
-import playout_cap_ref as R
+import selfplay_retrace as SR
 import surprise_ref as S
-from gpu_common import pkg
-from test_gpu_forced_playouts import _late_positions
+from gpu_common import pi_of, pkg
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-G = 8
 BASE, NSEED, CSEED, SIMS, FAST, ALPHA, K, QUOTA = 9100, 77, 99, 8, 4, 0.3, 2.0, 4
 SHARE, MAXW, PSEED = 0.75, 4.0, 31
 
@@ -90,133 +87,40 @@ def test_the_rule_on_the_device_is_the_restatement(share, max_weight, seed):
 
 
 # ---- 2. self-play equals the host-stepped composition, each record repeated by its copy count -----------------------------------------
-def _engine(threads, slots=G):
-    P = pkg()
-    eng = P.Engine(slots, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=threads)
-    eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
-    return eng
-
-
-def _selfplay(threads, full, share, meddle=False):
-    """the four late games in device self-play; `full`: under a playout cap, Dirichlet noise, forced playouts and pruning; share = None:
-    the setter is never called.  meddle: weighting is switched on while the self-play runs (which must change nothing)"""
-    eng = _engine(threads)
-    states, rngs = _late_positions()
-    eng.set_states(states)
-    eng.set_rng(rngs)
-    if full:
-        eng.selfplay_set_dirichlet(ALPHA, NSEED)
-        eng.selfplay_set_forced_playouts(K, True)
-        eng.selfplay_set_playout_cap(0.5, FAST, CSEED)
-    if share is not None:
-        if meddle:
-            eng.selfplay_set_surprise_weighting(SHARE, MAXW, PSEED)   # a non-zero setting first, then off
-        eng.selfplay_set_surprise_weighting(share, MAXW, PSEED)
-    eng.selfplay_start_games_from_states(BASE, QUOTA)
-    recs = []
-    for i in range(400):
-        eng.selfplay_run(16)
-        if meddle and i == 0:
-            assert eng.counters()["games_finished"] < QUOTA
-            eng.selfplay_set_surprise_weighting(SHARE, MAXW, PSEED)
-        recs.append(eng.drain())
-        c = eng.counters()
-        if c["games_finished"] + c["errors"] >= QUOTA:
-            break
-    c = eng.counters()
-    assert c["games_finished"] == QUOTA and c["errors"] == 0 and c["nodes_dropped"] == 0 and c["records_dropped"] == 0, c
-    return np.concatenate(recs), c, eng
-
-
-def _retrace(threads, full):
-    """the same four games through azr_mcts_*, as the forced-playouts test retraces them, keeping each recorded decision's prior row
-    and legal moves: per game (records [n, 265], KL [n])"""
-    eng = _engine(threads)
-    states, rngs = _late_positions()
-    dnv, thr = f32(eng.settings.dir_noise_value), eng.settings.temperature_threshold
-    games, tot = [], dict(decisions=0, simulations=0)
-    for g in range(QUOTA):
-        eng.set_states(np.repeat(states[g:g + 1], G, 0))          # every slot retraces game g; slot 0 is read
-        eng.set_rng(np.full(G, rngs[g], np.uint32))
-        eng.mcts_clear()
-        recs, kls, d = [], [], 0
-        while True:
-            whole = R.coin(0.5, CSEED, BASE + g, d) if full else True
-            valid = eng.valid_moves()
-            if full:
-                eta = eng.debug_root_noise(ALPHA, NSEED, [BASE + g], [d], valid[:1]) if whole else np.full((1, 43), dnv, f32)
-                eng.set_root_noise(np.repeat(eta, G, 0))
-                eng.set_forced_playouts(K if whole else 0.0)
-                eng.set_simulations(SIMS if whole else FAST)
-            eng.simulate()
-            st = eng.get_states()[0]
-            prior = eng.root_stats()[2][0]
-            pi = eng.pruned_policy()[0][0] if full else eng.policy()[0]
-            mv = eng.pick(sample=not (int(st[144]) + 256 * int(st[145]) > thr))
-            if whole:
-                rec = np.zeros(265, np.uint8)
-                rec[0] = st[146]
-                rec[1:89] = eng.encode()[0]
-                rec[93:265] = pi.view(np.uint8)
-                recs.append(rec)
-                kls.append(S.record_kl(pi, prior, valid[0]))
-            assert (eng.make_moves(mv) == 0).all()
-            budget = SIMS if whole else FAST
-            d += 1; tot["decisions"] += 1; tot["simulations"] += budget - budget % threads
-            status = int(eng.status()[0])
-            if status != -1:
-                break
-            assert d < 2000
-        for rec in recs:
-            z = 0.0 if status == -2 else (1.0 if int(rec[0]) == status else -1.0)
-            rec[89:93] = np.array([z], f32).view(np.uint8)
-        games.append((np.array(recs, np.uint8).reshape(len(recs), 265), np.array(kls, f32)))
-    eng.close()
-    return games, tot
-
-
-_cache = {}
-
-
-def _cached(kind, threads, full):
-    key = (kind, threads, full)
-    if key not in _cache:
-        if kind == "retrace":
-            _cache[key] = _retrace(threads, full)
-        else:
-            recs, c, eng = _selfplay(threads, full, SHARE if kind == "on" else None)
-            eng.close()
-            _cache[key] = (recs, c)
-    return _cache[key]
+def _run(threads, full, on):
+    """the four late games; `full`: under a playout cap, Dirichlet noise, forced playouts and pruning; on = False: the setter is never
+    called"""
+    return SR.Run(BASE, QUOTA, threads, SIMS, surprise=(SHARE, MAXW, PSEED) if on else None,
+                  **(dict(fast=FAST, cap=(0.5, CSEED), dirichlet=(ALPHA, NSEED), forced=(K, True)) if full else {}))
 
 
 def _expected(threads, full):
-    """per game (records, copies) by the restatement, and the retrace's totals"""
-    games, tot = _cached("retrace", threads, full)
-    return [(recs, S.game_copies(kl, SHARE, MAXW, PSEED, BASE + g)[1]) for g, (recs, kl) in enumerate(games)], tot
+    """per game (records, copies) by the restatement on the retrace's policies and priors, and the retrace's totals"""
+    games, tot = SR.cached("retrace", _run(threads, full, True))
+    out = []
+    for g, game in enumerate(games):
+        kl = np.array([S.record_kl(pi, pr, va) for pi, pr, va in zip(pi_of(game.records), game.prior, game.valid)], f32)
+        out.append((game.records, S.game_copies(kl, SHARE, MAXW, PSEED, BASE + g)[1]))
+    return out, tot
 
 
 @pytest.mark.parametrize("threads,full", [(1, False), (2, False), (2, True)])
 def test_selfplay_is_the_host_stepped_composition_repeated_by_the_copies(threads, full):
-    recs, c = _cached("on", threads, full)
+    recs, c = SR.cached("selfplay", _run(threads, full, True))
     games, tot = _expected(threads, full)
     allc = np.concatenate([cp for _, cp in games])
     print("records per game:", [len(r) for r, _ in games], "copies:", [cp.tolist() for _, cp in games], tot)
     # a condition of the test, not a measurement: the games hold a record that is left out and one that is written more than once
     assert (allc == 0).any() and (allc >= 2).any(), np.bincount(allc)
-    blob = recs.tobytes()
-    for g, (want, cp) in enumerate(games):
-        stream = np.repeat(want, cp, axis=0)
-        assert len(want) > 0 and (len(stream) == 0 or stream.tobytes() in blob), f"game {g}: its weighted record stream is not in the device's output"
-    assert len(recs) == int(allc.sum()) == c["samples"]
-    assert {k: c[k] for k in tot} == tot
+    SR.assert_streams(recs, c, games, tot)
+    assert len(recs) == int(allc.sum())
 
 
 # ---- 3. on against off ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("threads,full", [(2, False), (2, True)])
 def test_weighting_only_repeats_and_leaves_out_records(threads, full):
-    on, c1 = _cached("on", threads, full)
-    off, c0 = _cached("off", threads, full)
+    on, c1 = SR.cached("selfplay", _run(threads, full, True))
+    off, c0 = SR.cached("selfplay", _run(threads, full, False))
     for key in ("games_finished", "decisions", "simulations", "evaluations", "levels"):
         assert c0[key] == c1[key], key
     assert c0["samples"] == len(off) and c1["samples"] == len(on)
@@ -239,51 +143,34 @@ def test_weighting_only_repeats_and_leaves_out_records(threads, full):
 
 # ---- 4. slot independence ---------------------------------------------------------------------------------------------------------
 def test_a_quota_writes_the_same_records_on_two_and_on_eight_slots():
-    P = pkg()
-    N, out = 6, []
-    for slots in (2, 8):
-        eng = P.Engine(slots, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=2, max_game_rounds=36)
-        eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
-        eng.selfplay_set_surprise_weighting(SHARE, MAXW, PSEED)
-        eng.selfplay_start_games(BASE, N)
-        recs = []
-        for _ in range(4000):
-            eng.selfplay_run(64)
-            recs.append(eng.drain())
-            c = eng.counters()
-            if c["games_finished"] + c["errors"] >= N:
-                break
-        assert c["games_finished"] == N and c["errors"] == 0 and c["records_dropped"] == 0, c
-        r = np.concatenate(recs)
-        assert len(r) == c["samples"]
-        out.append((r[np.lexsort(r.T[::-1])], c["decisions"], c["simulations"], c["samples"]))
-        eng.close()
-    print("records %d of %d decisions" % (out[0][3], out[0][1]))
-    assert out[0][0].shape == out[1][0].shape and len(out[0][0]) > 50 and out[0][3] != out[0][1]
-    assert (out[0][0] == out[1][0]).all() and out[0][1:] == out[1][1:]
+    _, decisions, _, samples = SR.quota_on_slots((2, 8), lambda eng: eng.selfplay_set_surprise_weighting(SHARE, MAXW, PSEED), SIMS, BASE)
+    print("records %d of %d decisions" % (samples, decisions))
+    assert samples != decisions
 
 
 # ---- 5. off is the engine that never called it ------------------------------------------------------------------------------------
 def test_off_is_the_engine_that_never_called_it():
-    never, c0 = _cached("off", 2, False)
-    recs, c, eng = _selfplay(2, False, 0.0, meddle=True)          # on, then off before the start; on again while it runs
+    def meddle(i, eng):
+        if i == 0:                                                # on again while it runs
+            assert eng.counters()["games_finished"] < QUOTA
+            eng.selfplay_set_surprise_weighting(SHARE, MAXW, PSEED)
+
+    def on_then_off(eng):                                         # a non-zero setting first, then off before the start
+        eng.selfplay_set_surprise_weighting(SHARE, MAXW, PSEED)
+        eng.selfplay_set_surprise_weighting(0.0, MAXW, PSEED)
+
+    run = _run(2, False, False)
+    never, c0 = SR.cached("selfplay", run)
+    eng = SR.selfplay(run, on_then_off)
+    recs, c = SR.play_out(eng, QUOTA, 16, 400, after_run=meddle)
     assert recs.tobytes() == never.tobytes() and c == c0
     # the next start reads the setting
-    states, rngs = _late_positions()
-    eng.set_states(states)
-    eng.set_rng(rngs)
-    eng.selfplay_start_games_from_states(BASE, QUOTA)
-    again = []
-    for _ in range(400):
-        eng.selfplay_run(16)
-        again.append(eng.drain())
-        c = eng.counters()
-        if c["games_finished"] + c["errors"] >= QUOTA:
-            break
+    SR.place(eng, run)
+    again, c = SR.play_out(eng, QUOTA, 16, 400)
     eng.close()
-    on, c1 = _cached("on", 2, False)
+    on, c1 = SR.cached("selfplay", _run(2, False, True))
     assert on.tobytes() != never.tobytes()
-    assert np.concatenate(again).tobytes() == on.tobytes() and c == c1
+    assert again.tobytes() == on.tobytes() and c == c1
 
 
 # ---- 6. argument errors -----------------------------------------------------------------------------------------------------------

@@ -13,28 +13,10 @@ import pytest
 import torch
 
 import azr_testlib as T
-from gpu_common import ROOT, pkg
+from gpu_common import ROOT, pkg, records
 
 pytestmark = pytest.mark.gpu
 import torch_train_ref as train
-
-
-def records(n, seed=0):
-    """synthetic (s, pi, z) records on real encoded positions: pi random over a random support, z in {-1, 0, 1}"""
-    g = np.load(os.path.join(T.GOLDEN, "encode.npz"))
-    x = g["in88"]
-    rng = np.random.default_rng(seed)
-    x = x[rng.integers(0, len(x), n)]
-    pi = rng.uniform(0.0, 1.0, (n, 43)).astype(np.float32) * (rng.uniform(0, 1, (n, 43)) < 0.3)
-    pi[:, 42] += 1e-3
-    pi = (pi / pi.sum(1, keepdims=True)).astype(np.float32)
-    z = rng.integers(-1, 2, n).astype(np.float32)
-    rec = np.zeros((n, 265), np.uint8)
-    rec[:, 0] = x[:, 42]
-    rec[:, 1:89] = x
-    rec[:, 89:93] = z.view(np.uint8).reshape(n, 4)
-    rec[:, 93:265] = pi.view(np.uint8).reshape(n, 172)
-    return rec
 
 
 def torch_step(blocks, flat, rec, margin=None):

@@ -7,9 +7,8 @@ import pytest
 import torch
 
 import azr_testlib as T
-from gpu_common import pkg
+from gpu_common import pkg, records
 import torch_train_ref as train
-from test_gpu_train import records
 
 pytestmark = pytest.mark.gpu
 AZR_E_INVALID_ARGUMENT, AZR_E_STATE = 1, 7   # include/azr.h

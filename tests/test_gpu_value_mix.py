@@ -4,16 +4,14 @@ for bit; azr_mcts_root_value against the restatement on azr_mcts_root_stats' row
 decision by decision through the host-stepped entry points with z' filled in by the restatement (plain at one and two search threads,
 with a playout cap, Dirichlet noise, forced playouts and pruning, and that again under surprise weighting: both flush paths); the mix
 on against off; slot independence; off is the engine that never called it; the arena never sees it; argument checks.
-Engines of 8 games, one block, NET_F32, 8 simulations, on the late golden positions of the forced-playouts test."""
+Engines of 8 games, one block, NET_F32, 8 simulations, on the late golden positions of tests/selfplay_retrace.py."""
 import numpy as np
 import pytest
 
-import azr_testlib as T
-import playout_cap_ref as R
+import selfplay_retrace as SR
 import surprise_ref as S
 import value_mix_ref as V
-from gpu_common import arena_play, pkg
-from test_gpu_forced_playouts import _late_positions
+from gpu_common import arena_play, pi_of, pkg
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -98,17 +96,10 @@ def test_the_rule_on_the_device_is_the_restatement(q_share):
 
 
 # ---- 2. azr_mcts_root_value ----------------------------------------------------------------------------------------------------------
-def _engine(threads, slots=G):
-    P = pkg()
-    eng = P.Engine(slots, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=threads)
-    eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
-    return eng
-
-
 @pytest.mark.parametrize("threads", [1, 2])
 def test_root_value_is_the_restatement_on_root_stats(threads):
-    eng = _engine(threads)
-    states, rngs = _late_positions()
+    eng = SR.engine(threads, SIMS)
+    states, rngs = SR.late_positions()
     eng.set_states(states)
     eng.set_rng(rngs)
     eng.mcts_clear()
@@ -127,112 +118,17 @@ def test_root_value_is_the_restatement_on_root_stats(threads):
 
 
 # ---- 3. self-play is the host-stepped retrace with z' filled in by the restatement ---------------------------------------------------
-def _selfplay(threads, full, q_share, psw=False, meddle=False):
-    """the four late games in device self-play; `full`: under a playout cap, Dirichlet noise, forced playouts and pruning; psw: with
-    surprise weighting; q_share = None: the setter is never called.  meddle: the mix is switched on, then off before the start, and on
-    again while the self-play runs (all of which must change nothing)"""
-    eng = _engine(threads)
-    states, rngs = _late_positions()
-    eng.set_states(states)
-    eng.set_rng(rngs)
-    if full:
-        eng.selfplay_set_dirichlet(ALPHA, NSEED)
-        eng.selfplay_set_forced_playouts(K, True)
-        eng.selfplay_set_playout_cap(0.5, FAST, CSEED)
-    if psw:
-        eng.selfplay_set_surprise_weighting(SHARE, MAXW, PSEED)
-    if q_share is not None:
-        if meddle:
-            eng.selfplay_set_value_mix(QSHARE)
-        eng.selfplay_set_value_mix(q_share)
-    eng.selfplay_start_games_from_states(BASE, QUOTA)
-    return _play_out(eng, meddle), eng
+def _run(threads, full, psw, on):
+    """the four late games; `full`: under a playout cap, Dirichlet noise, forced playouts and pruning; psw: with surprise weighting;
+    on = False: the setter is never called"""
+    return SR.Run(BASE, QUOTA, threads, SIMS, surprise=(SHARE, MAXW, PSEED) if psw else None, value_mix=QSHARE if on else None,
+                  **(dict(fast=FAST, cap=(0.5, CSEED), dirichlet=(ALPHA, NSEED), forced=(K, True)) if full else {}))
 
 
-def _play_out(eng, meddle=False):
-    recs = []
-    for i in range(400):
-        eng.selfplay_run(16)
-        if meddle and i == 0:
-            assert eng.counters()["games_finished"] < QUOTA
-            eng.selfplay_set_value_mix(QSHARE)
-        recs.append(eng.drain())
-        c = eng.counters()
-        if c["games_finished"] + c["errors"] >= QUOTA:
-            break
-    c = eng.counters()
-    assert c["games_finished"] == QUOTA and c["errors"] == 0 and c["nodes_dropped"] == 0 and c["records_dropped"] == 0, c
-    return np.concatenate(recs), c
-
-
-def _retrace(threads, full):
-    """the same four games through azr_mcts_*, as the surprise-weighting test retraces them, keeping at each recorded decision the root
-    value by the restatement from azr_mcts_root_stats' N and Q (and the surprise): per game (records [n, 265] with the bare z, z [n],
-    q [n], has_q [n], KL [n])"""
-    eng = _engine(threads)
-    states, rngs = _late_positions()
-    dnv, thr = f32(eng.settings.dir_noise_value), eng.settings.temperature_threshold
-    games, tot = [], dict(decisions=0, simulations=0)
-    for g in range(QUOTA):
-        eng.set_states(np.repeat(states[g:g + 1], G, 0))          # every slot retraces game g; slot 0 is read
-        eng.set_rng(np.full(G, rngs[g], np.uint32))
-        eng.mcts_clear()
-        recs, kls, qs, hs, d = [], [], [], [], 0
-        while True:
-            whole = R.coin(0.5, CSEED, BASE + g, d) if full else True
-            valid = eng.valid_moves()
-            if full:
-                eta = eng.debug_root_noise(ALPHA, NSEED, [BASE + g], [d], valid[:1]) if whole else np.full((1, 43), dnv, f32)
-                eng.set_root_noise(np.repeat(eta, G, 0))
-                eng.set_forced_playouts(K if whole else 0.0)
-                eng.set_simulations(SIMS if whole else FAST)
-            eng.simulate()
-            st = eng.get_states()[0]
-            n, qq, prior = (a[0] for a in eng.root_stats())
-            pi = eng.pruned_policy()[0][0] if full else eng.policy()[0]
-            mv = eng.pick(sample=not (int(st[144]) + 256 * int(st[145]) > thr))
-            if whole:
-                rec = np.zeros(265, np.uint8)
-                rec[0] = st[146]
-                rec[1:89] = eng.encode()[0]
-                rec[93:265] = pi.view(np.uint8)
-                recs.append(rec)
-                kls.append(S.record_kl(pi, prior, valid[0]))
-                q, has = V.root_value(n, qq, valid[0])
-                qs.append(q); hs.append(has)
-            assert (eng.make_moves(mv) == 0).all()
-            budget = SIMS if whole else FAST
-            d += 1; tot["decisions"] += 1; tot["simulations"] += budget - budget % threads
-            status = int(eng.status()[0])
-            if status != -1:
-                break
-            assert d < 2000
-        zs = []
-        for rec in recs:
-            z = 0.0 if status == -2 else (1.0 if int(rec[0]) == status else -1.0)
-            rec[89:93] = np.array([z], f32).view(np.uint8)
-            zs.append(z)
-        games.append((np.array(recs, np.uint8).reshape(len(recs), 265), np.array(zs, f32), np.array(qs, f32), np.array(hs, bool),
-                      np.array(kls, f32)))
-    eng.close()
-    return games, tot
-
-
-_cache = {}
-
-
-def _cached(kind, threads, full, psw=False):
-    key = (kind, threads, full, psw)
-    if kind == "retrace":
-        key = (kind, threads, full, False)
-    if key not in _cache:
-        if kind == "retrace":
-            _cache[key] = _retrace(threads, full)
-        else:
-            (recs, c), eng = _selfplay(threads, full, QSHARE if kind == "on" else None, psw)
-            eng.close()
-            _cache[key] = (recs, c)
-    return _cache[key]
+def _root_values(game):
+    """(q [n], has_q [n]) by the restatement from azr_mcts_root_stats' N and Q at the game's recorded decisions"""
+    qh = [V.root_value(n, qq, va) for n, qq, va in zip(game.N, game.Q, game.valid)]
+    return np.array([x[0] for x in qh], f32), np.array([x[1] for x in qh], bool)
 
 
 def _mixed(recs, z, q, has):
@@ -245,33 +141,33 @@ def _mixed(recs, z, q, has):
 
 @pytest.mark.parametrize("threads,full,psw", [(1, False, False), (2, False, False), (2, True, False), (2, True, True)])
 def test_selfplay_is_the_host_stepped_retrace_with_the_restated_blend(threads, full, psw):
-    recs, c = _cached("on", threads, full, psw)
-    games, tot = _cached("retrace", threads, full)
-    z, q, has = (np.concatenate([g[i] for g in games]) for i in (1, 2, 3))
+    recs, c = SR.cached("selfplay", _run(threads, full, psw, True))
+    games, tot = SR.cached("retrace", _run(threads, full, psw, True))
+    roots = [_root_values(g) for g in games]
+    z, q, has = np.concatenate([g.z for g in games]), np.concatenate([r[0] for r in roots]), np.concatenate([r[1] for r in roots])
     zz = np.array([V.blend(z[r], q[r], has[r], QSHARE) for r in range(len(z))], f32)
-    print("records per game:", [len(g[0]) for g in games], tot)
+    print("records per game:", [len(g.records) for g in games], tot)
     print("z = +1: %d, z = -1: %d, q against z: %d, z' != z: %d, |z' - z| mean %.3f" %
           ((z == 1).sum(), (z == -1).sum(), (q * z < 0).sum(), (zz != z).sum(), float(np.abs(zz - z).mean())))
     # conditions of the test, on the retrace: both outcomes, a root value that disagrees with the outcome, a blend that moves z
     assert (z == 1).any() and (z == -1).any(), z
     assert (q * z < 0).any(), (q, z)
     assert (zz != z).any() and has.all()
-    blob, total = recs.tobytes(), 0
-    for g, (want, gz, gq, gh, kl) in enumerate(games):
-        stream = _mixed(want, gz, gq, gh)
+    streams = []
+    for g, (game, (gq, gh)) in enumerate(zip(games, roots)):
+        copies = None
         if psw:
-            stream = np.repeat(stream, S.game_copies(kl, SHARE, MAXW, PSEED, BASE + g)[1], axis=0)
-        total += len(stream)
-        assert len(want) > 0 and (len(stream) == 0 or stream.tobytes() in blob), f"game {g}: its blended record stream is not in the device's output"
-    assert len(recs) == total == c["samples"]
-    assert {k: c[k] for k in tot} == tot
+            kl = np.array([S.record_kl(pi, pr, va) for pi, pr, va in zip(pi_of(game.records), game.prior, game.valid)], f32)
+            copies = S.game_copies(kl, SHARE, MAXW, PSEED, BASE + g)[1]
+        streams.append((_mixed(game.records, game.z, gq, gh), copies))
+    SR.assert_streams(recs, c, streams, tot)
 
 
 # ---- 4. on against off ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("threads,full,psw", [(2, False, False), (2, True, True)])
 def test_the_mix_changes_the_four_value_bytes_only(threads, full, psw):
-    on, c1 = _cached("on", threads, full, psw)
-    off, c0 = _cached("off", threads, full, psw)
+    on, c1 = SR.cached("selfplay", _run(threads, full, psw, True))
+    off, c0 = SR.cached("selfplay", _run(threads, full, psw, False))
     assert c0 == c1 and c0["samples"] == len(off) == len(on)
     mask = np.ones(265, bool); mask[89:93] = False
 
@@ -288,44 +184,33 @@ def test_the_mix_changes_the_four_value_bytes_only(threads, full, psw):
 
 # ---- 5. slot independence ---------------------------------------------------------------------------------------------------------
 def test_a_quota_writes_the_same_records_on_two_and_on_eight_slots():
-    P = pkg()
-    N, out = 6, []
-    for slots in (2, 8):
-        eng = P.Engine(slots, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=2, max_game_rounds=36)
-        eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
-        eng.selfplay_set_value_mix(QSHARE)
-        eng.selfplay_start_games(BASE, N)
-        recs = []
-        for _ in range(4000):
-            eng.selfplay_run(64)
-            recs.append(eng.drain())
-            c = eng.counters()
-            if c["games_finished"] + c["errors"] >= N:
-                break
-        assert c["games_finished"] == N and c["errors"] == 0 and c["records_dropped"] == 0, c
-        r = np.concatenate(recs)
-        assert len(r) == c["samples"]
-        out.append((r[np.lexsort(r.T[::-1])], c["decisions"], c["simulations"], c["samples"]))
-        eng.close()
-    z = out[0][0][:, 89:93].copy().view(f32)[:, 0]
-    print("records %d, of them with a z' outside {-1, 0, 1}: %d" % (out[0][3], int((~np.isin(z, [-1, 0, 1])).sum())))
-    assert out[0][0].shape == out[1][0].shape and len(out[0][0]) > 50 and (~np.isin(z, [-1, 0, 1])).any()
-    assert (out[0][0] == out[1][0]).all() and out[0][1:] == out[1][1:]
+    recs, _, _, samples = SR.quota_on_slots((2, 8), lambda eng: eng.selfplay_set_value_mix(QSHARE), SIMS, BASE)
+    z = recs[:, 89:93].copy().view(f32)[:, 0]
+    print("records %d, of them with a z' outside {-1, 0, 1}: %d" % (samples, int((~np.isin(z, [-1, 0, 1])).sum())))
+    assert (~np.isin(z, [-1, 0, 1])).any()
 
 
 # ---- 6. off is the engine that never called it ------------------------------------------------------------------------------------
 def test_off_is_the_engine_that_never_called_it():
-    never, c0 = _cached("off", 2, False)
-    (recs, c), eng = _selfplay(2, False, 0.0, meddle=True)        # on, then off before the start; on again while it runs
+    def meddle(i, eng):
+        if i == 0:                                                # on again while it runs
+            assert eng.counters()["games_finished"] < QUOTA
+            eng.selfplay_set_value_mix(QSHARE)
+
+    def on_then_off(eng):                                         # on, then off before the start
+        eng.selfplay_set_value_mix(QSHARE)
+        eng.selfplay_set_value_mix(0.0)
+
+    run = _run(2, False, False, False)
+    never, c0 = SR.cached("selfplay", run)
+    eng = SR.selfplay(run, on_then_off)
+    recs, c = SR.play_out(eng, QUOTA, 16, 400, after_run=meddle)
     assert recs.tobytes() == never.tobytes() and c == c0
     # the next start reads the setting
-    states, rngs = _late_positions()
-    eng.set_states(states)
-    eng.set_rng(rngs)
-    eng.selfplay_start_games_from_states(BASE, QUOTA)
-    again, c = _play_out(eng)
+    SR.place(eng, run)
+    again, c = SR.play_out(eng, QUOTA, 16, 400)
     eng.close()
-    on, c1 = _cached("on", 2, False)
+    on, c1 = SR.cached("selfplay", _run(2, False, False, True))
     assert on.tobytes() != never.tobytes()
     assert again.tobytes() == on.tobytes() and c == c1
 
@@ -333,8 +218,7 @@ def test_off_is_the_engine_that_never_called_it():
 # ---- 7. the arena never sees it ---------------------------------------------------------------------------------------------------
 def test_the_arena_never_sees_it():
     P = pkg()
-    eng = P.Engine(2, blocks=1, sims=SIMS, dtype=P.NET_F32, threads=2, max_game_rounds=36)
-    eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
+    eng = SR.engine(2, SIMS, 2, max_game_rounds=36)
     eng.selfplay_set_value_mix(QSHARE)
     res, _, recs, _ = arena_play(eng, P.PLAYER_ALPHAZERO, P.PLAYER_SCRIPT, 2, 0, False, BASE, az=True)
     eng.close()

@@ -22,7 +22,7 @@ def exe():
 
 
 def test_train_data_mode(exe, tmp_path):
-    from test_log_grammar import GR, check
+    from log_grammar import GR, check
     common = ["-m", "train-data", "--dgss", "8", "--dgsr", "8", "--blocks", "1", "--bs", "64", "--cg", "4", "--ct", "0",
               "--gpu-games", "16"]
     r0 = subprocess.run([exe, *common, "--dtl", "0"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
@@ -45,7 +45,7 @@ def test_train_data_mode(exe, tmp_path):
 
 
 def test_train_script_mode(exe, tmp_path):
-    from test_log_grammar import GR, check
+    from log_grammar import GR, check
     r = subprocess.run([exe, "-m", "train-script", "--ti", "1", "--tg", "2", "--mcts", "8", "--blocks", "1", "--bs", "64",
                         "--cg", "2", "--ct", "0"], cwd=tmp_path, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr + r.stdout[-2000:]

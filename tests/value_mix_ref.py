@@ -6,13 +6,10 @@ tests/test_value_mix_ref.py checks the restatement against float64 on the CPU; t
 for bit."""
 import numpy as np
 
+from azr_testlib import bits
+
 f32 = np.float32
 MOVES = 43
-
-
-def bits(valid):
-    """legal-move mask -> bool [43]"""
-    return np.array([(int(valid) >> m) & 1 for m in range(MOVES)], bool)
 
 
 def root_sums(N, Q, valid):

@@ -7,43 +7,15 @@ mean number of non-zero pi entries per written record.  Forcing changes the game
 the two forced runs do (pruning only rewrites pi), so their game and simulation counts agree.  There is no threshold.
     python tools/forced_playouts_bench.py [--slots 512] [--games 512] [--mcts 100] [-t 2] [--blocks 20] [--dir-alpha 0.3] [--forced-k 2]"""
 import argparse
-import importlib
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-P = importlib.import_module("alphazero-risk_amd")
-
-
-def run(eng, games, passes):
-    eng.selfplay_start_games(20260001, games)
-    n = nonzero = 0
-    t0 = time.perf_counter()
-    while True:
-        eng.selfplay_run(passes)
-        c = eng.counters()
-        r = eng.drain()
-        n += len(r)
-        if len(r):
-            nonzero += int((np.ascontiguousarray(r[:, 93:265]).view(np.float32) != 0).sum())
-        if c["games_finished"] + c["errors"] >= games:
-            break
-    dt = time.perf_counter() - t0
-    assert n == c["samples"] and c["errors"] == 0 and c["records_dropped"] == 0, c
-    return dt, c, nonzero / max(n, 1)
+from selfplay_quota import P, common_args, run_quota, warm_up
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--slots", type=int, default=512)
-    ap.add_argument("--games", type=int, default=512)
-    ap.add_argument("--mcts", type=int, default=100)
-    ap.add_argument("-t", type=int, default=2)
-    ap.add_argument("--blocks", type=int, default=20)
+    ap = argparse.ArgumentParser(parents=[common_args()])
     ap.add_argument("--dir-alpha", type=float, default=0.3)
     ap.add_argument("--dir-seed", type=int, default=7)
     ap.add_argument("--forced-k", type=float, default=2.0)
@@ -52,12 +24,11 @@ def main():
     eng.init_random(5)
     eng.selfplay_set_dirichlet(a.dir_alpha, a.dir_seed)
     rows = []
-    eng.selfplay_start_games(1, a.slots)   # warm-up: first launches, events and staging buffers
-    eng.selfplay_run(16)
-    eng.discard_samples()
+    warm_up(eng, a.slots)
     for name, k, prune in (("forcing off", 0.0, False), (f"k = {a.forced_k}", a.forced_k, False), (f"k = {a.forced_k}, pruned target", a.forced_k, True)):
         eng.selfplay_set_forced_playouts(k, prune)
-        dt, c, nz = run(eng, a.games, 4 * (a.mcts + 2))
+        dt, c, nonzero = run_quota(eng, a.games, 4 * (a.mcts + 2), lambda eng, r: int((np.ascontiguousarray(r[:, 93:265]).view(np.float32) != 0).sum()))
+        nz = sum(nonzero) / max(c["samples"], 1)
         rows.append(dict(config=name, slots=a.slots, games=c["games_finished"], decisions=c["decisions"], records=c["samples"],
                          simulations=c["simulations"], seconds=round(dt, 3), games_per_s=round(c["games_finished"] / dt, 2),
                          simulations_per_s=round(c["simulations"] / dt, 1), nonzero_pi_per_record=round(nz, 2)))

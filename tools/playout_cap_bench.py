@@ -7,38 +7,13 @@ ceiling: a decision costs S descents without the cap and P*S + (1-P)*F on averag
 S / (P*S + (1-P)*F).  There is no threshold.
     python tools/playout_cap_bench.py [--slots 512] [--games 512] [--mcts 100] [-t 2] [--blocks 20] [--cap-prob 0.25] [--cap-fast 20]"""
 import argparse
-import importlib
 import json
-import os
-import sys
-import time
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-P = importlib.import_module("alphazero-risk_amd")
-
-
-def run(eng, games, passes):
-    eng.selfplay_start_games(20260001, games)
-    n = 0
-    t0 = time.perf_counter()
-    while True:
-        eng.selfplay_run(passes)
-        c = eng.counters()
-        n += len(eng.drain())
-        if c["games_finished"] + c["errors"] >= games:
-            break
-    dt = time.perf_counter() - t0
-    assert n == c["samples"] and c["errors"] == 0 and c["records_dropped"] == 0, c
-    return dt, c
+from selfplay_quota import P, common_args, run_quota, warm_up
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--slots", type=int, default=512)
-    ap.add_argument("--games", type=int, default=512)
-    ap.add_argument("--mcts", type=int, default=100)
-    ap.add_argument("-t", type=int, default=2)
-    ap.add_argument("--blocks", type=int, default=20)
+    ap = argparse.ArgumentParser(parents=[common_args()])
     ap.add_argument("--cap-prob", type=float, default=0.25)
     ap.add_argument("--cap-fast", type=int, default=20)
     ap.add_argument("--cap-seed", type=int, default=7)
@@ -47,11 +22,10 @@ def main():
     eng.init_random(5)
     S, F = a.mcts - a.mcts % a.t, a.cap_fast - a.cap_fast % a.t
     rows = []
-    eng.selfplay_start_games(1, a.slots)   # warm-up: first launches, events and staging buffers
-    eng.selfplay_run(16)
+    warm_up(eng, a.slots)
     for name, prob, fast in (("cap off", 1.0, 0), (f"P = {a.cap_prob}, N = {a.cap_fast}", a.cap_prob, a.cap_fast)):
         eng.selfplay_set_playout_cap(prob, fast, a.cap_seed)
-        dt, c = run(eng, a.games, 4 * (a.mcts + 2))
+        dt, c, _ = run_quota(eng, a.games, 4 * (a.mcts + 2), lambda eng, r: len(r))
         rows.append(dict(config=name, slots=a.slots, games=c["games_finished"], decisions=c["decisions"], records=c["samples"],
                          simulations=c["simulations"], seconds=round(dt, 3), games_per_s=round(c["games_finished"] / dt, 2),
                          decisions_per_s=round(c["decisions"] / dt, 1), records_per_s=round(c["samples"] / dt, 1),

@@ -9,32 +9,11 @@ off-run wrote more than once — two decisions with the same position, policy an
 apart.)  There is no threshold.
     python tools/surprise_weighting_bench.py [--slots 512] [--games 512] [--mcts 100] [-t 2] [--blocks 20] [--psw-share 0.5] [--psw-max 4]"""
 import argparse
-import importlib
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-P = importlib.import_module("alphazero-risk_amd")
-
-
-def run(eng, games, passes):
-    eng.selfplay_start_games(20260001, games)
-    recs = []
-    t0 = time.perf_counter()
-    while True:
-        eng.selfplay_run(passes)
-        c = eng.counters()
-        recs.append(eng.drain())
-        if c["games_finished"] + c["errors"] >= games:
-            break
-    dt = time.perf_counter() - t0
-    recs = np.concatenate(recs)
-    assert len(recs) == c["samples"] and c["errors"] == 0 and c["records_dropped"] == 0, c
-    return dt, c, recs
+from selfplay_quota import P, common_args, run_quota, warm_up
 
 
 def rows_with_counts(recs):
@@ -44,26 +23,19 @@ def rows_with_counts(recs):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--slots", type=int, default=512)
-    ap.add_argument("--games", type=int, default=512)
-    ap.add_argument("--mcts", type=int, default=100)
-    ap.add_argument("-t", type=int, default=2)
-    ap.add_argument("--blocks", type=int, default=20)
+    ap = argparse.ArgumentParser(parents=[common_args()])
     ap.add_argument("--psw-share", type=float, default=0.5)
     ap.add_argument("--psw-max", type=float, default=4.0)
     ap.add_argument("--psw-seed", type=int, default=0)
     a = ap.parse_args()
     eng = P.Engine(a.slots, blocks=a.blocks, sims=a.mcts, dtype=P.NET_BF16, threads=a.t)
     eng.init_random(5)
-    eng.selfplay_start_games(1, a.slots)   # warm-up: first launches, events and staging buffers
-    eng.selfplay_run(16)
-    eng.discard_samples()
+    warm_up(eng, a.slots)
     rows, written = [], []
     for name, share in (("weighting off", 0.0), (f"share = {a.psw_share}, max = {a.psw_max}", a.psw_share)):
         eng.selfplay_set_surprise_weighting(share, a.psw_max, a.psw_seed)
-        dt, c, recs = run(eng, a.games, 4 * (a.mcts + 2))
-        written.append(rows_with_counts(recs))
+        dt, c, recs = run_quota(eng, a.games, 4 * (a.mcts + 2))
+        written.append(rows_with_counts(np.concatenate(recs)))
         rows.append(dict(config=name, slots=a.slots, games=c["games_finished"], decisions=c["decisions"], records=c["samples"],
                          simulations=c["simulations"], seconds=round(dt, 3), games_per_s=round(c["games_finished"] / dt, 2),
                          simulations_per_s=round(c["simulations"] / dt, 1)))

@@ -8,58 +8,28 @@ mean |z' - z|, a histogram of z', and the share of records whose root value q di
 from the pair as (z' - (1 - share) z) / share, up to rounding; a drawn game's records, z = 0, are counted apart).  There is no threshold.
     python tools/value_mix_bench.py [--slots 512] [--games 512] [--mcts 100] [-t 2] [--blocks 20] [--q-share 0.5] [--repeats 2]"""
 import argparse
-import importlib
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-P = importlib.import_module("alphazero-risk_amd")
-
-
-def run(eng, games, passes):
-    eng.selfplay_start_games(20260001, games)
-    recs, tree, launches = [], 0.0, 0
-    t0 = time.perf_counter()
-    while True:
-        eng.selfplay_run(passes)
-        c = eng.counters()
-        recs.append(eng.drain())
-        p = eng.profile_last_run()
-        tree += p["tree_ms"] * p["launches"]
-        launches += p["launches"]
-        if c["games_finished"] + c["errors"] >= games:
-            break
-    dt = time.perf_counter() - t0
-    recs = np.concatenate(recs)
-    assert len(recs) == c["samples"] and c["errors"] == 0 and c["records_dropped"] == 0, c
-    return dt, c, recs, tree / max(launches, 1)
+from selfplay_quota import P, common_args, run_quota, warm_up
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--slots", type=int, default=512)
-    ap.add_argument("--games", type=int, default=512)
-    ap.add_argument("--mcts", type=int, default=100)
-    ap.add_argument("-t", type=int, default=2)
-    ap.add_argument("--blocks", type=int, default=20)
+    ap = argparse.ArgumentParser(parents=[common_args()])
     ap.add_argument("--q-share", type=float, default=0.5)
     ap.add_argument("--repeats", type=int, default=2)
     a = ap.parse_args()
     eng = P.Engine(a.slots, blocks=a.blocks, sims=a.mcts, dtype=P.NET_BF16, threads=a.t)
     eng.init_random(5)
-    eng.selfplay_start_games(1, a.slots)   # warm-up: first launches, events and staging buffers
-    eng.selfplay_run(16)
-    eng.discard_samples()
+    warm_up(eng, a.slots)
     rows, recs = {"off": [], "on": []}, {}
     for rep in range(a.repeats):
         for name, share in (("off", 0.0), ("on", a.q_share)):
             eng.selfplay_set_value_mix(share)
-            dt, c, r, tree_ms = run(eng, a.games, 4 * (a.mcts + 2))
-            recs[name] = r
+            dt, c, drains = run_quota(eng, a.games, 4 * (a.mcts + 2), lambda eng, r: (r, eng.profile_last_run()))
+            recs[name] = np.concatenate([r for r, _ in drains])
+            tree_ms = sum(p["tree_ms"] * p["launches"] for _, p in drains) / max(sum(p["launches"] for _, p in drains), 1)
             rows[name].append(dict(config="mix " + name + ("" if name == "off" else f", q_share = {a.q_share}"), run=rep + 1, slots=a.slots,
                                    games=c["games_finished"], decisions=c["decisions"], records=c["samples"], simulations=c["simulations"],
                                    seconds=round(dt, 3), games_per_s=round(c["games_finished"] / dt, 2),
