@@ -46,6 +46,13 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ResignStats(C.Structure):   # azr_resign_stats
+    _fields_ = [(n, C.c_uint64) for n in ("resigned", "holdout_games", "holdout_would_resign", "holdout_not_lost")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)   # azr_allreduce_fn
 
 
@@ -89,6 +96,7 @@ EXPORTS = [
     "azr_selfplay_start_games_from_states",
     "azr_selfplay_set_surprise_weighting", "azr_debug_surprise_weights",
     "azr_selfplay_set_value_mix", "azr_mcts_root_value", "azr_debug_value_mix",
+    "azr_selfplay_set_resign", "azr_selfplay_resign_stats", "azr_selfplay_resign_state", "azr_debug_resign",
 ]
 
 
@@ -174,6 +182,11 @@ def load_library(test_hooks=False):
         L.azr_mcts_root_value.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.azr_debug_value_mix.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_selfplay_set_resign.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_uint32]
+        L.azr_selfplay_resign_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_selfplay_resign_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_debug_resign.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[test_hooks] = L
         if not test_hooks:
             _lib = L
@@ -552,6 +565,40 @@ class Engine:
         q, has, zz = np.zeros(rows, np.float32), np.zeros(rows, np.uint8), np.zeros(rows, np.float32)
         self._chk(self.L.azr_debug_value_mix(self.h, float(q_share), _p(N), _p(Q), _p(v), _p(z), rows, _p(q), _p(has), _p(zz)))
         return q, has.astype(bool), zz
+
+    # ---- resignation with a no-resign holdout (this engine's own; off = every game is played to its end)
+    def selfplay_set_resign(self, q_resign, streak, holdout_share=0.1, seed=0):
+        """device self-play: a player whose root value q stays below q_resign for `streak` of its own recorded decisions in a row gives
+        the game up; a game held out by the coin of (seed, game seed, holdout_share) plays on and counts in the holdout statistics;
+        streak <= 0 = off; read by selfplay_start*"""
+        self._chk(self.L.azr_selfplay_set_resign(self.h, float(q_resign), int(streak), float(holdout_share), int(seed)))
+
+    def selfplay_resign_stats(self):
+        """dict(resigned, holdout_games, holdout_would_resign, holdout_not_lost) since the self-play counters were reset"""
+        s = ResignStats()
+        self._chk(self.L.azr_selfplay_resign_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def selfplay_resign_state(self):
+        """(run [G, 2] uint8, first [G] uint8 with 255 = none, holdout [G] bool) of the slots' running games"""
+        run, first, hold = np.zeros((self.G, 2), np.uint8), np.zeros(self.G, np.uint8), np.zeros(self.G, np.uint8)
+        self._chk(self.L.azr_selfplay_resign_state(self.h, _p(run), _p(first), _p(hold)))
+        return run, first, hold.astype(bool)
+
+    def debug_resign(self, q_resign, streak, holdout_share, seed, q, has_q, player, game_len, game_seed):
+        """the rule alone, on the device: q, has_q, player [rows] hold the games' decisions one game after the other
+        (rows = sum(game_len)) -> (resign_row [games] int32 with -1 = never, resigner [games] uint8 with 255 = nobody, holdout [games] bool)"""
+        q = np.ascontiguousarray(q, np.float32)
+        hq = np.ascontiguousarray(has_q, np.uint8)
+        pl = np.ascontiguousarray(player, np.uint8)
+        n = np.ascontiguousarray(game_len, np.uint32)
+        s = np.ascontiguousarray(game_seed, np.uint32)
+        rows = int(n.sum())
+        assert q.shape == hq.shape == pl.shape == (rows,) and n.ndim == 1 and n.shape == s.shape
+        row, who, hold = np.zeros(len(n), np.int32), np.zeros(len(n), np.uint8), np.zeros(len(n), np.uint8)
+        self._chk(self.L.azr_debug_resign(self.h, float(q_resign), int(streak), float(holdout_share), int(seed), _p(q), _p(hq), _p(pl),
+                                          _p(n), _p(s), len(n), _p(row), _p(who), _p(hold)))
+        return row, who, hold.astype(bool)
 
     # ---- self-play
     def selfplay_start(self, base_seed=20260001):

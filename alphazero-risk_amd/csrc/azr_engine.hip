@@ -182,6 +182,9 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // QMIX (self-play only): the value mix of the records (azr_valuemix.hpp) — the root value q of every staged record, from the root's
 // unpruned N and its Q, is kept beside it, and both flush paths write z' = (1 - q_share) z + q_share q in place of z.  The search, the
 // moves, pi, the copies and every counter are the ones without it.
+// Resignation (self-play only; azr_resign.hpp) is no template argument: E.resign_streak is wave-uniform and read once per decision.  On,
+// a recorded decision updates the mover's run from the root value after its record is staged; a run that reaches the streak ends the
+// game there for the opponent, or, in a held-out game, is only remembered.  Off, the decision is the one without it.
 template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false, bool QMIX = false>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
@@ -220,8 +223,14 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             uint32_t N; uint64_t valid;
             uint32_t mv = NONE;
             float P = 0.0f;   // SURPRISE: the root's stored prior row
-            float Q = 0.0f;   // QMIX: the root's mean values
-            if (root_node(t, root, N, valid, QMIX ? &Q : nullptr, SURPRISE ? &P : nullptr) != NO_NODE) {
+            float Q = 0.0f;   // QMIX, resignation: the root's mean values
+            // resignation (azr_resign.hpp): a runtime setting, wave-uniform, looked at here once per decision; off, nothing below runs
+            const bool resign = E.resign_streak > 0;
+            const uint32_t mover = root.cur;
+            uint32_t rs = 0;          // the running game's runs and `first`
+            bool resigned = false;    // the mover gives the game up at this decision
+            if (resign) rs = rfl(E.resign_state[g]);
+            if (root_node(t, root, N, valid, (QMIX || resign) ? &Q : nullptr, SURPRISE ? &P : nullptr) != NO_NODE) {
                 float pi = root_policy(N, valid);
                 mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
                 if (FORCED && E.prune && (!CAP || full)) {   // the record's pi from N'; the move above is N's
@@ -231,14 +240,16 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                 if (SURPRISE && (!CAP || full)) stage_surprise(E, g, c, pi, P, valid);
                 if (QMIX && (!CAP || full)) stage_root_value(E, g, c, N, Q, valid);   // N is the unpruned count
                 if (!CAP || full) stage_sample(E, g, c, root, pi, k);
+                if (resign && (!CAP || full)) resigned = resign_decision(E, g, c, rs, mover, N, Q, valid);
             }
             TP(16);
-            if (mv != NONE) make_move(root, mv, R); else root.err = E_LOGIC;
+            if (resigned) { mv = NONE; root.rng = c.rng; }   // no pick, no rFloat (the pick's above is taken back), no move: the game ends at this root
+            else if (mv != NONE) make_move(root, mv, R); else root.err = E_LOGIC;
             c.last_move = mv;
             c.decisions++;
             k.dec++;
             c.rng = root.rng;
-            int st = root.err ? ST_NOT_ENDED : game_status(root, R);
+            int st = resigned ? 1 - (int)mover /* a win for the opponent */ : root.err ? ST_NOT_ENDED : game_status(root, R);
             TP(17);
             if (root.err || st != ST_NOT_ENDED) {
                 if (root.err) { k.err++; c.error = root.err; }
@@ -250,6 +261,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                         k.samples += c.nsamples;
                     }
                     k.games++;
+                    if (resign) resign_count_game(E, g, rs, resigned, !resigned && resign_holdout(E.resign_threshold, E.resign_seed, c.seed), st);
                 }
                 c.status = st;
                 selfplay_next_game(E, g, t, c, root);
@@ -384,6 +396,44 @@ __global__ __launch_bounds__(64) void k_debug_value_mix(float q_share, const uin
     }
 }
 
+// azr_selfplay_resign_state: each slot's runs, `first` and the holdout coin of its running game (an idle slot: 0, 0, none, not held out)
+__global__ __launch_bounds__(64) void k_resign_state(Dev E, uint8_t* run_out, uint8_t* first_out, uint8_t* holdout_out)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    const bool on = c.mode != 0;
+    const uint32_t rs = on ? rfl(E.resign_state[g]) : 0u;
+    if (lane_id() == 0) {
+        run_out[2 * g] = (uint8_t)(rs & 255u);
+        run_out[2 * g + 1] = (uint8_t)((rs >> 8) & 255u);
+        first_out[g] = (uint8_t)resign_first(rs);
+        holdout_out[g] = on && resign_holdout(E.resign_threshold, E.resign_seed, c.seed) ? 1 : 0;
+    }
+}
+
+// azr_debug_resign: the rule alone, one wave per game, through the device functions of the self-play step.  Game i's decisions are rows
+// first[i] .. first[i] + game_len[i] - 1 of q / has_q / player.
+__global__ __launch_bounds__(64) void k_debug_resign(float q_resign, uint32_t streak, uint32_t threshold, uint32_t seed, const float* q,
+                                                     const uint8_t* has_q, const uint8_t* player, const uint32_t* first, const uint32_t* game_len,
+                                                     const uint32_t* game_seed, int32_t* row_out, uint8_t* resigner_out, uint8_t* holdout_out)
+{
+    const size_t i = blockIdx.x;
+    const size_t r0 = rfl(first[i]);
+    const uint32_t n = rfl(game_len[i]);
+    uint32_t rs = 0, who = 255u;
+    int32_t row = -1;
+    for (uint32_t r = 0; r < n && row < 0; r++) {
+        const uint32_t p = rfl((uint32_t)player[r0 + r]) & 1u;
+        if (resign_update(rs, p, rdlf(q[r0 + r], 0), rfl((uint32_t)has_q[r0 + r]) != 0u, q_resign, streak)) { row = (int32_t)r; who = p; }
+    }
+    if (lane_id() == 0) {
+        row_out[i] = row;
+        resigner_out[i] = (uint8_t)who;
+        holdout_out[i] = resign_holdout(threshold, seed, rfl(game_seed[i])) ? 1 : 0;
+    }
+}
+
 __global__ __launch_bounds__(64) void k_pick(Dev E, int sample, uint8_t* moves)
 {
     const int g = blockIdx.x;
@@ -427,6 +477,7 @@ __global__ __launch_bounds__(64) void k_selfplay_start(Dev E, int keep)
         c.rng = s.rng;
         ws_store(s, E.state + (size_t)g * GREC);
     }
+    if (lane_id() == 0) E.resign_state[g] = 0u;   // resignation: no run, nobody first (azr_resign.hpp)
     ctl_store(c, &E.ctl[g]);
 }
 
@@ -661,6 +712,8 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     HIPCHK(h, dmalloc(&d.alog_rounds, G * ALOG));
     HIPCHK(h, dmalloc(&d.alog_final, G * ALOG * GREC));
     HIPCHK(h, dmalloc(&d.root_eta, G * MOVES));
+    HIPCHK(h, dmalloc(&d.resign_state, G));
+    HIPCHK(h, dmalloc(&d.resign_stats, G * 4));
     HIPCHK(h, hipMemsetAsync(d.root_eta, 0, G * MOVES * sizeof(float), h->stream));
     HIPCHK(h, hipMemsetAsync(d.state, 0, G * GREC, h->stream));
     HIPCHK(h, hipMemsetAsync(d.ctl, 0, G * sizeof(Ctl), h->stream));
@@ -671,6 +724,8 @@ static int engine_init(azr_engine* h, const azr_settings* s)
     HIPCHK(h, hipMemsetAsync(d.net_v, 0, GT * sizeof(float), h->stream));
     HIPCHK(h, hipMemsetAsync(d.ring_count, 0, 2 * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(d.counters, 0, (size_t)d.G * sizeof(Counters), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.resign_state, 0, G * sizeof(uint32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.resign_stats, 0, G * 4 * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(d.active, 0, sizeof(uint32_t), h->stream));
     int rc = net_alloc(h);
     if (rc) return rc;
@@ -689,7 +744,7 @@ extern "C" int azr_engine_destroy(azr_engine* h)
     void* ptrs[] = {d.sp_started, d.state, d.ctl, d.nodes, d.touch, d.nhash, d.table, d.freel, d.path, d.leaf_in, d.leaf_key,
                     d.leaf_valid, d.leaf_hash, d.net_pi, d.net_v, d.stage, d.ring, d.ring_count, d.counters, d.active,
                     d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final, d.root_eta, d.stage_kl,
-                    d.stage_q};
+                    d.stage_q, d.resign_state, d.resign_stats};
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : h->tree2) if (p) hipFree(p);
     if (d.leaf_list) hipFree(d.leaf_list);
@@ -1068,6 +1123,8 @@ static int full_prob_check(azr_engine* h, const char* who, float full_prob, cons
     return full_prob >= 0.0f ? AZR_OK : bad_argument(h, std::string(who) + ": full_prob must be a number >= 0" + note);   // (NaN fails)
 }
 static uint32_t cap_threshold_of(float full_prob) { return full_prob >= 1.0f ? (1u << 24) : (uint32_t)(full_prob * 16777216.0f); }
+// the holdout coin's threshold of a resignation's holdout_share in [0, 1] (2^24 at 1: every game is held out)
+static uint32_t resign_threshold_of(float holdout_share) { return (uint32_t)(holdout_share * 16777216.0f); }
 
 // The azr_selfplay_set_* options as they stand now, into what this self-play's steps carry (h->sp) and the Dev fields they read: a
 // running self-play never sees a setter's change.  The host-stepped options end here (root_eta is this self-play's from now on).
@@ -1088,6 +1145,10 @@ static void resolve_selfplay_options(azr_engine* h)
     d.psw_max = o.psw_max;
     d.psw_seed = o.psw_seed;
     d.q_share = o.q_share;
+    d.resign_streak = o.resign_streak;
+    d.resign_q = o.resign_q;
+    d.resign_threshold = resign_threshold_of(o.resign_holdout);
+    d.resign_seed = o.resign_seed;
     d.eta_const = 0;
 }
 
@@ -1105,6 +1166,7 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
     const unsigned long long started = quota ? std::min<unsigned long long>(quota, (unsigned long long)h->d.G) : 0ull;
     HIPCHK(h, hipMemcpyAsync(h->d.sp_started, &started, sizeof started, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d.counters, 0, (size_t)h->d.G * sizeof(Counters), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d.resign_stats, 0, (size_t)h->d.G * 4 * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(h->d.ring_count, 0, sizeof(unsigned long long), h->stream));
     LAUNCH(h, k_selfplay_start, h->d, keep);
     resolve_selfplay_options(h);
@@ -1346,6 +1408,106 @@ extern "C" int azr_debug_value_mix(azr_engine* h, float q_share, const uint32_t*
     D2H(h, q_out, oq.p, n * 4);
     D2H(h, has_q_out, oh.p, n);
     D2H(h, z_out, oz.p, n * 4);
+    SYNC(h);
+    return AZR_OK;
+}
+
+// ---- resignation ----------------------------------------------------------------------------------------
+// numbers; when on (streak > 0): q_resign in [-1, 1], streak <= 255, holdout_share in [0, 1]
+static int resign_check(azr_engine* h, const char* who, float q_resign, int streak, float holdout_share)
+{
+    if (q_resign != q_resign || holdout_share != holdout_share)
+        return bad_argument(h, std::string(who) + ": q_resign and holdout_share must be numbers");
+    if (streak <= 0) return AZR_OK;
+    if (!(q_resign >= -1.0f && q_resign <= 1.0f)) return bad_argument(h, std::string(who) + ": q_resign must lie in [-1, 1]");
+    if (streak > 255) return bad_argument(h, std::string(who) + ": streak must be at most 255 (<= 0 = off)");
+    if (!(holdout_share >= 0.0f && holdout_share <= 1.0f)) return bad_argument(h, std::string(who) + ": holdout_share must lie in [0, 1]");
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_set_resign(azr_engine* h, float q_resign, int streak, float holdout_share, uint32_t seed)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (int rc = resign_check(h, "azr_selfplay_set_resign", q_resign, streak, holdout_share)) return rc;
+    const bool on = streak > 0;
+    h->sp_set.resign_streak = on ? streak : 0;
+    h->sp_set.resign_q = on ? q_resign : 0.0f;
+    h->sp_set.resign_holdout = on ? holdout_share : 0.0f;
+    h->sp_set.resign_seed = seed;
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_resign_stats(azr_engine* h, azr_resign_stats* out)
+{
+    ENTER(h);
+    if (!out) return AZR_E_INVALID_ARGUMENT;
+    std::vector<unsigned long long> rows((size_t)h->d.G * 4);
+    D2H(h, rows.data(), h->d.resign_stats, rows.size() * sizeof(unsigned long long));
+    SYNC(h);
+    memset(out, 0, sizeof *out);
+    for (size_t g = 0; g < (size_t)h->d.G; g++) {
+        out->resigned += rows[g * 4]; out->holdout_games += rows[g * 4 + 1];
+        out->holdout_would_resign += rows[g * 4 + 2]; out->holdout_not_lost += rows[g * 4 + 3];
+    }
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_resign_state(azr_engine* h, uint8_t* run_host, uint8_t* first_host, uint8_t* holdout_host)
+{
+    ENTER(h);
+    if (!run_host || !first_host || !holdout_host) return AZR_E_INVALID_ARGUMENT;
+    const size_t G = (size_t)h->d.G;
+    if (h->mode != 2 || h->d.resign_streak <= 0) {
+        memset(run_host, 0, 2 * G); memset(first_host, 255, G); memset(holdout_host, 0, G);
+        return AZR_OK;
+    }
+    DevBuf br, bf, bh;
+    HIPCHK(h, br.alloc(2 * G)); HIPCHK(h, bf.alloc(G)); HIPCHK(h, bh.alloc(G));
+    LAUNCH(h, k_resign_state, h->d, (uint8_t*)br.p, (uint8_t*)bf.p, (uint8_t*)bh.p);
+    D2H(h, run_host, br.p, 2 * G);
+    D2H(h, first_host, bf.p, G);
+    D2H(h, holdout_host, bh.p, G);
+    SYNC(h);
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_resign(azr_engine* h, float q_resign, int streak, float holdout_share, uint32_t seed, const float* q,
+                                const uint8_t* has_q, const uint8_t* player, const uint32_t* game_len, const uint32_t* game_seed, int games,
+                                int32_t* resign_row_out, uint8_t* resigner_out, uint8_t* holdout_out)
+{
+    ENTER(h);
+    if (int rc = resign_check(h, "azr_debug_resign", q_resign, streak, holdout_share)) return rc;
+    if (streak <= 0) return bad_argument(h, "azr_debug_resign: streak must lie in [1, 255]");
+    if (games < 0 || (games > 0 && (!game_len || !game_seed || !resign_row_out || !resigner_out || !holdout_out))) return AZR_E_INVALID_ARGUMENT;
+    if (games == 0) return AZR_OK;
+    std::vector<uint32_t> first((size_t)games);
+    size_t rows = 0;
+    for (int i = 0; i < games; i++) {
+        first[i] = (uint32_t)rows;
+        rows += game_len[i];
+        if (rows > 0x7fffffffu) return bad_argument(h, "azr_debug_resign: more than 2^31 - 1 decisions");
+    }
+    if (rows > 0 && (!q || !has_q || !player)) return AZR_E_INVALID_ARGUMENT;
+    const size_t n = (size_t)games;
+    DevBuf bq, bh, bp, bf, bl, bs, orow, owho, ohold;
+    HIPCHK(h, bq.alloc(rows * 4)); HIPCHK(h, bh.alloc(rows)); HIPCHK(h, bp.alloc(rows));
+    HIPCHK(h, bf.alloc(n * 4)); HIPCHK(h, bl.alloc(n * 4)); HIPCHK(h, bs.alloc(n * 4));
+    HIPCHK(h, orow.alloc(n * 4)); HIPCHK(h, owho.alloc(n)); HIPCHK(h, ohold.alloc(n));
+    if (rows) {
+        H2D(h, bq.p, q, rows * 4);
+        H2D(h, bh.p, has_q, rows);
+        H2D(h, bp.p, player, rows);
+    }
+    H2D(h, bf.p, first.data(), n * 4);
+    H2D(h, bl.p, game_len, n * 4);
+    H2D(h, bs.p, game_seed, n * 4);
+    hipLaunchKernelGGL(k_debug_resign, dim3(games), dim3(64), 0, h->stream, q_resign, (uint32_t)streak, resign_threshold_of(holdout_share),
+                       seed, (const float*)bq.p, (const uint8_t*)bh.p, (const uint8_t*)bp.p, (const uint32_t*)bf.p, (const uint32_t*)bl.p,
+                       (const uint32_t*)bs.p, (int32_t*)orow.p, (uint8_t*)owho.p, (uint8_t*)ohold.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, resign_row_out, orow.p, n * 4);
+    D2H(h, resigner_out, owho.p, n);
+    D2H(h, holdout_out, ohold.p, n);
     SYNC(h);
     return AZR_OK;
 }
@@ -1627,6 +1789,7 @@ extern "C" int azr_arena_start(azr_engine* h, int player1, int player2, int game
     h->arena_pass = 0;
     HIPCHK(h, hipMemsetAsync(d.arena_res, 0, 8 * sizeof(int), h->stream));
     HIPCHK(h, hipMemsetAsync(d.counters, 0, (size_t)d.G * sizeof(Counters), h->stream));
+    HIPCHK(h, hipMemsetAsync(d.resign_stats, 0, (size_t)d.G * 4 * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(d.alog_status, 0, (size_t)d.G * ALOG, h->stream));
     LAUNCH(h, k_arena_start, d);
     SYNC(h);

@@ -140,6 +140,14 @@ struct Dev {
     // everything else: the offsets the kernels without it read stay where they were.
     float q_share;             // the share of the root value q in a record's z (0 = off)
     float* stage_q;            // [G][SCAP]  q of each staged record's root, NaN = none (allocated by the first azr_selfplay_start* that blends)
+    // resignation with a no-resign holdout (this engine's own; read by the self-play k_tree_step instantiations, once per decision;
+    // azr_resign.hpp).  No template argument: resign_streak is wave-uniform, and 0 leaves the step what it was.
+    int resign_streak;         // decisions in a row below resign_q after which their player gives up (0 = off)
+    float resign_q;            // the bound on the root value q
+    uint32_t resign_threshold; // (uint32_t)(holdout_share * 2^24): the holdout coin's
+    uint32_t resign_seed;      // the coin is keyed by (resign_seed, game seed)
+    uint32_t* resign_state;    // [G]  run[0] | run[1] << 8 | first << 16 of each slot's running game (azr_resign.hpp)
+    unsigned long long* resign_stats;   // [G][4]  resigned, holdout_games, holdout_would_resign, holdout_not_lost: per slot, summed by the host
 };
 constexpr int ALOG = 16;
 
@@ -154,7 +162,7 @@ struct HostOpts {
     int sims = 0;              // azr_mcts_set_simulations: the budget (0 = the settings')
 };
 // Device self-play, as the azr_selfplay_set_* setters leave them.  A running self-play never sees a change: azr_selfplay_start* resolves
-// them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune, psw_* and q_share.
+// them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune, psw_*, q_share and resign_*.
 struct SelfplayOpts {
     float alpha = 0.0f;        // azr_selfplay_set_dirichlet (0 = off)
     uint32_t noise_seed = 0;
@@ -167,6 +175,10 @@ struct SelfplayOpts {
     float psw_max = 1.0f;
     uint32_t psw_seed = 0;
     float q_share = 0.0f;      // azr_selfplay_set_value_mix (0 = off)
+    int resign_streak = 0;     // azr_selfplay_set_resign (0 = off)
+    float resign_q = 0.0f;
+    float resign_holdout = 0.0f;
+    uint32_t resign_seed = 0;
 };
 
 // folded network parameters on device

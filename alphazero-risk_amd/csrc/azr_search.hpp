@@ -5,6 +5,7 @@
 #include "azr_cap.hpp"
 #include "azr_noise.hpp"
 #include "azr_surprise.hpp"
+#include "azr_resign.hpp"
 
 namespace azr {
 
@@ -176,6 +177,22 @@ __device__ __forceinline__ void stage_root_value(const Dev& E, int g, const Ctl&
     bool has_q;
     const float q = root_value(N, Q, valid, has_q);
     if (lane_id() == 0) E.stage_q[(size_t)g * E.SCAP + c.nsamples] = has_q ? q : __uint_as_float(0x7FC00000u);
+}
+
+// Resignation at a recorded decision of player p of slot g's game, after its record has been staged: the rule of include/azr.h on the
+// root value of the finished search (N the unpruned count) and the slot's state `rs`, which goes back to memory.  True: the game ends
+// here, p gives it up.  A held-out game only remembers who would have been first.
+__device__ __forceinline__ bool resign_decision(const Dev& E, int g, const Ctl& c, uint32_t& rs, uint32_t p, uint32_t N, float Q, uint64_t valid)
+{
+    bool has_q;
+    const float q = root_value(N, Q, valid, has_q);
+    bool resigned = false;
+    if (resign_update(rs, p, q, has_q, E.resign_q, (uint32_t)E.resign_streak)) {
+        if (resign_holdout(E.resign_threshold, E.resign_seed, c.seed)) resign_note_first(rs, p);
+        else resigned = true;
+    }
+    if (lane_id() == 0) E.resign_state[g] = rs;
+    return resigned;
 }
 
 // Lists this slot's waiting leaves (leaf slot g * T + thread, in thread order) behind those of the slots that came first: one atomic per
@@ -351,9 +368,10 @@ __device__ __forceinline__ uint32_t root_node(const Tree& t, const WS& root, uin
 // the slot's next self-play game.  Unlimited mode: seeds base + g, base + G + g, ...  Quota mode (azr_selfplay_start_games,
 // Counter::hasNext of alphazero_trainer.cpp:83): the next game index is a ticket from one atomic counter — exactly
 // sp_quota games are started, seeds base .. base + sp_quota - 1, each game a function of its seed alone; a slot that
-// draws no ticket goes idle (mode 0).
+// draws no ticket goes idle (mode 0).  Under resignation the slot's runs and `first` start over with the game (azr_resign.hpp).
 __device__ __forceinline__ void selfplay_next_game(const Dev& E, int g, const Tree& t, Ctl& c, WS& root)
 {
+    if (E.resign_streak > 0 && lane_id() == 0) E.resign_state[g] = 0u;
     c.game_no++;
     c.seed = E.base_seed + c.game_no * (uint32_t)E.G + (uint32_t)g;
     if (E.sp_quota) {

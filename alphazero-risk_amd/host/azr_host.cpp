@@ -109,6 +109,10 @@ void Settings::init(int argc, char* argv[])
         {"psw-max", "[this build] cap on one record's weight under --psw-share (within [1, 64])", "4", false},
         {"psw-seed", "[this build] seed of the coin that rounds a record's weight to its copy count (independent of --seed, --dir-seed and --cap-seed)", std::to_string(PSW_SEED), false},
         {"q-share", "[this build] self-play value mix: share of the search's root value q in the records' value target, z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1; Lc0's q_ratio)", "0", false},
+        {"resign-q", "[this build] self-play resignation: the bound on the search's root value q; a player whose q stays below it for --resign-streak of its own recorded decisions in a row gives the game up (within [-1, 1]; AlphaGo Zero, KataGo)", "-0.9", false},
+        {"resign-streak", "[this build] decisions in a row below --resign-q after which their player resigns (0 = off: every game is played to its end; at most 255)", "0", false},
+        {"resign-holdout", "[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose (within [0, 1])", "0.1", false},
+        {"resign-seed", "[this build] seed of the coin that holds a game out of resignation (independent of --seed, --dir-seed, --cap-seed and --psw-seed)", std::to_string(RESIGN_SEED), false},
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -312,6 +316,37 @@ void Settings::init(int argc, char* argv[])
             exit(2);
         }
         Q_SHARE = (float)sh;
+    }
+    {
+        char* end = nullptr;
+        const std::string kv = get("resign-streak");
+        const long sk = strtol(kv.c_str(), &end, 10);
+        if (kv.empty() || *end != '\0' || sk < 0 || sk > 255) {
+            fprintf(stderr, "--resign-streak: '%s' is not a streak (a whole number in [0, 255]; 0 = off)\n", kv.c_str());
+            exit(2);
+        }
+        RESIGN_STREAK = (int)sk;
+        const std::string qv = get("resign-q");
+        const double rq = strtod(qv.c_str(), &end);
+        if (qv.empty() || *end != '\0' || !(rq >= -1.0) || rq > 1.0) {
+            fprintf(stderr, "--resign-q: '%s' is not a bound on the root value (a number in [-1, 1])\n", qv.c_str());
+            exit(2);
+        }
+        RESIGN_Q = (float)rq;
+        const std::string hv = get("resign-holdout");
+        const double ho = strtod(hv.c_str(), &end);
+        if (hv.empty() || *end != '\0' || !(ho >= 0.0) || ho > 1.0) {
+            fprintf(stderr, "--resign-holdout: '%s' is not a share (a number in [0, 1])\n", hv.c_str());
+            exit(2);
+        }
+        RESIGN_HOLDOUT = (float)ho;
+        const std::string dv = get("resign-seed");
+        const unsigned long long sd = dv.empty() || dv[0] == '-' ? 0 : strtoull(dv.c_str(), &end, 10);
+        if (dv.empty() || dv[0] == '-' || *end != '\0' || sd > 0xffffffffull) {
+            fprintf(stderr, "--resign-seed: '%s' is not a 32-bit seed\n", dv.c_str());
+            exit(2);
+        }
+        RESIGN_SEED = (uint32_t)sd;
     }
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
@@ -790,6 +825,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         e.check(azr_selfplay_set_surprise_weighting(e.h, SETTINGS.PSW_SHARE, SETTINGS.PSW_MAX, SETTINGS.PSW_SEED), "selfplay_set_surprise_weighting");
         // value mix of the generated games' records: --q-share 0 (default) writes the bare game outcome
         e.check(azr_selfplay_set_value_mix(e.h, SETTINGS.Q_SHARE), "selfplay_set_value_mix");
+        // resignation in the generated games: --resign-streak 0 (default) plays every game to its end
+        e.check(azr_selfplay_set_resign(e.h, SETTINGS.RESIGN_Q, SETTINGS.RESIGN_STREAK, SETTINGS.RESIGN_HOLDOUT, SETTINGS.RESIGN_SEED), "selfplay_set_resign");
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);
@@ -807,6 +844,7 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         }
         rep[i].games = c.games_finished; rep[i].decisions = c.decisions; rep[i].simulations = c.simulations;
         rep[i].samples = storageGroup[i].data.size(); rep[i].errors = c.errors;
+        e.check(azr_selfplay_resign_stats(e.h, &rep[i].resign), "resign_stats");
     });
     SelfPlayReport tot;
     tot.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -815,6 +853,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         trainStorage.extend(storageGroup[i]);
         tot.games += rep[i].games; tot.decisions += rep[i].decisions; tot.simulations += rep[i].simulations;
         tot.samples += rep[i].samples; tot.errors += rep[i].errors;
+        tot.resign.resigned += rep[i].resign.resigned; tot.resign.holdout_games += rep[i].resign.holdout_games;
+        tot.resign.holdout_would_resign += rep[i].resign.holdout_would_resign; tot.resign.holdout_not_lost += rep[i].resign.holdout_not_lost;
     }
     printf("\nGenerated %d new samples for total %d\n", int(trainStorage.data.size() - before), int(trainStorage.data.size()));
     return tot;
@@ -830,6 +870,14 @@ void AlphaZeroTrainer::train(std::shared_ptr<AlphaZeroNNGroup> trainGroup, std::
         printf("Self-play: %llu games, %llu decisions, %llu simulations in %.2f s  =>  %.0f simulations/s, %.2f games/s\n",
                (unsigned long long)r.games, (unsigned long long)r.decisions, (unsigned long long)r.simulations, r.seconds,
                r.simulations / r.seconds, r.games / r.seconds);
+        if (SETTINGS.RESIGN_STREAK > 0) {  // the holdout's false positives: would-be resigners that went on not to lose
+            const azr_resign_stats& s = r.resign;
+            printf("Resignation: %llu resigned, %llu held out, %llu of them would have resigned, %llu of those did not lose  =>  false-positive share ",
+                   (unsigned long long)s.resigned, (unsigned long long)s.holdout_games, (unsigned long long)s.holdout_would_resign,
+                   (unsigned long long)s.holdout_not_lost);
+            if (s.holdout_would_resign) printf("%.3f\n", (double)s.holdout_not_lost / (double)s.holdout_would_resign);
+            else printf("n/a\n");
+        }
         trainStorage.trimOldExamples();
         trainGroup->train(trainStorage.data, SETTINGS.EPOCHS);
         if (updateIfImprovement(trainGroup, generateGroup, true)) trainStorage.updateOldGamesIndex();

@@ -25,7 +25,7 @@ namespace azrhost {
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
 // `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2,
-// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap; --forced-k, --prune-target for forced playouts and policy target pruning; --psw-share, --psw-max, --psw-seed for policy surprise weighting of its records; --q-share for the value mix of their z), the others marked "[this build]" in --help.
+// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap; --forced-k, --prune-target for forced playouts and policy target pruning; --psw-share, --psw-max, --psw-seed for policy surprise weighting of its records; --q-share for the value mix of their z; --resign-q, --resign-streak, --resign-holdout, --resign-seed for resignation with a no-resign holdout), the others marked "[this build]" in --help.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:
@@ -85,6 +85,10 @@ public:
     float PSW_MAX = 4.0f;                // --psw-max: ... the cap on one record's weight ...
     uint32_t PSW_SEED = 0;               // --psw-seed: ... and the seed of the coin that rounds a weight to a copy count (self-play generation of -m train only, like --dir-alpha)
     float Q_SHARE = 0.0f;                // --q-share: value mix of the self-play records, the share of the root value q in z' = (1 - share) z + share q (0 = off; self-play generation of -m train only, like --dir-alpha)
+    float RESIGN_Q = -0.9f;              // --resign-q: resignation in the self-play games, the bound on the root value q ...
+    int RESIGN_STREAK = 0;               // --resign-streak: ... the decisions in a row below it after which their player gives up (0 = off) ...
+    float RESIGN_HOLDOUT = 0.1f;         // --resign-holdout: ... the share of the games that never resign and measure the rule's false positives ...
+    uint32_t RESIGN_SEED = 0;            // --resign-seed: ... and the seed of the coin that holds a game out (self-play generation of -m train only, like --dir-alpha)
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 
@@ -279,6 +283,7 @@ public:
 
 struct SelfPlayReport {
     uint64_t games = 0, decisions = 0, simulations = 0, samples = 0, errors = 0;
+    azr_resign_stats resign{};   // --resign-streak > 0: games given up, and what the held-out games would have done
     double seconds = 0;
 };
 

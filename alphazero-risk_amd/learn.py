@@ -200,6 +200,8 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         share = shard_mod.split_count(a.tg, world, rank)   # one self-play shard per GPU (alphazero_trainer.cpp:41-57)
         new_recs = [np.zeros((0, 265), np.uint8)]
         c = dict(games_finished=0, simulations=0, errors=0)
+        resign_on = getattr(a, "resign_streak", 0) > 0
+        rs = dict(resigned=0, holdout_games=0, holdout_would_resign=0, holdout_not_lost=0)
         if share > 0:
             # exactly `share` games, each played to its end (Counter::hasNext, alphazero_trainer.cpp:83); this rank's seed
             # stream continues where its previous iteration stopped, so no (iteration, rank) pair ever replays a game
@@ -208,6 +210,8 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
             gen.selfplay_set_forced_playouts(getattr(a, "forced_k", 0.0), getattr(a, "prune_target", 0))   # forced playouts / target pruning of the generated games only (0 / 0 = off)
             gen.selfplay_set_surprise_weighting(getattr(a, "psw_share", 0.0), getattr(a, "psw_max", 4.0), getattr(a, "psw_seed", 0))   # surprise weighting of the generated games' records only (0 = every record once)
             gen.selfplay_set_value_mix(getattr(a, "q_share", 0.0))   # value mix of the generated games' records only (0 = the bare game outcome)
+            gen.selfplay_set_resign(getattr(a, "resign_q", -0.9), getattr(a, "resign_streak", 0), getattr(a, "resign_holdout", 0.1),
+                                    getattr(a, "resign_seed", 0))   # resignation in the generated games only (streak 0 = every game to its end)
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -216,15 +220,22 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
                 new_recs.append(gen.drain())
             if c["records_dropped"]:
                 raise RuntimeError(f"{c['records_dropped']} self-play records were dropped: raise sample_capacity")
+            rs = gen.selfplay_resign_stats()
         new_recs = np.concatenate(new_recs)
         if dist is not None:   # the one exchange step of data generation: records of all shards, in rank order
             import torch
             new_recs = shard_mod.gather_records(torch.from_numpy(new_recs).to(cdev), dist).cpu().numpy()
             c = shard_mod.reduce_counters({k: c[k] for k in ("games_finished", "simulations")}, dist, device=cdev)
+            if resign_on:
+                rs = shard_mod.reduce_counters(rs, dist, device=cdev)
             log(f"Record exchange: all_gather + counter all_reduce, backend {dist.get_backend()}, tensors on {cdev}, world {world}")
         dt = time.time() - t0
         log(f"Generated {len(new_recs)} new samples for total {len(records) + len(new_recs)}  "
             f"[{c['games_finished']} games, {c['simulations'] / dt:.0f} simulations/s, {c['games_finished'] / dt:.2f} games/s]")
+        if resign_on:   # the holdout's false positives: would-be resigners that went on not to lose
+            fp = f"{rs['holdout_not_lost'] / rs['holdout_would_resign']:.3f}" if rs["holdout_would_resign"] else "n/a"
+            log(f"Resignation: {rs['resigned']} resigned, {rs['holdout_games']} held out, {rs['holdout_would_resign']} of them would have resigned, "
+                f"{rs['holdout_not_lost']} of those did not lose  =>  false-positive share {fp}")
         records = np.concatenate([records, new_recs])
         records, old_game_index = trim_old_examples(records, old_game_index, a.s, 16384 * a.bs)
         # ---- trainGroup->train (alphazero_gpu_cluster.cpp:221-231)
@@ -360,6 +371,15 @@ def main():
     ap.add_argument("--q-share", type=float, default=0.0,
                     help="[this build] self-play value mix: share of the search's root value q in the records' value target, "
                          "z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1)")
+    ap.add_argument("--resign-q", type=float, default=-0.9,
+                    help="[this build] self-play resignation: the bound on the search's root value q; a player whose q stays below it for "
+                         "--resign-streak of its own recorded decisions in a row gives the game up (within [-1, 1])")
+    ap.add_argument("--resign-streak", type=int, default=0,
+                    help="[this build] decisions in a row below --resign-q after which their player resigns (0 = off; at most 255)")
+    ap.add_argument("--resign-holdout", type=float, default=0.1,
+                    help="[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose "
+                         "(within [0, 1])")
+    ap.add_argument("--resign-seed", type=int, default=0, help="[this build] seed of the coin that holds a game out of resignation")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -389,6 +409,14 @@ def main():
         ap.error(f"--psw-seed: {a.psw_seed} is not a 32-bit seed")
     if not 0.0 <= a.q_share <= 1.0:   # (a NaN fails both comparisons)
         ap.error(f"--q-share: {a.q_share} is not a share (a number in [0, 1]; 0 = off)")
+    if not 0 <= a.resign_streak <= 255:
+        ap.error(f"--resign-streak: {a.resign_streak} is not a streak (a whole number in [0, 255]; 0 = off)")
+    if not -1.0 <= a.resign_q <= 1.0:
+        ap.error(f"--resign-q: {a.resign_q} is not a bound on the root value (a number in [-1, 1])")
+    if not 0.0 <= a.resign_holdout <= 1.0:
+        ap.error(f"--resign-holdout: {a.resign_holdout} is not a share (a number in [0, 1])")
+    if not 0 <= a.resign_seed <= 0xFFFFFFFF:
+        ap.error(f"--resign-seed: {a.resign_seed} is not a 32-bit seed")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():
         learn(a)

@@ -396,6 +396,67 @@ int azr_mcts_root_value(azr_engine* h, float* q_host /*[G]*/, uint8_t* has_q_hos
 int azr_debug_value_mix(azr_engine* h, float q_share, const uint32_t* N, const float* Q /*[rows][43]*/, const uint64_t* valid,
                         const float* z /*[rows]*/, int rows, float* q_out, uint8_t* has_q_out, float* z_out);
 
+/* ---- resignation with a no-resign holdout (this engine's own; off after azr_engine_create) ---------------------------
+ * The reference plays every self-play game to its last dice roll: a game that is decided long before it ends still pays
+ * mcts_simulations at each of its closing decisions.  With resignation (AlphaGo Zero, KataGo) a player whose root value stays below a
+ * bound for `streak` of its own recorded decisions in a row gives the game up.  A share of the games is held out: such a game never
+ * resigns, plays on, and reports at its natural end how often the player who would have resigned did not lose — the rule's false
+ * positives.  The search never depends on it: up to the decision at which it ends, a resigning game is the game without the feature,
+ * record for record but for z.
+ * All arithmetic is fp32.  q and has_q are those of the value mix (see "Root value of a finished search" above), from the root's
+ * unpruned N and its Q when the decision's search has finished.  p = the mover at the root, byte 0 of the record.
+ *
+ * Per-game state, zeroed when a game starts or is entered through azr_selfplay_start*_from_states: run[0], run[1], 8-bit counters that
+ * saturate at 255; first, one of {none, 0, 1}.
+ *
+ * Holdout coin of a game with seed s; mix as in the playout cap's coin:
+ *     k = mix(seed + 0x2545F491);   k = mix(k ^ s);   k = mix(k + 0x68E31DA4)
+ *     holdout  <=>  (k >> 8) < (uint32_t)(holdout_share * 16777216.0f)        (the threshold is computed once, on the host, in float)
+ * The coin is a function of (seed, s, holdout_share) alone: not of the slot, the number of games or threads or the pass schedule; it
+ * is recomputed from the game's seed and never stored, and nothing is drawn from the game's own RNG stream.  The two constants are
+ * none of the Dirichlet sampler's (0x9E3779B9, 0x85EBCA6B), the playout cap's (0xC2B2AE35, 0x27D4EB2F) or the copy coin's
+ * (0x165667B1, 0xD3A2646C).  holdout_share = 1 holds every game out, 0 none.
+ *
+ * At a decision — under a playout cap at a full decision only; a fast decision neither reads nor changes the state — after the
+ * decision's record (with its surprise and root value, if in force) has been staged as without the feature, and before the pick:
+ *     below  = has_q && q < q_resign
+ *     run[p] = below ? min(run[p] + 1, 255) : 0                               (the other player's run is untouched)
+ *     gives_up = run[p] >= streak
+ * gives_up in a game that is not held out: the game ends here — no pick, no rFloat, no move.  Its status is 1 - p, a win for the
+ * opponent; its staged records, the resigning decision's included, are flushed with that status through the flush of any finished game
+ * (so the value mix, surprise copies and `samples` work as for any finished game); `decisions` counts the resigning decision,
+ * `games_finished` the game (a quota run still ends at games_finished + errors == games); the slot takes its next game exactly as
+ * after a natural end.
+ * gives_up in a held-out game: nothing in play changes; if first is none, first = p.
+ * When a held-out game ends naturally with status st: holdout_games += 1; if first is not none, holdout_would_resign += 1, and if
+ * st != 1 - first (the would-be resigner won or drew) holdout_not_lost += 1.  A game abandoned on a rules error counts nowhere.
+ *
+ * Whether and where a game resigns is a function of its seed, its searches and the four arguments alone.  The arena (azr_arena_*),
+ * scripted collection and the host-stepped searches (azr_mcts_*) never see it.
+ *
+ * streak <= 0 = off (default).  q_resign is a plain bound on q (a typical value is -0.9; it may be positive).  Read by
+ * azr_selfplay_start*; a running self-play never sees a change.  AZR_E_INVALID_ARGUMENT, with a reason in azr_last_error, for a NaN,
+ * or — when on — q_resign outside [-1, 1], streak > 255 or holdout_share outside [0, 1]. */
+int azr_selfplay_set_resign(azr_engine* h, float q_resign, int streak, float holdout_share, uint32_t seed);
+typedef struct azr_resign_stats {
+    uint64_t resigned;              /* games that ended by resignation (they count in games_finished too) */
+    uint64_t holdout_games;         /* held-out games that ended naturally */
+    uint64_t holdout_would_resign;  /* ... of them, those in which a player reached the streak */
+    uint64_t holdout_not_lost;      /* ... of those, the ones the first such player won or drew: the false positives */
+} azr_resign_stats;
+/* Kept per game slot by the slot's own wavefront, without atomics, and summed here; reset wherever azr_selfplay_counters' are. */
+int azr_selfplay_resign_stats(azr_engine* h, azr_resign_stats* out);
+/* the state of each slot's running game: run_host [G][2], first_host [G] (255 = none), holdout_host [G] (the coin of the game's seed;
+ * 0 for a slot that has gone idle).  All 0 / 255 / 0 when resignation is off or the engine is not in self-play. */
+int azr_selfplay_resign_state(azr_engine* h, uint8_t* run_host /*[G][2]*/, uint8_t* first_host /*[G]*/, uint8_t* holdout_host /*[G]*/);
+/* the rule alone, on the device, one wavefront per game through the device functions of the self-play step: q, has_q, player [rows]
+ * hold the games' decisions one game after the other, rows = the sum of game_len[i], i < games; game_seed[i] = the game's seed s.
+ * resign_row_out [games] = the row within the game at which the streak is first reached, or -1; resigner_out [games] = that row's
+ * player, or 255 — both for held-out games too; holdout_out [games] = the coin.  streak in [1, 255]. */
+int azr_debug_resign(azr_engine* h, float q_resign, int streak, float holdout_share, uint32_t seed, const float* q, const uint8_t* has_q,
+                     const uint8_t* player /*[rows]*/, const uint32_t* game_len, const uint32_t* game_seed, int games,
+                     int32_t* resign_row_out, uint8_t* resigner_out, uint8_t* holdout_out /*[games]*/);
+
 /* ---- device-resident self-play (trainer move loop, alphazero_trainer.cpp:80-119) --------------------------- */
 /* (Re)start all G games: game g plays seeds base_seed + g, then base_seed + G + g, ... */
 int azr_selfplay_start(azr_engine* h, uint32_t base_seed);
