@@ -97,6 +97,8 @@ EXPORTS = [
     "azr_selfplay_set_surprise_weighting", "azr_debug_surprise_weights",
     "azr_selfplay_set_value_mix", "azr_mcts_root_value", "azr_debug_value_mix",
     "azr_selfplay_set_resign", "azr_selfplay_resign_stats", "azr_selfplay_resign_state", "azr_debug_resign",
+    "azr_selfplay_set_gumbel", "azr_mcts_set_gumbel", "azr_mcts_set_root_gumbel", "azr_mcts_root_gumbel", "azr_mcts_gumbel_policy",
+    "azr_mcts_gumbel_pick", "azr_debug_root_gumbel", "azr_debug_gumbel_select", "azr_debug_exp32",
 ]
 
 
@@ -187,6 +189,15 @@ def load_library(test_hooks=False):
         L.azr_selfplay_resign_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.azr_debug_resign.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_selfplay_set_gumbel.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_uint32]
+        L.azr_mcts_set_gumbel.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+        L.azr_mcts_set_root_gumbel.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_mcts_root_gumbel.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_mcts_gumbel_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.azr_mcts_gumbel_pick.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_debug_root_gumbel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.azr_debug_gumbel_select.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.azr_debug_exp32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _libs[test_hooks] = L
         if not test_hooks:
             _lib = L
@@ -599,6 +610,75 @@ class Engine:
         self._chk(self.L.azr_debug_resign(self.h, float(q_resign), int(streak), float(holdout_share), int(seed), _p(q), _p(hq), _p(pl),
                                           _p(n), _p(s), len(n), _p(row), _p(who), _p(hold)))
         return row, who, hold.astype(bool)
+
+    # ---- Gumbel root search with sequential halving (this engine's own; off = PUCT at the root and the visit distribution as pi)
+    def selfplay_set_gumbel(self, m, c_visit=50.0, c_scale=0.5, seed=0):
+        """device self-play: every root considers its m best moves by g + logit (g a Gumbel vector of (seed, game seed, decision)),
+        spends the budget on them by sequential halving, plays the most visited and records softmax(logit + sigma(completed Q));
+        m = 0 = off; read by selfplay_start*, which refuses it together with Dirichlet noise, a playout cap or forced playouts"""
+        self._chk(self.L.azr_selfplay_set_gumbel(self.h, int(m), float(c_visit), float(c_scale), int(seed)))
+
+    def set_gumbel(self, m, c_visit=50.0, c_scale=0.5):
+        """host-stepped searches: the same search under the vector of set_root_gumbel; m = 0 = off; clears the trees when it toggles"""
+        self._chk(self.L.azr_mcts_set_gumbel(self.h, int(m), float(c_visit), float(c_scale)))
+
+    def set_root_gumbel(self, g):
+        """g [G, 43] for the searches that follow, used as given; None = zeros"""
+        if g is None:
+            self._chk(self.L.azr_mcts_set_root_gumbel(self.h, None))
+            return
+        g = np.ascontiguousarray(g, np.float32)
+        assert g.shape == (self.G, MOVES)
+        self._chk(self.L.azr_mcts_set_root_gumbel(self.h, _p(g)))
+
+    def root_gumbel(self):
+        """the Gumbel vector in force at each game's current root, [G, 43]; zeros where none"""
+        g = np.zeros((self.G, MOVES), np.float32)
+        self._chk(self.L.azr_mcts_root_gumbel(self.h, _p(g)))
+        return g
+
+    def gumbel_policy(self):
+        """(pi [G, 43], completed Q [G, 43]) of the last search's roots, as a self-play decision records them"""
+        pi, q = np.zeros((self.G, MOVES), np.float32), np.zeros((self.G, MOVES), np.float32)
+        self._chk(self.L.azr_mcts_gumbel_policy(self.h, _p(pi), _p(q)))
+        return pi, q
+
+    def gumbel_pick(self):
+        """the Gumbel decision's move of every game, [G] uint8; nothing is drawn"""
+        m = np.zeros(self.G, np.uint8)
+        self._chk(self.L.azr_mcts_gumbel_pick(self.h, _p(m)))
+        return m
+
+    def debug_root_gumbel(self, seed, game_seed, decision, valid, greedy):
+        """the draw alone: one vector per (game_seed[i], decision[i], valid[i], greedy[i]) -> [n, 43]"""
+        s = np.ascontiguousarray(game_seed, np.uint32)
+        d = np.ascontiguousarray(decision, np.uint32)
+        v = np.ascontiguousarray(valid, np.uint64)
+        gr = np.ascontiguousarray(greedy, np.uint8)
+        assert s.ndim == 1 and s.shape == d.shape == v.shape == gr.shape
+        g = np.zeros((len(s), MOVES), np.float32)
+        self._chk(self.L.azr_debug_root_gumbel(self.h, int(seed), _p(s), _p(d), _p(v), _p(gr), len(s), _p(g)))
+        return g
+
+    def debug_gumbel_select(self, m, n, c_visit, c_scale, N, N0, act, Q, P, g, vhat, valid, claim):
+        """the root-level selection alone on synthetic rows: N, N0, act, Q, P, g [rows, 43], vhat, valid, claim [rows] -> (move, cv)"""
+        N, N0, act = (np.ascontiguousarray(a, np.uint32) for a in (N, N0, act))
+        Q, P, g, vhat = (np.ascontiguousarray(a, np.float32) for a in (Q, P, g, vhat))
+        v = np.ascontiguousarray(valid, np.uint64)
+        c = np.ascontiguousarray(claim, np.uint32)
+        rows = len(v)
+        assert N.shape == N0.shape == act.shape == Q.shape == P.shape == g.shape == (rows, MOVES) and vhat.shape == c.shape == (rows,)
+        mv, cv = np.zeros(rows, np.uint8), np.zeros(rows, np.uint32)
+        self._chk(self.L.azr_debug_gumbel_select(self.h, int(m), int(n), float(c_visit), float(c_scale), _p(N), _p(N0), _p(act), _p(Q), _p(P),
+                                                 _p(g), _p(vhat), _p(v), _p(c), rows, _p(mv), _p(cv)))
+        return mv, cv
+
+    def debug_exp32(self, x):
+        """the engine's exponential alone, on the device"""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros(x.shape, np.float32)
+        self._chk(self.L.azr_debug_exp32(self.h, _p(x), x.size, _p(out)))
+        return out
 
     # ---- self-play
     def selfplay_start(self, base_seed=20260001):

@@ -185,11 +185,15 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // Resignation (self-play only; azr_resign.hpp) is no template argument: E.resign_streak is wave-uniform and read once per decision.  On,
 // a recorded decision updates the mover's run from the root value after its record is staged; a run that reaches the streak ends the
 // game there for the opponent, or, in a held-out game, is only remembered.  Off, the decision is the one without it.
-template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false, bool QMIX = false>
+// GUMBEL (without NOISE, CAP and FORCED): the Gumbel root search (azr_gumbel.hpp) — at path depth 0 the descents select by
+// gumbel_select_root under the root's vector g (E.root_g; self-play: a draw per new root), an expanded node keeps the net's value, and
+// a self-play decision takes gumbel_move and stages gumbel_policy, without an rFloat.  Staging, z back-fill, turnover, quota, surprise
+// weighting, value mix and resignation work on what they are handed.
+template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false, bool QMIX = false, bool GUMBEL = false>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
-    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED) && (SELFPLAY || !SURPRISE) && (SELFPLAY || !QMIX),
-                  "CAP, SURPRISE and QMIX need SELFPLAY, FORCED implies NOISE: launch_tree_step lists the twenty-seven");
+    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED) && (SELFPLAY || !SURPRISE) && (SELFPLAY || !QMIX) && (!GUMBEL || (!NOISE && !CAP && !FORCED)),
+                  "CAP, SURPRISE and QMIX need SELFPLAY, FORCED implies NOISE, GUMBEL excludes NOISE, CAP and FORCED: launch_tree_step lists the thirty-two");
     __shared__ int8_t scratch[128];
     const int g = blockIdx.x;
     TP_BEGIN();
@@ -212,8 +216,9 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
     float eta = 0.0f;
     if (NOISE) eta = E.root_eta[(size_t)g * MOVES + (lane_id() < MOVES ? lane_id() : 0)];
     if (FORCED && !SELFPLAY && E.eta_const) eta = E.noise_value;   // host-stepped, no vector set: the constant form
+    if (GUMBEL) eta = E.root_g[(size_t)g * MOVES + (lane_id() < MOVES ? lane_id() : 0)];   // the root's g travels where eta would
     TP(0);
-    consume_pending(E, g, t, c, k);
+    consume_pending<GUMBEL>(E, g, t, c, k);
     for (;;) {
         TP(6);
         if ((int)c.sims_done >= (CAP ? Sd.simulations : S.simulations)) {
@@ -230,9 +235,20 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             uint32_t rs = 0;          // the running game's runs and `first`
             bool resigned = false;    // the mover gives the game up at this decision
             if (resign) rs = rfl(E.resign_state[g]);
-            if (root_node(t, root, N, valid, (QMIX || resign) ? &Q : nullptr, SURPRISE ? &P : nullptr) != NO_NODE) {
-                float pi = root_policy(N, valid);
-                mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
+            if (root_node(t, root, N, valid, (GUMBEL || QMIX || resign) ? &Q : nullptr, (GUMBEL || SURPRISE) ? &P : nullptr) != NO_NODE) {
+                float pi;
+                if (GUMBEL) {   // no rFloat: the move is a function of the search and g; one score serves the move and the record
+                    // (the node is looked up again, as for the pruned counts below: keeping root_node's index in a variable, in any form,
+                    //  moves one s_mov in three of the existing SURPRISE steps, and those stay the parent's instruction for instruction)
+                    const uint32_t rkd = ws_record_dword(root);
+                    const uint32_t ridx = tree_lookup(t, rkd, key_hash(t, rkd));
+                    const GumbelScore sc = gumbel_score(N, Q, P, node_vhat(t, ridx), valid, E.gumbel_cvisit, E.gumbel_cscale);
+                    mv = gumbel_move(sc, N, E.root_n0[(size_t)g * MOVES + (lane_id() < MOVES ? lane_id() : 0)], eta, valid);
+                    pi = gumbel_policy(sc, valid);
+                } else {
+                    pi = root_policy(N, valid);
+                    mv = (int)root.round > S.temperature_threshold ? pick_highest(pi) : pick_random(root, pi);
+                }
                 if (FORCED && E.prune && (!CAP || full)) {   // the record's pi from N'; the move above is N's
                     const uint32_t rkd = ws_record_dword(root);
                     pi = root_policy(root_pruned_counts(E, S, t, tree_lookup(t, rkd, key_hash(t, rkd)), N, valid, eta, E.forced_k), valid);
@@ -270,13 +286,14 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             TP(18);
             if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
             if (NOISE) eta = new_root_noise<CAP, FORCED>(E, g, c, root, full);   // the next decision's root, or the next game's first
+            if (GUMBEL) eta = new_root_gumbel(E, g, c, root);
             if (c.mode == 0) break;  // quota exhausted: the slot idles
             tree_trim(t, c);
             c.sims_done = 0; c.sims_started = 0;
             TP(14);
         }
         uint32_t err = 0;
-        int r = search_round<NOISE, FORCED>(E, CAP ? Sd : S, g, t, c, root, scratch, k, err, eta, (FORCED && (!CAP || full)) ? E.forced_k : 0.0f);
+        int r = search_round<NOISE, FORCED, GUMBEL>(E, CAP ? Sd : S, g, t, c, root, scratch, k, err, eta, (FORCED && (!CAP || full)) ? E.forced_k : 0.0f);
         if (r == RD_LEAF) break;
         if (r == RD_FAIL) {
             k.err++;
@@ -286,6 +303,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
                 root_dirty = true;
                 if (CAP) { full = cap_full(E.cap_threshold, E.cap_seed, c.seed, c.decisions); Sd.simulations = full ? S.simulations : E.cap_fast; }
                 if (NOISE) eta = new_root_noise<CAP, FORCED>(E, g, c, root, full);
+                if (GUMBEL) eta = new_root_gumbel(E, g, c, root);
                 if (c.mode == 0) break;
                 tree_trim(t, c);
                 continue;
@@ -569,6 +587,91 @@ __global__ __launch_bounds__(64) void k_debug_root_noise(float alpha, uint32_t n
     if (lane_id() < MOVES) out[i * MOVES + lane_id()] = eta;
 }
 
+// the first root's g of every slot (azr_selfplay_start* whose steps carry GUMBEL), as k_selfplay_noise is the first root's eta
+__global__ __launch_bounds__(64) void k_selfplay_gumbel(Dev E)
+{
+    const int g = blockIdx.x;
+    Ctl c;
+    ctl_load(c, &E.ctl[g]);
+    WS root;
+    ws_load(root, E.state + (size_t)g * GREC);
+    new_root_gumbel(E, g, c, root);
+}
+
+// the rows of game g's root a Gumbel decision reads (false: the root is not in the tree)
+struct GumbelRoot { uint32_t N, N0; float Q, P, g, vhat; uint64_t valid; };
+__device__ __forceinline__ bool gumbel_root(const Dev& E, int g, GumbelRoot& r)
+{
+    Tree t = tree_of(E, g);
+    WS root;
+    ws_load(root, E.state + (size_t)g * GREC);
+    r.Q = r.P = r.g = r.vhat = 0.0f; r.N0 = 0;
+    const uint32_t ridx = root_node(t, root, r.N, r.valid, &r.Q, &r.P);
+    if (ridx == NO_NODE) return false;
+    const uint32_t ll = lane_id() < MOVES ? lane_id() : 0;
+    r.N0 = E.root_n0[(size_t)g * MOVES + ll];
+    r.g = E.root_g[(size_t)g * MOVES + ll];
+    r.vhat = node_vhat(t, ridx);
+    return true;
+}
+
+// azr_mcts_gumbel_policy: the record's pi and (optional) the completed Q of every game's root, as the self-play decision computes them
+__global__ __launch_bounds__(64) void k_gumbel_policy(Dev E, float* qhat_out, float* pi_out)
+{
+    const int g = blockIdx.x;
+    GumbelRoot r;
+    float pi = 0.0f, qhat = 0.0f;
+    if (gumbel_root(E, g, r)) pi = gumbel_policy(gumbel_score(r.N, r.Q, r.P, r.vhat, r.valid, E.gumbel_cvisit, E.gumbel_cscale), r.valid, &qhat);
+    const uint32_t l = lane_id();
+    if (l < MOVES) {
+        pi_out[(size_t)g * MOVES + l] = pi;
+        if (qhat_out) qhat_out[(size_t)g * MOVES + l] = qhat;
+    }
+}
+
+// azr_mcts_gumbel_pick: the move of every game's decision (NONE for a root that is not in the tree); nothing is drawn
+__global__ __launch_bounds__(64) void k_gumbel_pick(Dev E, uint8_t* moves)
+{
+    const int g = blockIdx.x;
+    GumbelRoot r;
+    uint32_t mv = NONE;
+    if (gumbel_root(E, g, r)) mv = gumbel_move(gumbel_score(r.N, r.Q, r.P, r.vhat, r.valid, E.gumbel_cvisit, E.gumbel_cscale), r.N, r.N0, r.g, r.valid);
+    if (lane_id() == 0) moves[g] = (uint8_t)mv;
+}
+
+// azr_debug_root_gumbel: the draw alone, one wave per vector
+__global__ __launch_bounds__(64) void k_debug_root_gumbel(uint32_t seed, const uint32_t* game_seed, const uint32_t* decision, const uint64_t* valid,
+                                                          const uint8_t* greedy, float* out)
+{
+    const size_t i = blockIdx.x;
+    const float gum = gumbel_draw(seed, rfl(game_seed[i]), rfl(decision[i]), rfl64(valid[i]), rfl((uint32_t)greedy[i]) != 0u);
+    if (lane_id() < MOVES) out[i * MOVES + lane_id()] = gum;
+}
+
+// azr_debug_gumbel_select: the root-level selection alone on synthetic rows, one wave per row
+__global__ __launch_bounds__(64) void k_debug_gumbel_select(uint32_t m, uint32_t n, float c_visit, float c_scale, const uint32_t* N, const uint32_t* N0,
+                                                            const uint32_t* act, const float* Q, const float* P, const float* g, const float* vhat,
+                                                            const uint64_t* valid, const uint32_t* claim, uint8_t* move_out, uint32_t* cv_out)
+{
+    const size_t i = blockIdx.x;
+    const uint32_t l = lane_id(), ll = l < MOVES ? l : 0;
+    const size_t at = i * MOVES + ll;
+    uint32_t cv;
+    const uint32_t W = (N[at] & N_MASK) | (act[at] << 24);
+    const uint32_t mv = gumbel_select(W, N0[at], Q[at], P[at], g[at], rdlf(vhat[i], 0), rfl64(valid[i]), rfl(claim[i]), m, n, c_visit, c_scale, cv);
+    if (l == 0) {
+        move_out[i] = (uint8_t)mv;
+        cv_out[i] = cv;
+    }
+}
+
+// azr_debug_exp32: the exponential alone, one lane per argument
+__global__ __launch_bounds__(64) void k_debug_exp32(const float* x, int n, float* out)
+{
+    const int i = (int)(blockIdx.x * 64u + threadIdx.x);
+    if (i < n) out[i] = exp32(x[i]);
+}
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -744,7 +847,7 @@ extern "C" int azr_engine_destroy(azr_engine* h)
     void* ptrs[] = {d.sp_started, d.state, d.ctl, d.nodes, d.touch, d.nhash, d.table, d.freel, d.path, d.leaf_in, d.leaf_key,
                     d.leaf_valid, d.leaf_hash, d.net_pi, d.net_v, d.stage, d.ring, d.ring_count, d.counters, d.active,
                     d.arena_taken, d.arena_res, d.prev_start, d.script, d.alog_status, d.alog_rounds, d.alog_final, d.root_eta, d.stage_kl,
-                    d.stage_q, d.resign_state, d.resign_stats};
+                    d.stage_q, d.resign_state, d.resign_stats, d.root_g, d.root_n0};
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : h->tree2) if (p) hipFree(p);
     if (d.leaf_list) hipFree(d.leaf_list);
@@ -949,36 +1052,45 @@ extern "C" int azr_mcts_trim(azr_engine* h)
 extern "C" int azr_mcts_begin(azr_engine* h)
 {
     ENTER(h);
+    // a Gumbel search after an arena: the arena's steps expanded nodes without the net's value, and none of them may be searched
+    if (h->mode == 3 && h->host.gumbel_m > 0) LAUNCH(h, k_tree_clear, h->d);
     h->mode = 1;
     LAUNCH(h, k_search_begin, h->d);
     SYNC(h);
     return AZR_OK;
 }
 
-// The twenty-seven k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
-// self-play also under a CAP, which doubles its three, each of those six with SURPRISE, and each of those twelve with QMIX.  CAP,
-// SURPRISE and QMIX need SELFPLAY and FORCED implies NOISE (k_tree_step asserts all four).
+// The thirty-two k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
+// self-play also under a CAP, which doubles its three, each of those six with SURPRISE, and each of those twelve with QMIX; and the five
+// with GUMBEL: host-stepped, and self-play with and without SURPRISE and QMIX.  CAP, SURPRISE and QMIX need SELFPLAY, FORCED implies
+// NOISE, GUMBEL excludes NOISE, CAP and FORCED (k_tree_step asserts all five).
 // Callers say what is in force; forced playouts without root noise run the NOISE instantiation, on the constant vector.
 static int launch_tree_step(azr_engine* h, const Dev& d, bool selfplay, const StepOpts& o)
 {
     void (*step)(Dev) = nullptr;
 #define AZR_STEP(SP, N, C, F, W, M) \
     case (M) << 5 | (W) << 4 | (SP) << 3 | (N) << 2 | (C) << 1 | (F): step = k_tree_step<SP, N, C, F, W, M>; break
+#define AZR_STEP_GUMBEL(SP, W, M) \
+    case 1 << 6 | (M) << 5 | (W) << 4 | (SP) << 3: step = k_tree_step<SP, 0, 0, 0, W, M, 1>; break
 #define AZR_STEP_SP(W, M) \
     AZR_STEP(1, 0, 0, 0, W, M); AZR_STEP(1, 1, 0, 0, W, M); AZR_STEP(1, 1, 0, 1, W, M); \
     AZR_STEP(1, 0, 1, 0, W, M); AZR_STEP(1, 1, 1, 0, W, M); AZR_STEP(1, 1, 1, 1, W, M)
     // (the fifteen without QMIX first, in the order they always had, then their self-play twelve again with QMIX)
-    switch (o.qmix << 5 | o.surprise << 4 | selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
+    switch (o.gumbel << 6 | o.qmix << 5 | o.surprise << 4 | selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
         AZR_STEP(0, 0, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 1, 0, 0);
         AZR_STEP_SP(0, 0);
         AZR_STEP_SP(1, 0);
         AZR_STEP_SP(0, 1);
         AZR_STEP_SP(1, 1);
+        AZR_STEP_GUMBEL(0, 0, 0);
+        AZR_STEP_GUMBEL(1, 0, 0); AZR_STEP_GUMBEL(1, 1, 0); AZR_STEP_GUMBEL(1, 0, 1); AZR_STEP_GUMBEL(1, 1, 1);
     }
+#undef AZR_STEP_GUMBEL
 #undef AZR_STEP_SP
 #undef AZR_STEP
     if (!step) {
-        h->err = "launch_tree_step: a playout cap, surprise weighting or a value mix on a host-stepped search: there is no such k_tree_step";
+        h->err = "launch_tree_step: a playout cap, surprise weighting or a value mix on a host-stepped search, or a Gumbel search with root "
+                 "noise, a playout cap or forced playouts: there is no such k_tree_step";
         return AZR_E_LOGIC;
     }
     hipLaunchKernelGGL(step, dim3(d.G), dim3(64), 0, h->stream, d);
@@ -992,11 +1104,12 @@ static StepOpts options_in_force(const azr_engine* h, int mode)
 {
     if (mode == 2) return h->sp;
     if (mode == 3) return StepOpts{};
-    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f, false, false};
+    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f, false, false, h->host.gumbel_m > 0};
 }
 // ... and the device view a search-related launch sees with it.  eta_const: no root vector is there to read (a self-play whose steps
 // carry NOISE keeps one per root).  Outside a self-play: the handle's without a self-play's leftovers, with azr_mcts_set_forced_playouts /
-// azr_mcts_set_simulations applied; the steps without FORCED read none of forced_k, prune and eta_const.
+// azr_mcts_set_simulations / azr_mcts_set_gumbel applied; the steps without FORCED read none of forced_k, prune and eta_const, the steps
+// without GUMBEL none of gumbel_*.
 static Dev search_view(const azr_engine* h, int mode)
 {
     Dev d = h->d;
@@ -1005,6 +1118,9 @@ static Dev search_view(const azr_engine* h, int mode)
     if (mode == 2) return d;
     d.forced_k = o.forced ? h->host.forced_k : 0.0f;
     d.prune = 0;
+    d.gumbel_m = mode != 3 ? h->host.gumbel_m : 0;
+    d.gumbel_cvisit = h->host.gumbel_cvisit;
+    d.gumbel_cscale = h->host.gumbel_cscale;
     if (mode != 3 && h->host.sims > 0) d.search.simulations = h->host.sims - h->host.sims % d.T;
     return d;
 }
@@ -1133,7 +1249,7 @@ static void resolve_selfplay_options(azr_engine* h)
     const SelfplayOpts& o = h->sp_set;
     Dev& d = h->d;
     h->host = HostOpts{};
-    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f, o.psw_share > 0.0f, o.q_share > 0.0f};
+    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f, o.psw_share > 0.0f, o.q_share > 0.0f, o.gumbel_m > 0};
     d.noise_alpha = o.alpha;
     d.noise_seed = o.noise_seed;
     d.cap_threshold = cap_threshold_of(o.cap_prob);
@@ -1149,11 +1265,39 @@ static void resolve_selfplay_options(azr_engine* h)
     d.resign_q = o.resign_q;
     d.resign_threshold = resign_threshold_of(o.resign_holdout);
     d.resign_seed = o.resign_seed;
+    d.gumbel_m = o.gumbel_m;
+    d.gumbel_cvisit = o.gumbel_cvisit;
+    d.gumbel_cscale = o.gumbel_cscale;
+    d.gumbel_seed = o.gumbel_seed;
     d.eta_const = 0;
+}
+
+// the Gumbel search's two per-game rows, with the first search that needs them: an engine that never runs one allocates none
+static int gumbel_alloc(azr_engine* h)
+{
+    const size_t n = (size_t)h->d.G * MOVES;
+    if (!h->d.root_g) {
+        HIPCHK(h, dmalloc(&h->d.root_g, n));
+        HIPCHK(h, hipMemsetAsync(h->d.root_g, 0, n * sizeof(float), h->stream));
+    }
+    if (!h->d.root_n0) {
+        HIPCHK(h, dmalloc(&h->d.root_n0, n));
+        HIPCHK(h, hipMemsetAsync(h->d.root_n0, 0, n * sizeof(uint32_t), h->stream));
+    }
+    return AZR_OK;
 }
 
 static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long quota, int keep = 0)
 {
+    // a Gumbel search has no root noise, no fast decisions and no forced playouts: refused before anything of the handle changes
+    if (h->sp_set.gumbel_m > 0) {
+        const SelfplayOpts& o = h->sp_set;
+        const char* other = o.alpha > 0.0f ? "Dirichlet noise (azr_selfplay_set_dirichlet)" :
+                            (o.cap_prob < 1.0f && o.cap_fast_sims > 0) ? "a playout cap (azr_selfplay_set_playout_cap)" :
+                            o.forced_k > 0.0f ? "forced playouts (azr_selfplay_set_forced_playouts)" : nullptr;
+        if (other) return bad_argument(h, std::string("azr_selfplay_start: the Gumbel root search (azr_selfplay_set_gumbel) does not go with ") + other + ": switch one of them off");
+        if (int rc = gumbel_alloc(h)) return rc;
+    }
     // the surprises' buffer, with the first self-play that weights its records: an engine that never does allocates none
     if (h->sp_set.psw_share > 0.0f && !h->d.stage_kl) HIPCHK(h, dmalloc(&h->d.stage_kl, (size_t)h->d.G * h->d.SCAP));
     // ... and the root values' buffer, with the first self-play that blends them into z
@@ -1174,6 +1318,7 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
     else if (h->sp.noise && h->sp.cap) LAUNCH(h, (k_selfplay_noise<true, false>), h->d);
     else if (h->sp.noise) LAUNCH(h, (k_selfplay_noise<false, false>), h->d);
     else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, (size_t)h->d.G * MOVES * sizeof(float), h->stream));
+    if (h->sp.gumbel) LAUNCH(h, k_selfplay_gumbel, h->d);
     SYNC(h);
     return AZR_OK;
 }
@@ -1182,6 +1327,7 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
 extern "C" int azr_mcts_set_root_noise(azr_engine* h, const float* eta)
 {
     ENTER(h);
+    if (eta && h->host.gumbel_m > 0) return bad_argument(h, "azr_mcts_set_root_noise: a Gumbel search is in force (azr_mcts_set_gumbel), which takes no root noise");
     const size_t sz = (size_t)h->d.G * MOVES * sizeof(float);
     if (eta) H2D(h, h->d.root_eta, eta, sz);
     else HIPCHK(h, hipMemsetAsync(h->d.root_eta, 0, sz, h->stream));
@@ -1254,6 +1400,7 @@ extern "C" int azr_mcts_set_forced_playouts(azr_engine* h, float k)
     if (!h) return AZR_E_BAD_HANDLE;
     int rc = forced_k_check(h, "azr_mcts_set_forced_playouts", k);
     if (rc) return rc;
+    if (k > 0.0f && h->host.gumbel_m > 0) return bad_argument(h, "azr_mcts_set_forced_playouts: a Gumbel search is in force (azr_mcts_set_gumbel), which forces no playouts");
     h->host.forced_k = k > 0.0f ? k : 0.0f;
     return AZR_OK;
 }
@@ -1508,6 +1655,170 @@ extern "C" int azr_debug_resign(azr_engine* h, float q_resign, int streak, float
     D2H(h, resign_row_out, orow.p, n * 4);
     D2H(h, resigner_out, owho.p, n);
     D2H(h, holdout_out, ohold.p, n);
+    SYNC(h);
+    return AZR_OK;
+}
+
+// ---- Gumbel root search ---------------------------------------------------------------------------------
+// numbers; m in [0, 43]; when on (m > 0): c_visit >= 0, c_scale > 0
+static int gumbel_check(azr_engine* h, const char* who, int m, float c_visit, float c_scale)
+{
+    if (!(c_visit - c_visit == 0.0f) || !(c_scale - c_scale == 0.0f)) return bad_argument(h, std::string(who) + ": c_visit and c_scale must be finite numbers");
+    if (m < 0 || m > MOVES) return bad_argument(h, std::string(who) + ": m = " + std::to_string(m) + " outside [0, 43] (0 = off)");
+    if (m > 0 && !(c_visit >= 0.0f && c_scale > 0.0f)) return bad_argument(h, std::string(who) + ": c_visit must be >= 0 and c_scale > 0");
+    return AZR_OK;
+}
+
+extern "C" int azr_selfplay_set_gumbel(azr_engine* h, int m, float c_visit, float c_scale, uint32_t seed)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (int rc = gumbel_check(h, "azr_selfplay_set_gumbel", m, c_visit, c_scale)) return rc;
+    h->sp_set.gumbel_m = m;
+    h->sp_set.gumbel_cvisit = m > 0 ? c_visit : 0.0f;
+    h->sp_set.gumbel_cscale = m > 0 ? c_scale : 0.0f;
+    h->sp_set.gumbel_seed = seed;
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_set_gumbel(azr_engine* h, int m, float c_visit, float c_scale)
+{
+    ENTER(h);
+    if (int rc = gumbel_check(h, "azr_mcts_set_gumbel", m, c_visit, c_scale)) return rc;
+    if (m > 0 && (h->host.noise || h->host.forced_k > 0.0f))
+        return bad_argument(h, std::string("azr_mcts_set_gumbel: ") + (h->host.noise ? "a root noise vector (azr_mcts_set_root_noise)" : "forced playouts (azr_mcts_set_forced_playouts)") +
+                                   " is in force, which a Gumbel search does not go with");
+    const bool toggles = (m > 0) != (h->host.gumbel_m > 0);
+    if (m > 0) { if (int rc = gumbel_alloc(h)) return rc; }
+    h->host.gumbel_m = m;
+    h->host.gumbel_cvisit = m > 0 ? c_visit : 0.0f;
+    h->host.gumbel_cscale = m > 0 ? c_scale : 0.0f;
+    if (toggles) {   // no node without the net's value is searched by a Gumbel search: the trees start empty
+        LAUNCH(h, k_tree_clear, h->d);
+        if (h->mode == 2) h->mode = 0;   // (a running self-play's trees are gone with them)
+    }
+    SYNC(h);
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_set_root_gumbel(azr_engine* h, const float* g_host)
+{
+    ENTER(h);
+    if (int rc = gumbel_alloc(h)) return rc;
+    const size_t sz = (size_t)h->d.G * MOVES * sizeof(float);
+    if (g_host) H2D(h, h->d.root_g, g_host, sz);
+    else HIPCHK(h, hipMemsetAsync(h->d.root_g, 0, sz, h->stream));
+    SYNC(h);
+    if (h->mode == 2) h->mode = 0;   // the array was a running self-play's: that self-play is over
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_root_gumbel(azr_engine* h, float* g_host)
+{
+    ENTER(h);
+    if (!g_host) return AZR_E_INVALID_ARGUMENT;
+    const size_t sz = (size_t)h->d.G * MOVES * sizeof(float);
+    if (!options_in_force(h, h->mode).gumbel || !h->d.root_g) { memset(g_host, 0, sz); return AZR_OK; }
+    D2H(h, g_host, h->d.root_g, sz);
+    SYNC(h);
+    return AZR_OK;
+}
+
+// a Gumbel search's settings in force (a running self-play's, else the host-stepped ones), or the reason there are none
+static int gumbel_view(azr_engine* h, const char* who, Dev& d)
+{
+    d = search_view(h, h->mode);
+    if (d.gumbel_m <= 0 || !d.root_g || !d.root_n0) {
+        h->err = std::string(who) + ": no Gumbel search is in force (azr_mcts_set_gumbel, or a self-play started under azr_selfplay_set_gumbel)";
+        return AZR_E_STATE;
+    }
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_gumbel_policy(azr_engine* h, float* pi_host, float* qhat_host)
+{
+    ENTER(h);
+    if (!pi_host) return AZR_E_INVALID_ARGUMENT;
+    Dev d;
+    if (int rc = gumbel_view(h, "azr_mcts_gumbel_policy", d)) return rc;
+    const size_t sz = (size_t)h->d.G * MOVES * 4;
+    DevBuf bq, bp;
+    HIPCHK(h, bq.alloc(sz)); HIPCHK(h, bp.alloc(sz));
+    LAUNCH(h, k_gumbel_policy, d, (float*)bq.p, (float*)bp.p);
+    if (qhat_host) D2H(h, qhat_host, bq.p, sz);
+    D2H(h, pi_host, bp.p, sz);
+    SYNC(h);
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_gumbel_pick(azr_engine* h, uint8_t* moves_host)
+{
+    ENTER(h);
+    if (!moves_host) return AZR_E_INVALID_ARGUMENT;
+    Dev d;
+    if (int rc = gumbel_view(h, "azr_mcts_gumbel_pick", d)) return rc;
+    LAUNCH_OUT(h, moves_host, (size_t)h->d.G, uint8_t, k_gumbel_pick, d);
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_root_gumbel(azr_engine* h, uint32_t seed, const uint32_t* game_seed, const uint32_t* decision, const uint64_t* valid,
+                                     const uint8_t* greedy, int rows, float* g_out)
+{
+    ENTER(h);
+    if (rows < 0 || (rows > 0 && (!game_seed || !decision || !valid || !greedy || !g_out))) return AZR_E_INVALID_ARGUMENT;
+    if (rows == 0) return AZR_OK;
+    const size_t n = (size_t)rows;
+    DevBuf bs, bd, bv, bg, bo;
+    HIPCHK(h, bs.alloc(n * 4)); HIPCHK(h, bd.alloc(n * 4)); HIPCHK(h, bv.alloc(n * 8)); HIPCHK(h, bg.alloc(n)); HIPCHK(h, bo.alloc(n * MOVES * 4));
+    H2D(h, bs.p, game_seed, n * 4);
+    H2D(h, bd.p, decision, n * 4);
+    H2D(h, bv.p, valid, n * 8);
+    H2D(h, bg.p, greedy, n);
+    hipLaunchKernelGGL(k_debug_root_gumbel, dim3(rows), dim3(64), 0, h->stream, seed, (const uint32_t*)bs.p, (const uint32_t*)bd.p,
+                       (const uint64_t*)bv.p, (const uint8_t*)bg.p, (float*)bo.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, g_out, bo.p, n * MOVES * 4);
+    SYNC(h);
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_gumbel_select(azr_engine* h, int m, int n, float c_visit, float c_scale, const uint32_t* N, const uint32_t* N0,
+                                       const uint32_t* act, const float* Q, const float* P, const float* g, const float* vhat,
+                                       const uint64_t* valid, const uint32_t* claim, int rows, uint8_t* move_out, uint32_t* cv_out)
+{
+    ENTER(h);
+    if (int rc = gumbel_check(h, "azr_debug_gumbel_select", m, c_visit, c_scale)) return rc;
+    if (m <= 0 || n <= 0) return bad_argument(h, "azr_debug_gumbel_select: m must lie in [1, 43] and n be positive");
+    if (rows < 0 || (rows > 0 && (!N || !N0 || !act || !Q || !P || !g || !vhat || !valid || !claim || !move_out || !cv_out))) return AZR_E_INVALID_ARGUMENT;
+    if (rows == 0) return AZR_OK;
+    const size_t r = (size_t)rows, row = r * MOVES * 4;
+    DevBuf b[6], bh, bv, bc, om, oc;
+    const void* src[6] = {N, N0, act, Q, P, g};
+    for (int i = 0; i < 6; i++) { HIPCHK(h, b[i].alloc(row)); H2D(h, b[i].p, src[i], row); }
+    HIPCHK(h, bh.alloc(r * 4)); HIPCHK(h, bv.alloc(r * 8)); HIPCHK(h, bc.alloc(r * 4)); HIPCHK(h, om.alloc(r)); HIPCHK(h, oc.alloc(r * 4));
+    H2D(h, bh.p, vhat, r * 4);
+    H2D(h, bv.p, valid, r * 8);
+    H2D(h, bc.p, claim, r * 4);
+    hipLaunchKernelGGL(k_debug_gumbel_select, dim3(rows), dim3(64), 0, h->stream, (uint32_t)m, (uint32_t)n, c_visit, c_scale, (const uint32_t*)b[0].p,
+                       (const uint32_t*)b[1].p, (const uint32_t*)b[2].p, (const float*)b[3].p, (const float*)b[4].p, (const float*)b[5].p,
+                       (const float*)bh.p, (const uint64_t*)bv.p, (const uint32_t*)bc.p, (uint8_t*)om.p, (uint32_t*)oc.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, move_out, om.p, r);
+    D2H(h, cv_out, oc.p, r * 4);
+    SYNC(h);
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_exp32(azr_engine* h, const float* x, int n, float* out)
+{
+    ENTER(h);
+    if (n < 0 || (n > 0 && (!x || !out))) return AZR_E_INVALID_ARGUMENT;
+    if (n == 0) return AZR_OK;
+    DevBuf bx, bo;
+    HIPCHK(h, bx.alloc((size_t)n * 4)); HIPCHK(h, bo.alloc((size_t)n * 4));
+    H2D(h, bx.p, x, (size_t)n * 4);
+    hipLaunchKernelGGL(k_debug_exp32, dim3((n + 63) / 64), dim3(64), 0, h->stream, (const float*)bx.p, n, (float*)bo.p);
+    HIPCHK(h, hipGetLastError());
+    D2H(h, out, bo.p, (size_t)n * 4);
     SYNC(h);
     return AZR_OK;
 }

@@ -148,21 +148,31 @@ struct Dev {
     uint32_t resign_seed;      // the coin is keyed by (resign_seed, game seed)
     uint32_t* resign_state;    // [G]  run[0] | run[1] << 8 | first << 16 of each slot's running game (azr_resign.hpp)
     unsigned long long* resign_stats;   // [G][4]  resigned, holdout_games, holdout_would_resign, holdout_not_lost: per slot, summed by the host
+    // Gumbel root search (this engine's own; read by the k_tree_step instantiations with GUMBEL, k_selfplay_gumbel, k_gumbel_policy and
+    // k_gumbel_pick only; azr_gumbel.hpp).  Behind everything else again.  Both arrays are allocated at first use.
+    float* root_g;             // [G][43]  the Gumbel vector in force at each game's root (lane i <-> move i)
+    uint32_t* root_n0;         // [G][43]  N0: the root's N row when the search in progress made its first root-level selection
+    int gumbel_m;              // moves considered at a root (0 = off)
+    float gumbel_cvisit;       // sigma = ((c_visit + max N) * c_scale) * qhat
+    float gumbel_cscale;
+    uint32_t gumbel_seed;      // device self-play: g is keyed by (gumbel_seed, game seed, decision, move)
 };
 constexpr int ALOG = 16;
 
 // The options of the search variants (host side).  Which of them a tree step carries: root noise, a playout cap (self-play only),
 // forced playouts, policy surprise weighting of the records and the value mix of their z (both self-play only) — the template
-// arguments of k_tree_step after SELFPLAY.
-struct StepOpts { bool noise = false, cap = false, forced = false, surprise = false, qmix = false; };
+// arguments of k_tree_step after SELFPLAY; and the Gumbel root search, which excludes the first three.
+struct StepOpts { bool noise = false, cap = false, forced = false, surprise = false, qmix = false, gumbel = false; };
 // Host-stepped searches (azr_mcts_*): in force from the setter's call until the next azr_selfplay_start*.
 struct HostOpts {
     bool noise = false;        // azr_mcts_set_root_noise: a vector per game is set in d.root_eta
     float forced_k = 0.0f;     // azr_mcts_set_forced_playouts (0 = off)
     int sims = 0;              // azr_mcts_set_simulations: the budget (0 = the settings')
+    int gumbel_m = 0;          // azr_mcts_set_gumbel (0 = off)
+    float gumbel_cvisit = 0.0f, gumbel_cscale = 0.0f;
 };
 // Device self-play, as the azr_selfplay_set_* setters leave them.  A running self-play never sees a change: azr_selfplay_start* resolves
-// them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune, psw_*, q_share and resign_*.
+// them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune, psw_*, q_share, resign_* and gumbel_*.
 struct SelfplayOpts {
     float alpha = 0.0f;        // azr_selfplay_set_dirichlet (0 = off)
     uint32_t noise_seed = 0;
@@ -179,6 +189,9 @@ struct SelfplayOpts {
     float resign_q = 0.0f;
     float resign_holdout = 0.0f;
     uint32_t resign_seed = 0;
+    int gumbel_m = 0;          // azr_selfplay_set_gumbel (0 = off)
+    float gumbel_cvisit = 0.0f, gumbel_cscale = 0.0f;
+    uint32_t gumbel_seed = 0;
 };
 
 // folded network parameters on device

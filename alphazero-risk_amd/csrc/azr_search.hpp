@@ -6,6 +6,7 @@
 #include "azr_noise.hpp"
 #include "azr_surprise.hpp"
 #include "azr_resign.hpp"
+#include "azr_gumbel.hpp"
 
 namespace azr {
 
@@ -210,6 +211,8 @@ __device__ __forceinline__ void list_pending(const Dev& E, int g, const Ctl& c, 
 // AlphaZeroMCTS::search leaf branch, after the future resolved (alphazero_mcts.cpp:350-356): expand + backup, for every
 // search thread with a pending leaf, in thread order.  A state another thread has added meanwhile is dropped
 // (StateSimulationsStorage::add, alphazero_mcts.cpp:203-215) and its value still backed up.
+// GUMBEL: the net's value of the expanded node — for its mover, what tree_backup takes — is kept in the node (azr_gumbel.hpp).
+template <bool GUMBEL = false>
 __device__ __forceinline__ void consume_pending(const Dev& E, int g, const Tree& t, Ctl& c, StepCount& k)
 {
     if (!c.pending) return;
@@ -235,7 +238,11 @@ __device__ __forceinline__ void consume_pending(const Dev& E, int g, const Tree&
                 k.drop += c.hiwater;
                 tree_clear(t, c);
             }
-            if (tree_expand(t, c, kd, h, valid, prior) == NO_NODE) k.drop++;
+            if (GUMBEL) {
+                const uint32_t idx = tree_expand(t, c, kd, h, valid, prior);
+                if (idx == NO_NODE) k.drop++;
+                else node_set_vhat(t, idx, v);
+            } else if (tree_expand(t, c, kd, h, valid, prior) == NO_NODE) k.drop++;
         }
         TP(4);
         k.evals++;
@@ -258,7 +265,8 @@ enum : int { RD_DONE = 0, RD_LEAF = 1, RD_FAIL = 2 };
 // `S`: the settings of the tree that is searching (the arena's player B may carry its own budget and PUCT constant).
 // NOISE: the game's root noise vector `eta` (lane i <-> move i) enters the first selection of every descent (tree_select).
 // FORCED: that selection forces playouts with the factor `fk` (0 = not in this search: a fast decision under a playout cap).
-template <bool NOISE, bool FORCED = false>
+// GUMBEL: that selection is gumbel_select_root's (azr_gumbel.hpp) for the claim index sims_started - 1; `eta` carries the root's g.
+template <bool NOISE, bool FORCED = false, bool GUMBEL = false>
 __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
                                             StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
 {
@@ -303,7 +311,11 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
                 break;
             }
             k.levels++;
-            uint32_t mv = tree_select<NOISE, FORCED>(t, idx, nr, S, c.search_id, scratch, plen == 0, E.noise_eps, eta, fk);
+            uint32_t mv;
+            if (GUMBEL && plen == 0)
+                mv = gumbel_select_root(t, idx, nr, c.search_id, E.root_n0 + (size_t)g * MOVES, c.sims_started - 1u, (uint32_t)E.gumbel_m,
+                                        (uint32_t)S.simulations, E.gumbel_cvisit, E.gumbel_cscale, eta);
+            else mv = tree_select<NOISE, FORCED>(t, idx, nr, S, c.search_id, scratch, plen == 0, E.noise_eps, eta, fk);
             TP(12);
             if (mv == NONE) { fail = true; s.err = E_LOGIC; break; }
             uint32_t before = s.cur;
@@ -334,13 +346,13 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
 // One round of AlphaZeroMCTS::simulate for all T search threads of the game, in thread order: every thread without a
 // pending leaf runs descents until it blocks on the net.  RD_LEAF = at least one leaf is waiting; RD_DONE = the counter
 // is exhausted and every claimed simulation is backed up.
-template <bool NOISE, bool FORCED = false>
+template <bool NOISE, bool FORCED = false, bool GUMBEL = false>
 __device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
                                             StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
 {
     for (int th = 0; th < E.T; th++) {
         if ((c.pending >> th) & 1u) continue;
-        int r = run_descents<NOISE, FORCED>(E, S, g, t, th, c, root, scratch, k, err_out, eta, fk);
+        int r = run_descents<NOISE, FORCED, GUMBEL>(E, S, g, t, th, c, root, scratch, k, err_out, eta, fk);
         if (r == RD_FAIL) { c.pending = 0; return RD_FAIL; }
         if (r == RD_LEAF && plen_get(c, th) == 0) break;  // root expansion: the threads start after setRootState
     }
@@ -402,6 +414,16 @@ __device__ __forceinline__ float new_root_noise(const Dev& E, int g, const Ctl& 
     if (c.mode != 0) eta = draw ? dirichlet_draw(E.noise_alpha, E.noise_seed, c.seed, c.decisions, valid_moves(root, E.rules)) : E.noise_value;
     if (lane_id() < MOVES) E.root_eta[(size_t)g * MOVES + lane_id()] = eta;
     return eta;
+}
+
+// g of game g's NEW root in a self-play whose steps carry GUMBEL (azr_gumbel.hpp): stored for azr_mcts_root_gumbel and handed to the
+// descents and the decision; zeros for a slot that went idle and for a greedy root (its round above temperature_threshold)
+__device__ __forceinline__ float new_root_gumbel(const Dev& E, int g, const Ctl& c, const WS& root)
+{
+    float gum = 0.0f;
+    if (c.mode != 0) gum = gumbel_draw(E.gumbel_seed, c.seed, c.decisions, valid_moves(root, E.rules), (int)root.round > E.search.temperature_threshold);
+    if (lane_id() < MOVES) E.root_g[(size_t)g * MOVES + lane_id()] = gum;
+    return gum;
 }
 
 // N' of the root node `ridx` under policy target pruning (azr_forced.hpp), lane = move: the node's Q, P and sumN word, the root-level

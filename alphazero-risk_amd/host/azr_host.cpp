@@ -113,6 +113,10 @@ void Settings::init(int argc, char* argv[])
         {"resign-streak", "[this build] decisions in a row below --resign-q after which their player resigns (0 = off: every game is played to its end; at most 255)", "0", false},
         {"resign-holdout", "[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose (within [0, 1])", "0.1", false},
         {"resign-seed", "[this build] seed of the coin that holds a game out of resignation (independent of --seed, --dir-seed, --cap-seed and --psw-seed)", std::to_string(RESIGN_SEED), false},
+        {"gumbel-m", "[this build] self-play Gumbel root search with sequential halving: moves considered at a root, sampled without replacement through Gumbel noise; the winner is played and softmax(logit + sigma(completed Q)) recorded (0 = off: PUCT at the root, the visit distribution as pi; at most 43; not with --dir-alpha, --cap-prob or --forced-k; Danihelka et al. 2022)", "0", false},
+        {"gumbel-cvisit", "[this build] c_visit of sigma = ((c_visit + max N) * c_scale) * completed Q under --gumbel-m (at least 0)", "50", false},
+        {"gumbel-cscale", "[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1]: half the paper's, whose values lie in [0, 1] (above 0)", "0.5", false},
+        {"gumbel-seed", "[this build] seed of the Gumbel vectors (independent of --seed: the games' dice and deals do not move)", std::to_string(GUMBEL_SEED), false},
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -347,6 +351,37 @@ void Settings::init(int argc, char* argv[])
             exit(2);
         }
         RESIGN_SEED = (uint32_t)sd;
+    }
+    {
+        char* end = nullptr;
+        const std::string mv = get("gumbel-m");
+        const long gm = strtol(mv.c_str(), &end, 10);
+        if (mv.empty() || *end != '\0' || gm < 0 || gm > 43) {
+            fprintf(stderr, "--gumbel-m: '%s' is not a number of root moves (a whole number in [0, 43]; 0 = off)\n", mv.c_str());
+            exit(2);
+        }
+        GUMBEL_M = (int)gm;
+        const std::string vv = get("gumbel-cvisit");
+        const double cv = strtod(vv.c_str(), &end);
+        if (vv.empty() || *end != '\0' || !(cv >= 0.0) || !(cv <= 1e30)) {
+            fprintf(stderr, "--gumbel-cvisit: '%s' is not a c_visit (a finite number, at least 0)\n", vv.c_str());
+            exit(2);
+        }
+        GUMBEL_CVISIT = (float)cv;
+        const std::string sv = get("gumbel-cscale");
+        const double cs = strtod(sv.c_str(), &end);
+        if (sv.empty() || *end != '\0' || !(cs > 0.0) || !(cs <= 1e30)) {
+            fprintf(stderr, "--gumbel-cscale: '%s' is not a c_scale (a finite number above 0)\n", sv.c_str());
+            exit(2);
+        }
+        GUMBEL_CSCALE = (float)cs;
+        const std::string dv = get("gumbel-seed");
+        const unsigned long long sd = dv.empty() || dv[0] == '-' ? 0 : strtoull(dv.c_str(), &end, 10);
+        if (dv.empty() || dv[0] == '-' || *end != '\0' || sd > 0xffffffffull) {
+            fprintf(stderr, "--gumbel-seed: '%s' is not a 32-bit seed\n", dv.c_str());
+            exit(2);
+        }
+        GUMBEL_SEED = (uint32_t)sd;
     }
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
@@ -827,6 +862,8 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         e.check(azr_selfplay_set_value_mix(e.h, SETTINGS.Q_SHARE), "selfplay_set_value_mix");
         // resignation in the generated games: --resign-streak 0 (default) plays every game to its end
         e.check(azr_selfplay_set_resign(e.h, SETTINGS.RESIGN_Q, SETTINGS.RESIGN_STREAK, SETTINGS.RESIGN_HOLDOUT, SETTINGS.RESIGN_SEED), "selfplay_set_resign");
+        // Gumbel root search in the generated games: --gumbel-m 0 (default) selects by PUCT at the root and records the visit distribution
+        e.check(azr_selfplay_set_gumbel(e.h, SETTINGS.GUMBEL_M, SETTINGS.GUMBEL_CVISIT, SETTINGS.GUMBEL_CSCALE, SETTINGS.GUMBEL_SEED), "selfplay_set_gumbel");
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);
@@ -870,6 +907,9 @@ void AlphaZeroTrainer::train(std::shared_ptr<AlphaZeroNNGroup> trainGroup, std::
         printf("Self-play: %llu games, %llu decisions, %llu simulations in %.2f s  =>  %.0f simulations/s, %.2f games/s\n",
                (unsigned long long)r.games, (unsigned long long)r.decisions, (unsigned long long)r.simulations, r.seconds,
                r.simulations / r.seconds, r.games / r.seconds);
+        if (SETTINGS.GUMBEL_M > 0)
+            printf("Gumbel root search: m %d, c_visit %g, c_scale %g, seed %u\n", SETTINGS.GUMBEL_M, SETTINGS.GUMBEL_CVISIT, SETTINGS.GUMBEL_CSCALE,
+                   SETTINGS.GUMBEL_SEED);
         if (SETTINGS.RESIGN_STREAK > 0) {  // the holdout's false positives: would-be resigners that went on not to lose
             const azr_resign_stats& s = r.resign;
             printf("Resignation: %llu resigned, %llu held out, %llu of them would have resigned, %llu of those did not lose  =>  false-positive share ",

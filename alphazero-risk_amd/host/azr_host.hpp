@@ -25,7 +25,7 @@ namespace azrhost {
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
 // `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2,
-// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap; --forced-k, --prune-target for forced playouts and policy target pruning; --psw-share, --psw-max, --psw-seed for policy surprise weighting of its records; --q-share for the value mix of their z; --resign-q, --resign-streak, --resign-holdout, --resign-seed for resignation with a no-resign holdout), the others marked "[this build]" in --help.
+// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap; --forced-k, --prune-target for forced playouts and policy target pruning; --psw-share, --psw-max, --psw-seed for policy surprise weighting of its records; --q-share for the value mix of their z; --resign-q, --resign-streak, --resign-holdout, --resign-seed for resignation with a no-resign holdout; --gumbel-m, --gumbel-cvisit, --gumbel-cscale, --gumbel-seed for the Gumbel root search with sequential halving), the others marked "[this build]" in --help.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:
@@ -89,6 +89,10 @@ public:
     int RESIGN_STREAK = 0;               // --resign-streak: ... the decisions in a row below it after which their player gives up (0 = off) ...
     float RESIGN_HOLDOUT = 0.1f;         // --resign-holdout: ... the share of the games that never resign and measure the rule's false positives ...
     uint32_t RESIGN_SEED = 0;            // --resign-seed: ... and the seed of the coin that holds a game out (self-play generation of -m train only, like --dir-alpha)
+    int GUMBEL_M = 0;                    // --gumbel-m: Gumbel root search in the self-play games, the moves considered at a root (0 = off: PUCT at the root and the visit distribution as pi) ...
+    float GUMBEL_CVISIT = 50.0f;         // --gumbel-cvisit, --gumbel-cscale: ... sigma = ((c_visit + max N) * c_scale) * completed Q, values in [-1, 1] ...
+    float GUMBEL_CSCALE = 0.5f;
+    uint32_t GUMBEL_SEED = 0;            // --gumbel-seed: ... and the seed of the Gumbel vectors (self-play generation of -m train only, like --dir-alpha; not with --dir-alpha, --cap-prob or --forced-k)
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 

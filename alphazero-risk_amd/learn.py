@@ -212,6 +212,8 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
             gen.selfplay_set_value_mix(getattr(a, "q_share", 0.0))   # value mix of the generated games' records only (0 = the bare game outcome)
             gen.selfplay_set_resign(getattr(a, "resign_q", -0.9), getattr(a, "resign_streak", 0), getattr(a, "resign_holdout", 0.1),
                                     getattr(a, "resign_seed", 0))   # resignation in the generated games only (streak 0 = every game to its end)
+            gen.selfplay_set_gumbel(getattr(a, "gumbel_m", 0), getattr(a, "gumbel_cvisit", 50.0), getattr(a, "gumbel_cscale", 0.5),
+                                    getattr(a, "gumbel_seed", 0))   # Gumbel root search in the generated games only (m 0 = PUCT at the root)
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -232,6 +234,8 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         dt = time.time() - t0
         log(f"Generated {len(new_recs)} new samples for total {len(records) + len(new_recs)}  "
             f"[{c['games_finished']} games, {c['simulations'] / dt:.0f} simulations/s, {c['games_finished'] / dt:.2f} games/s]")
+        if getattr(a, "gumbel_m", 0) > 0:
+            log(f"Gumbel root search: m {a.gumbel_m}, c_visit {a.gumbel_cvisit:g}, c_scale {a.gumbel_cscale:g}, seed {a.gumbel_seed}")
         if resign_on:   # the holdout's false positives: would-be resigners that went on not to lose
             fp = f"{rs['holdout_not_lost'] / rs['holdout_would_resign']:.3f}" if rs["holdout_would_resign"] else "n/a"
             log(f"Resignation: {rs['resigned']} resigned, {rs['holdout_games']} held out, {rs['holdout_would_resign']} of them would have resigned, "
@@ -380,6 +384,15 @@ def main():
                     help="[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose "
                          "(within [0, 1])")
     ap.add_argument("--resign-seed", type=int, default=0, help="[this build] seed of the coin that holds a game out of resignation")
+    ap.add_argument("--gumbel-m", type=int, default=0,
+                    help="[this build] self-play Gumbel root search with sequential halving: moves considered at a root, sampled without "
+                         "replacement through Gumbel noise; the winner is played and softmax(logit + sigma(completed Q)) recorded "
+                         "(0 = off; at most 43; not with --dir-alpha, --cap-prob or --forced-k)")
+    ap.add_argument("--gumbel-cvisit", type=float, default=50.0,
+                    help="[this build] c_visit of sigma = ((c_visit + max N) * c_scale) * completed Q under --gumbel-m (at least 0)")
+    ap.add_argument("--gumbel-cscale", type=float, default=0.5,
+                    help="[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1] (above 0)")
+    ap.add_argument("--gumbel-seed", type=int, default=0, help="[this build] seed of the Gumbel vectors")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -409,6 +422,16 @@ def main():
         ap.error(f"--psw-seed: {a.psw_seed} is not a 32-bit seed")
     if not 0.0 <= a.q_share <= 1.0:   # (a NaN fails both comparisons)
         ap.error(f"--q-share: {a.q_share} is not a share (a number in [0, 1]; 0 = off)")
+    if not 0 <= a.gumbel_m <= 43:
+        ap.error(f"--gumbel-m: {a.gumbel_m} is not a number of root moves (a whole number in [0, 43]; 0 = off)")
+    if not 0.0 <= a.gumbel_cvisit <= 1e30:   # (a NaN fails both comparisons)
+        ap.error(f"--gumbel-cvisit: {a.gumbel_cvisit} is not a c_visit (a finite number, at least 0)")
+    if not 0.0 < a.gumbel_cscale <= 1e30:
+        ap.error(f"--gumbel-cscale: {a.gumbel_cscale} is not a c_scale (a finite number above 0)")
+    if not 0 <= a.gumbel_seed <= 0xFFFFFFFF:
+        ap.error(f"--gumbel-seed: {a.gumbel_seed} is not a 32-bit seed")
+    if a.gumbel_m > 0 and (a.dir_alpha > 0 or (a.cap_prob < 1 and a.cap_fast > 0) or a.forced_k > 0):
+        ap.error("--gumbel-m: the Gumbel root search does not go with --dir-alpha, --cap-prob / --cap-fast or --forced-k")
     if not 0 <= a.resign_streak <= 255:
         ap.error(f"--resign-streak: {a.resign_streak} is not a streak (a whole number in [0, 255]; 0 = off)")
     if not -1.0 <= a.resign_q <= 1.0:

@@ -457,6 +457,105 @@ int azr_debug_resign(azr_engine* h, float q_resign, int streak, float holdout_sh
                      const uint8_t* player /*[rows]*/, const uint32_t* game_len, const uint32_t* game_seed, int games,
                      int32_t* resign_row_out, uint8_t* resigner_out, uint8_t* holdout_out /*[games]*/);
 
+/* ---- Gumbel root search with sequential halving (this engine's own; off after azr_engine_create) ---------------------
+ * The reference selects by PUCT at every level and records the root's visit distribution; at 16 to 100 simulations over up to 43 moves
+ * that target is a coarse copy of the prior, and nothing makes it an improvement on the prior.  Gumbel AlphaZero (Danihelka, Guez,
+ * Schrittwieser, Silver, "Policy improvement by planning with Gumbel", ICLR 2022) samples the root's candidate moves without
+ * replacement through Gumbel noise, spends the budget on them by sequential halving, plays the winner and records
+ * softmax(logit + sigma(completed Q)).  Here it replaces the selection at path depth 0 and the decision; deeper levels keep PUCT (the
+ * paper's deterministic non-root selection is not built), and the arena (azr_arena_*) never sees it.
+ * All arithmetic below is fp32, each operation rounded on its own (no fused multiply-add), in the order written; lane i <-> move i.
+ *
+ * Per root.  P = the node's stored prior row (azr_mcts_root_stats);  logit[a] = ln32(max(P[a], 1.17549435e-38f)) with the ln32 of
+ * "policy surprise weighting";  valid = the node's legal moves;  n = the search budget in force, S - S % T;  m_eff = min(m, the number
+ * of legal moves);  N, Q = the node's rows, act[a] = the visits of a in flight in other search threads (the top byte of the N word).
+ * N0 = the root's N row at the moment this search made its first root-level selection (kept per game; a root that tree reuse brought
+ * along starts with N0 = N);  ns[a] = N[a] > N0[a] ? N[a] - N0[a] : 0, the search-local count of completed visits.
+ *
+ * exp32(x), the engine's own exponential for x <= 0:
+ *     if (x < -104.0f) return 0
+ *     kf = rint(x * 1.44269502f) (to nearest, ties to even);   k = (int)kf
+ *     r = (x - kf * 0.693145752f) - kf * 1.42860682e-06f
+ *     p = 1.98412701e-04f;   then p = p * r + c for c = 1.38888892e-03f, 8.33333377e-03f, 4.16666679e-02f, 1.66666672e-01f, 0.5f,
+ *         1.0f, 1.0f in turn (a multiply, then an add)
+ *     k1 = k >> 1 (arithmetic);   exp32 = (p * 2^k1) * 2^(k - k1)                (the two powers of two are exact floats)
+ * Against the double exponential on a grid of [-104, 0] (tests/test_gumbel_ref.py): relative error at most 9.84e-8 where the result is
+ * a normal float, at most 0.775 of the smallest denormal below that; exp32(0) = 1 exactly; no argument <= 0 gives a NaN.
+ *
+ * The Gumbel vector of a root.  d = the decisions already taken in the running game, s = the game's seed, as in the playout cap's coin,
+ * whose mix this is:
+ *     k = mix(seed + 0xB5297A4D);   k = mix(k ^ s);   k = mix((k ^ d) + 0x1B56C4E9);   k_a = mix(k ^ ((a + 1) * 0x9E3779B9))
+ *     u = ((float)(mix(k_a) >> 9) + 0.5f) * 2^-23                                   (the first uniform of the Dirichlet sampler's stream k_a)
+ *     g[a] = -ln32(-ln32(u))   for a legal a,   0 for an illegal one
+ * The two constants are nobody else's (Dirichlet 0x9E3779B9, 0x85EBCA6B; cap 0xC2B2AE35, 0x27D4EB2F; copies 0x165667B1, 0xD3A2646C;
+ * holdout 0x2545F491, 0x68E31DA4).  g is a function of (seed, s, d, a) alone; nothing is drawn from the game's own RNG stream.  A root
+ * whose round is above temperature_threshold gets g = 0 everywhere: the greedy late game, so the threshold keeps its meaning.
+ *
+ * Net value of a node, vhat: the value the net returned when the node was expanded, for the node's mover (the sign the backup takes).
+ * It is kept in the node — the float behind its 43 priors, which is 0 in every node a search without the feature expands — so it
+ * survives tree reuse; switching the feature on clears the trees, so no node without a vhat is searched.
+ *
+ * Completed Q.
+ *     seen[a] = a is legal and N[a] > 0;   total = the integer sum of N over the legal moves
+ *     wp = the sum of P[a], wq = the sum of P[a] * Q[a] over the seen moves, each summed one after the other from 0.0f in index order
+ *     v_mix = (total > 0 && wp > 0) ? (vhat + (float)total * (wq / wp)) / (1.0f + (float)total) : vhat
+ *     qhat[a] = seen[a] ? Q[a] : v_mix
+ *     sigma[a] = ((c_visit + (float)(the largest N of a legal move)) * c_scale) * qhat[a]
+ * Values lie in [-1, 1] and are not rescaled.  The paper rescales them to [0, 1], q01 = (q + 1) / 2, so the paper's [0, 1] convention
+ * is half this c_scale's effect per unit: its c_scale of 1.0 is 0.5 here.
+ *
+ * Considered visits, cv(m_eff, n, i) for the claim index i = 0 .. n - 1 (the i-th descent the search starts):
+ *     m_eff <= 1:  cv = i.
+ *     else L = ceil(log2 m_eff), k = m_eff, base = 0, and until n entries exist:  e = max(1, n / (L * k)) (integer);  for j = 0 .. e - 1
+ *     emit k entries equal to base + j;  base += e;  k = max(2, k / 2).
+ * m_eff = 4, n = 16 gives 0,0,0,0,1,1,1,1,2,2,3,3,4,4,5,5 and the search-local visits (6, 6, 2, 2).  It is recomputed from i, never stored.
+ *
+ * Root-level selection of claim i (path depth 0 only):
+ *     cnt[a] = ns[a] + act[a]
+ *     candidates = the legal moves with cnt == cv;  if there is none, the legal moves with the largest cnt below cv;  if there is still
+ *     none (a root that a transposition visited from below), all legal moves
+ *     the move = the candidate with the largest (g + logit) + sigma, the lowest index on ties
+ * with the bookkeeping of the PUCT selection (the in-flight count of the move goes up, the node counts as visited).  The first m_eff
+ * claims all see qhat = v_mix on the unvisited moves and so take the m_eff best by g + logit: the sample without replacement.
+ *
+ * Decision.  The move = the legal move with the largest ns, among those the largest (g + logit) + sigma, the lowest index on ties;
+ * nothing is drawn, so a Gumbel decision takes no rFloat from the game's stream.  The record's pi:
+ *     x[a] = logit[a] + sigma[a] on the legal moves;  mx = their maximum;  e[a] = exp32(x[a] - mx);  sum = e[0] + .. + e[42] one after the
+ *     other from 0.0f with 0 for an illegal move;  pi[a] = e[a] / sum, 0 for an illegal move.
+ * Staging, z back-fill, game turnover, quota, surprise weighting (on this pi), the value mix and resignation (on the node's N and Q)
+ * work as without the feature.
+ *
+ * Device self-play: m = 0 = off (default); read by azr_selfplay_start*, a running self-play never sees a change.
+ * AZR_E_INVALID_ARGUMENT, with a reason in azr_last_error, for m outside [0, 43], a c_visit or c_scale that is not finite, or — when
+ * on — c_visit < 0 or c_scale <= 0.  azr_selfplay_start* returns AZR_E_INVALID_ARGUMENT, with a reason, when the Gumbel search is set
+ * together with Dirichlet noise, a playout cap or forced playouts; the handle stays as it was. */
+int azr_selfplay_set_gumbel(azr_engine* h, int m, float c_visit, float c_scale, uint32_t seed);
+/* host-stepped searches (azr_mcts_simulate / azr_mcts_begin..apply): the same search under the vector of azr_mcts_set_root_gumbel.
+ * Holds until set again; azr_selfplay_start* ends it.  Switching it on or off clears the trees, and so does the first azr_mcts_begin /
+ * azr_mcts_simulate after an arena while it is on (the arena's searches expand nodes without a vhat).  Refused
+ * (AZR_E_INVALID_ARGUMENT) while a root noise vector or forced playouts are in force, as those two setters are while it is. */
+int azr_mcts_set_gumbel(azr_engine* h, int m, float c_visit, float c_scale);
+/* g_host [G][43]: the vector of each game's root for the searches that follow, used as given; NULL = zeros */
+int azr_mcts_set_root_gumbel(azr_engine* h, const float* g_host);
+/* the vector in force at each game's current root, g_host [G][43] (a running self-play's draws, or what was set); zeros when no
+ * Gumbel search is in force */
+int azr_mcts_root_gumbel(azr_engine* h, float* g_host);
+/* of the last search's roots, by the device functions of the self-play decision: the record's pi, pi_host [G][43], and (optional)
+ * the completed Q, qhat_host [G][43], 0 on illegal moves; the decision's move, moves_host [G] (43 for a root that is not in the
+ * tree).  AZR_E_STATE when no Gumbel search is in force. */
+int azr_mcts_gumbel_policy(azr_engine* h, float* pi_host, float* qhat_host /*optional*/);
+int azr_mcts_gumbel_pick(azr_engine* h, uint8_t* moves_host);
+/* the draw alone, on the device: g_out [rows][43] for (game_seed[i], decision[i], valid[i], greedy[i] != 0 = a root above the threshold) */
+int azr_debug_root_gumbel(azr_engine* h, uint32_t seed, const uint32_t* game_seed, const uint32_t* decision, const uint64_t* valid,
+                          const uint8_t* greedy, int rows, float* g_out);
+/* the root-level selection alone, on the device, one wavefront per synthetic row: N, N0, act, Q, P, g [rows][43], vhat, valid and the
+ * claim index [rows] -> the move (43 = none) and cv.  m in [1, 43], n > 0. */
+int azr_debug_gumbel_select(azr_engine* h, int m, int n, float c_visit, float c_scale, const uint32_t* N, const uint32_t* N0,
+                            const uint32_t* act, const float* Q, const float* P, const float* g, const float* vhat,
+                            const uint64_t* valid, const uint32_t* claim, int rows, uint8_t* move_out, uint32_t* cv_out);
+/* exp32 alone, on the device: out[i] = exp32(x[i]), i < n */
+int azr_debug_exp32(azr_engine* h, const float* x, int n, float* out);
+
 /* ---- device-resident self-play (trainer move loop, alphazero_trainer.cpp:80-119) --------------------------- */
 /* (Re)start all G games: game g plays seeds base_seed + g, then base_seed + G + g, ... */
 int azr_selfplay_start(azr_engine* h, uint32_t base_seed);
