@@ -921,6 +921,56 @@ struct DevBuf {
 
 static int bad_argument(azr_engine* h, const std::string& why) { h->err = why; return AZR_E_INVALID_ARGUMENT; }
 
+// The staging of a boundary call around one launch.  in(): a device copy of a host array of n elements.  out(): a device buffer of n
+// elements that goes back to a host array after the launch (no host array: an output nobody asked for; the kernel still gets its
+// buffer).  The first HIP error is kept and makes the calls behind it return nullptr; STAGED_LAUNCH hands it to HIPCHK before anything
+// is launched.  Every buffer is freed when the struct goes.
+struct Stage {
+    struct Buf { void* dev; void* host; size_t bytes; };
+    azr_engine* h;
+    hipError_t err = hipSuccess;
+    std::vector<Buf> bufs;
+    explicit Stage(azr_engine* h_) : h(h_) {}
+    ~Stage() { for (Buf& b : bufs) hipFree(b.dev); }
+    void* buf(const void* src, void* dst, size_t bytes)
+    {
+        void* p = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&p, bytes ? bytes : 1);
+        if (err != hipSuccess) return nullptr;
+        bufs.push_back({p, dst, bytes});
+        if (src && bytes) err = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h->stream);
+        return p;
+    }
+    template <class T> const T* in(const T* src, size_t n) { return (const T*)buf(src, nullptr, n * sizeof(T)); }
+    template <class T> T* out(T* dst, size_t n) { return (T*)buf(nullptr, dst, n * sizeof(T)); }
+    hipError_t finish()   // behind the launch: its error, every output that was asked for, the stream drained
+    {
+        err = hipGetLastError();
+        for (Buf& b : bufs)
+            if (err == hipSuccess && b.host) err = hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream);
+        return err == hipSuccess ? hipStreamSynchronize(h->stream) : err;
+    }
+};
+#define STAGED_LAUNCH(st, kern, blocks, ...)                                                      \
+    do {                                                                                          \
+        HIPCHK((st).h, (st).err);                                                                 \
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, (st).h->stream, __VA_ARGS__);         \
+        HIPCHK((st).h, (st).finish());                                                            \
+    } while (0)
+
+// the first row of each game where the games' rows lie one behind the other; false where they are more than 2^31 - 1
+static bool first_rows(const uint32_t* game_len, int games, std::vector<uint32_t>& first, size_t& rows)
+{
+    first.resize((size_t)games);
+    rows = 0;
+    for (int i = 0; i < games; i++) {
+        first[i] = (uint32_t)rows;
+        rows += game_len[i];
+        if (rows > 0x7fffffffu) return false;
+    }
+    return true;
+}
+
 // one 32-bit field of every game's Ctl line <-> a packed host array of G values (`field` = offsetof(Ctl, ...)): a strided copy queued on
 // the handle's stream, the caller synchronises
 static hipError_t ctl_field_get(azr_engine* h, size_t field, void* dst)
@@ -1191,14 +1241,11 @@ extern "C" int azr_mcts_simulate(azr_engine* h)
 extern "C" int azr_mcts_root_stats(azr_engine* h, uint32_t* n, float* q, float* p)
 {
     ENTER(h);
-    const size_t sz = (size_t)h->d.G * MOVES * 4;
-    DevBuf bn, bq, bp;
-    HIPCHK(h, bn.alloc(sz)); HIPCHK(h, bq.alloc(sz)); HIPCHK(h, bp.alloc(sz));
-    LAUNCH(h, k_root_stats, h->d, (uint32_t*)bn.p, (float*)bq.p, (float*)bp.p, (float*)nullptr);
-    if (n) D2H(h, n, bn.p, sz);
-    if (q) D2H(h, q, bq.p, sz);
-    if (p) D2H(h, p, bp.p, sz);
-    SYNC(h);
+    const size_t sz = (size_t)h->d.G * MOVES;
+    Stage st(h);
+    uint32_t* dn = st.out(n, sz);
+    float *dq = st.out(q, sz), *dp = st.out(p, sz);
+    STAGED_LAUNCH(st, k_root_stats, h->d.G, h->d, dn, dq, dp, (float*)nullptr);
     return AZR_OK;
 }
 
@@ -1206,13 +1253,10 @@ extern "C" int azr_mcts_root_value(azr_engine* h, float* q, uint8_t* has_q)
 {
     ENTER(h);
     if (!q) return AZR_E_INVALID_ARGUMENT;
-    const size_t G = (size_t)h->d.G;
-    DevBuf bq, bh;
-    HIPCHK(h, bq.alloc(G * 4)); HIPCHK(h, bh.alloc(G));
-    LAUNCH(h, k_root_value, h->d, (float*)bq.p, (uint8_t*)bh.p);
-    D2H(h, q, bq.p, G * 4);
-    if (has_q) D2H(h, has_q, bh.p, G);
-    SYNC(h);
+    Stage st(h);
+    float* dq = st.out(q, (size_t)h->d.G);
+    uint8_t* dh = st.out(has_q, (size_t)h->d.G);
+    STAGED_LAUNCH(st, k_root_value, h->d.G, h->d, dq, dh);
     return AZR_OK;
 }
 
@@ -1371,17 +1415,11 @@ extern "C" int azr_debug_root_noise(azr_engine* h, float alpha, uint32_t noise_s
     if (int rc = alpha_check(h, "azr_debug_root_noise", alpha, false)) return rc;
     if (n < 0 || (n > 0 && (!game_seed || !decision || !valid || !eta_out))) return AZR_E_INVALID_ARGUMENT;
     if (n == 0) return AZR_OK;
-    DevBuf bs, bd, bv, bo;
-    HIPCHK(h, bs.alloc((size_t)n * 4)); HIPCHK(h, bd.alloc((size_t)n * 4)); HIPCHK(h, bv.alloc((size_t)n * 8));
-    HIPCHK(h, bo.alloc((size_t)n * MOVES * sizeof(float)));
-    H2D(h, bs.p, game_seed, (size_t)n * 4);
-    H2D(h, bd.p, decision, (size_t)n * 4);
-    H2D(h, bv.p, valid, (size_t)n * 8);
-    hipLaunchKernelGGL(k_debug_root_noise, dim3(n), dim3(64), 0, h->stream, alpha, noise_seed, (const uint32_t*)bs.p, (const uint32_t*)bd.p,
-                       (const uint64_t*)bv.p, (float*)bo.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, eta_out, bo.p, (size_t)n * MOVES * sizeof(float));
-    SYNC(h);
+    Stage st(h);
+    const uint32_t *ds = st.in(game_seed, (size_t)n), *dd = st.in(decision, (size_t)n);
+    const uint64_t* dv = st.in(valid, (size_t)n);
+    float* eta = st.out(eta_out, (size_t)n * MOVES);
+    STAGED_LAUNCH(st, k_debug_root_noise, n, alpha, noise_seed, ds, dd, dv, eta);
     return AZR_OK;
 }
 
@@ -1440,13 +1478,11 @@ extern "C" int azr_mcts_pruned_policy(azr_engine* h, float* pi, uint32_t* n_prun
     ENTER(h);
     if (!pi) return AZR_E_INVALID_ARGUMENT;
     const Dev d = search_view(h, h->mode);
-    const size_t sz = (size_t)h->d.G * MOVES * 4;
-    DevBuf bn, bp;
-    HIPCHK(h, bn.alloc(sz)); HIPCHK(h, bp.alloc(sz));
-    LAUNCH(h, k_pruned_policy, d, (uint32_t*)bn.p, (float*)bp.p);
-    if (n_pruned) D2H(h, n_pruned, bn.p, sz);
-    D2H(h, pi, bp.p, sz);
-    SYNC(h);
+    const size_t sz = (size_t)h->d.G * MOVES;
+    Stage st(h);
+    uint32_t* dn = st.out(n_pruned, sz);
+    float* dp = st.out(pi, sz);
+    STAGED_LAUNCH(st, k_pruned_policy, h->d.G, d, dn, dp);
     return AZR_OK;
 }
 
@@ -1487,33 +1523,18 @@ extern "C" int azr_debug_surprise_weights(azr_engine* h, float share, float max_
     if (int rc = surprise_check(h, "azr_debug_surprise_weights", share, max_weight)) return rc;
     if (!(share > 0.0f)) return bad_argument(h, "azr_debug_surprise_weights: share must lie in (0, 1]");
     if (games < 0 || (games > 0 && (!game_len || !game_seed))) return AZR_E_INVALID_ARGUMENT;
-    std::vector<uint32_t> first((size_t)games);
-    size_t rows = 0;
-    for (int i = 0; i < games; i++) {
-        first[i] = (uint32_t)rows;
-        rows += game_len[i];
-        if (rows > 0x7fffffffu) return bad_argument(h, "azr_debug_surprise_weights: more than 2^31 - 1 records");
-    }
+    std::vector<uint32_t> first;
+    size_t rows;
+    if (!first_rows(game_len, games, first, rows)) return bad_argument(h, "azr_debug_surprise_weights: more than 2^31 - 1 records");
     if (rows > 0 && (!pi || !prior || !valid || !kl_out || !w_out || !copies_out)) return AZR_E_INVALID_ARGUMENT;
     if (rows == 0) return AZR_OK;
-    DevBuf bp, bq, bv, bf, bl, bs, bk, bw, bc;
-    HIPCHK(h, bp.alloc(rows * MOVES * 4)); HIPCHK(h, bq.alloc(rows * MOVES * 4)); HIPCHK(h, bv.alloc(rows * 8));
-    HIPCHK(h, bf.alloc((size_t)games * 4)); HIPCHK(h, bl.alloc((size_t)games * 4)); HIPCHK(h, bs.alloc((size_t)games * 4));
-    HIPCHK(h, bk.alloc(rows * 4)); HIPCHK(h, bw.alloc(rows * 4)); HIPCHK(h, bc.alloc(rows * 4));
-    H2D(h, bp.p, pi, rows * MOVES * 4);
-    H2D(h, bq.p, prior, rows * MOVES * 4);
-    H2D(h, bv.p, valid, rows * 8);
-    H2D(h, bf.p, first.data(), (size_t)games * 4);
-    H2D(h, bl.p, game_len, (size_t)games * 4);
-    H2D(h, bs.p, game_seed, (size_t)games * 4);
-    hipLaunchKernelGGL(k_debug_surprise, dim3(games), dim3(64), 0, h->stream, share, max_weight, seed, (const float*)bp.p, (const float*)bq.p,
-                       (const uint64_t*)bv.p, (const uint32_t*)bf.p, (const uint32_t*)bl.p, (const uint32_t*)bs.p, (float*)bk.p, (float*)bw.p,
-                       (uint32_t*)bc.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, kl_out, bk.p, rows * 4);
-    D2H(h, w_out, bw.p, rows * 4);
-    D2H(h, copies_out, bc.p, rows * 4);
-    SYNC(h);
+    Stage st(h);
+    const float *dpi = st.in(pi, rows * MOVES), *dprior = st.in(prior, rows * MOVES);
+    const uint64_t* dv = st.in(valid, rows);
+    const uint32_t *df = st.in(first.data(), (size_t)games), *dl = st.in(game_len, (size_t)games), *ds = st.in(game_seed, (size_t)games);
+    float *dk = st.out(kl_out, rows), *dw = st.out(w_out, rows);
+    uint32_t* dc = st.out(copies_out, rows);
+    STAGED_LAUNCH(st, k_debug_surprise, games, share, max_weight, seed, dpi, dprior, dv, df, dl, ds, dk, dw, dc);
     return AZR_OK;
 }
 
@@ -1542,20 +1563,15 @@ extern "C" int azr_debug_value_mix(azr_engine* h, float q_share, const uint32_t*
     if (rows < 0 || (rows > 0 && (!N || !Q || !valid || !z || !q_out || !has_q_out || !z_out))) return AZR_E_INVALID_ARGUMENT;
     if (rows == 0) return AZR_OK;
     const size_t n = (size_t)rows;
-    DevBuf bn, bq, bv, bz, oq, oh, oz;
-    HIPCHK(h, bn.alloc(n * MOVES * 4)); HIPCHK(h, bq.alloc(n * MOVES * 4)); HIPCHK(h, bv.alloc(n * 8)); HIPCHK(h, bz.alloc(n * 4));
-    HIPCHK(h, oq.alloc(n * 4)); HIPCHK(h, oh.alloc(n)); HIPCHK(h, oz.alloc(n * 4));
-    H2D(h, bn.p, N, n * MOVES * 4);
-    H2D(h, bq.p, Q, n * MOVES * 4);
-    H2D(h, bv.p, valid, n * 8);
-    H2D(h, bz.p, z, n * 4);
-    hipLaunchKernelGGL(k_debug_value_mix, dim3(rows), dim3(64), 0, h->stream, q_share, (const uint32_t*)bn.p, (const float*)bq.p,
-                       (const uint64_t*)bv.p, (const float*)bz.p, (float*)oq.p, (uint8_t*)oh.p, (float*)oz.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, q_out, oq.p, n * 4);
-    D2H(h, has_q_out, oh.p, n);
-    D2H(h, z_out, oz.p, n * 4);
-    SYNC(h);
+    Stage st(h);
+    const uint32_t* dn = st.in(N, n * MOVES);
+    const float* dq = st.in(Q, n * MOVES);
+    const uint64_t* dv = st.in(valid, n);
+    const float* dz = st.in(z, n);
+    float* oq = st.out(q_out, n);
+    uint8_t* oh = st.out(has_q_out, n);
+    float* oz = st.out(z_out, n);
+    STAGED_LAUNCH(st, k_debug_value_mix, rows, q_share, dn, dq, dv, dz, oq, oh, oz);
     return AZR_OK;
 }
 
@@ -1608,13 +1624,9 @@ extern "C" int azr_selfplay_resign_state(azr_engine* h, uint8_t* run_host, uint8
         memset(run_host, 0, 2 * G); memset(first_host, 255, G); memset(holdout_host, 0, G);
         return AZR_OK;
     }
-    DevBuf br, bf, bh;
-    HIPCHK(h, br.alloc(2 * G)); HIPCHK(h, bf.alloc(G)); HIPCHK(h, bh.alloc(G));
-    LAUNCH(h, k_resign_state, h->d, (uint8_t*)br.p, (uint8_t*)bf.p, (uint8_t*)bh.p);
-    D2H(h, run_host, br.p, 2 * G);
-    D2H(h, first_host, bf.p, G);
-    D2H(h, holdout_host, bh.p, G);
-    SYNC(h);
+    Stage st(h);
+    uint8_t *dr = st.out(run_host, 2 * G), *df = st.out(first_host, G), *dh = st.out(holdout_host, G);
+    STAGED_LAUNCH(st, k_resign_state, h->d.G, h->d, dr, df, dh);
     return AZR_OK;
 }
 
@@ -1627,35 +1639,18 @@ extern "C" int azr_debug_resign(azr_engine* h, float q_resign, int streak, float
     if (streak <= 0) return bad_argument(h, "azr_debug_resign: streak must lie in [1, 255]");
     if (games < 0 || (games > 0 && (!game_len || !game_seed || !resign_row_out || !resigner_out || !holdout_out))) return AZR_E_INVALID_ARGUMENT;
     if (games == 0) return AZR_OK;
-    std::vector<uint32_t> first((size_t)games);
-    size_t rows = 0;
-    for (int i = 0; i < games; i++) {
-        first[i] = (uint32_t)rows;
-        rows += game_len[i];
-        if (rows > 0x7fffffffu) return bad_argument(h, "azr_debug_resign: more than 2^31 - 1 decisions");
-    }
+    std::vector<uint32_t> first;
+    size_t rows;
+    if (!first_rows(game_len, games, first, rows)) return bad_argument(h, "azr_debug_resign: more than 2^31 - 1 decisions");
     if (rows > 0 && (!q || !has_q || !player)) return AZR_E_INVALID_ARGUMENT;
     const size_t n = (size_t)games;
-    DevBuf bq, bh, bp, bf, bl, bs, orow, owho, ohold;
-    HIPCHK(h, bq.alloc(rows * 4)); HIPCHK(h, bh.alloc(rows)); HIPCHK(h, bp.alloc(rows));
-    HIPCHK(h, bf.alloc(n * 4)); HIPCHK(h, bl.alloc(n * 4)); HIPCHK(h, bs.alloc(n * 4));
-    HIPCHK(h, orow.alloc(n * 4)); HIPCHK(h, owho.alloc(n)); HIPCHK(h, ohold.alloc(n));
-    if (rows) {
-        H2D(h, bq.p, q, rows * 4);
-        H2D(h, bh.p, has_q, rows);
-        H2D(h, bp.p, player, rows);
-    }
-    H2D(h, bf.p, first.data(), n * 4);
-    H2D(h, bl.p, game_len, n * 4);
-    H2D(h, bs.p, game_seed, n * 4);
-    hipLaunchKernelGGL(k_debug_resign, dim3(games), dim3(64), 0, h->stream, q_resign, (uint32_t)streak, resign_threshold_of(holdout_share),
-                       seed, (const float*)bq.p, (const uint8_t*)bh.p, (const uint8_t*)bp.p, (const uint32_t*)bf.p, (const uint32_t*)bl.p,
-                       (const uint32_t*)bs.p, (int32_t*)orow.p, (uint8_t*)owho.p, (uint8_t*)ohold.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, resign_row_out, orow.p, n * 4);
-    D2H(h, resigner_out, owho.p, n);
-    D2H(h, holdout_out, ohold.p, n);
-    SYNC(h);
+    Stage st(h);   // (no decision at all: the three row arrays are empty, and the kernel still runs over the games)
+    const float* dq = st.in(q, rows);
+    const uint8_t *dh = st.in(has_q, rows), *dp = st.in(player, rows);
+    const uint32_t *df = st.in(first.data(), n), *dl = st.in(game_len, n), *ds = st.in(game_seed, n);
+    int32_t* orow = st.out(resign_row_out, n);
+    uint8_t *owho = st.out(resigner_out, n), *ohold = st.out(holdout_out, n);
+    STAGED_LAUNCH(st, k_debug_resign, games, q_resign, (uint32_t)streak, resign_threshold_of(holdout_share), seed, dq, dh, dp, df, dl, ds, orow, owho, ohold);
     return AZR_OK;
 }
 
@@ -1740,13 +1735,10 @@ extern "C" int azr_mcts_gumbel_policy(azr_engine* h, float* pi_host, float* qhat
     if (!pi_host) return AZR_E_INVALID_ARGUMENT;
     Dev d;
     if (int rc = gumbel_view(h, "azr_mcts_gumbel_policy", d)) return rc;
-    const size_t sz = (size_t)h->d.G * MOVES * 4;
-    DevBuf bq, bp;
-    HIPCHK(h, bq.alloc(sz)); HIPCHK(h, bp.alloc(sz));
-    LAUNCH(h, k_gumbel_policy, d, (float*)bq.p, (float*)bp.p);
-    if (qhat_host) D2H(h, qhat_host, bq.p, sz);
-    D2H(h, pi_host, bp.p, sz);
-    SYNC(h);
+    const size_t sz = (size_t)h->d.G * MOVES;
+    Stage st(h);
+    float *dq = st.out(qhat_host, sz), *dp = st.out(pi_host, sz);
+    STAGED_LAUNCH(st, k_gumbel_policy, h->d.G, d, dq, dp);
     return AZR_OK;
 }
 
@@ -1767,17 +1759,12 @@ extern "C" int azr_debug_root_gumbel(azr_engine* h, uint32_t seed, const uint32_
     if (rows < 0 || (rows > 0 && (!game_seed || !decision || !valid || !greedy || !g_out))) return AZR_E_INVALID_ARGUMENT;
     if (rows == 0) return AZR_OK;
     const size_t n = (size_t)rows;
-    DevBuf bs, bd, bv, bg, bo;
-    HIPCHK(h, bs.alloc(n * 4)); HIPCHK(h, bd.alloc(n * 4)); HIPCHK(h, bv.alloc(n * 8)); HIPCHK(h, bg.alloc(n)); HIPCHK(h, bo.alloc(n * MOVES * 4));
-    H2D(h, bs.p, game_seed, n * 4);
-    H2D(h, bd.p, decision, n * 4);
-    H2D(h, bv.p, valid, n * 8);
-    H2D(h, bg.p, greedy, n);
-    hipLaunchKernelGGL(k_debug_root_gumbel, dim3(rows), dim3(64), 0, h->stream, seed, (const uint32_t*)bs.p, (const uint32_t*)bd.p,
-                       (const uint64_t*)bv.p, (const uint8_t*)bg.p, (float*)bo.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, g_out, bo.p, n * MOVES * 4);
-    SYNC(h);
+    Stage st(h);
+    const uint32_t *ds = st.in(game_seed, n), *dd = st.in(decision, n);
+    const uint64_t* dv = st.in(valid, n);
+    const uint8_t* dg = st.in(greedy, n);
+    float* go = st.out(g_out, n * MOVES);
+    STAGED_LAUNCH(st, k_debug_root_gumbel, rows, seed, ds, dd, dv, dg, go);
     return AZR_OK;
 }
 
@@ -1790,21 +1777,15 @@ extern "C" int azr_debug_gumbel_select(azr_engine* h, int m, int n, float c_visi
     if (m <= 0 || n <= 0) return bad_argument(h, "azr_debug_gumbel_select: m must lie in [1, 43] and n be positive");
     if (rows < 0 || (rows > 0 && (!N || !N0 || !act || !Q || !P || !g || !vhat || !valid || !claim || !move_out || !cv_out))) return AZR_E_INVALID_ARGUMENT;
     if (rows == 0) return AZR_OK;
-    const size_t r = (size_t)rows, row = r * MOVES * 4;
-    DevBuf b[6], bh, bv, bc, om, oc;
-    const void* src[6] = {N, N0, act, Q, P, g};
-    for (int i = 0; i < 6; i++) { HIPCHK(h, b[i].alloc(row)); H2D(h, b[i].p, src[i], row); }
-    HIPCHK(h, bh.alloc(r * 4)); HIPCHK(h, bv.alloc(r * 8)); HIPCHK(h, bc.alloc(r * 4)); HIPCHK(h, om.alloc(r)); HIPCHK(h, oc.alloc(r * 4));
-    H2D(h, bh.p, vhat, r * 4);
-    H2D(h, bv.p, valid, r * 8);
-    H2D(h, bc.p, claim, r * 4);
-    hipLaunchKernelGGL(k_debug_gumbel_select, dim3(rows), dim3(64), 0, h->stream, (uint32_t)m, (uint32_t)n, c_visit, c_scale, (const uint32_t*)b[0].p,
-                       (const uint32_t*)b[1].p, (const uint32_t*)b[2].p, (const float*)b[3].p, (const float*)b[4].p, (const float*)b[5].p,
-                       (const float*)bh.p, (const uint64_t*)bv.p, (const uint32_t*)bc.p, (uint8_t*)om.p, (uint32_t*)oc.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, move_out, om.p, r);
-    D2H(h, cv_out, oc.p, r * 4);
-    SYNC(h);
+    const size_t r = (size_t)rows;
+    Stage st(h);
+    const uint32_t *dN = st.in(N, r * MOVES), *dN0 = st.in(N0, r * MOVES), *dact = st.in(act, r * MOVES);
+    const float *dQ = st.in(Q, r * MOVES), *dP = st.in(P, r * MOVES), *dg = st.in(g, r * MOVES), *dvh = st.in(vhat, r);
+    const uint64_t* dv = st.in(valid, r);
+    const uint32_t* dc = st.in(claim, r);
+    uint8_t* om = st.out(move_out, r);
+    uint32_t* oc = st.out(cv_out, r);
+    STAGED_LAUNCH(st, k_debug_gumbel_select, rows, (uint32_t)m, (uint32_t)n, c_visit, c_scale, dN, dN0, dact, dQ, dP, dg, dvh, dv, dc, om, oc);
     return AZR_OK;
 }
 
@@ -1813,13 +1794,10 @@ extern "C" int azr_debug_exp32(azr_engine* h, const float* x, int n, float* out)
     ENTER(h);
     if (n < 0 || (n > 0 && (!x || !out))) return AZR_E_INVALID_ARGUMENT;
     if (n == 0) return AZR_OK;
-    DevBuf bx, bo;
-    HIPCHK(h, bx.alloc((size_t)n * 4)); HIPCHK(h, bo.alloc((size_t)n * 4));
-    H2D(h, bx.p, x, (size_t)n * 4);
-    hipLaunchKernelGGL(k_debug_exp32, dim3((n + 63) / 64), dim3(64), 0, h->stream, (const float*)bx.p, n, (float*)bo.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, out, bo.p, (size_t)n * 4);
-    SYNC(h);
+    Stage st(h);
+    const float* dx = st.in(x, (size_t)n);
+    float* dout = st.out(out, (size_t)n);
+    STAGED_LAUNCH(st, k_debug_exp32, (n + 63) / 64, dx, n, dout);
     return AZR_OK;
 }
 
@@ -1853,15 +1831,10 @@ extern "C" int azr_debug_playout_cap(azr_engine* h, float full_prob, uint32_t ca
     if (int rc = full_prob_check(h, "azr_debug_playout_cap", full_prob, "")) return rc;
     if (n < 0 || (n > 0 && (!game_seed || !decision || !full_out))) return AZR_E_INVALID_ARGUMENT;
     if (n == 0) return AZR_OK;
-    DevBuf bs, bd, bo;
-    HIPCHK(h, bs.alloc((size_t)n * 4)); HIPCHK(h, bd.alloc((size_t)n * 4)); HIPCHK(h, bo.alloc((size_t)n));
-    H2D(h, bs.p, game_seed, (size_t)n * 4);
-    H2D(h, bd.p, decision, (size_t)n * 4);
-    hipLaunchKernelGGL(k_debug_playout_cap, dim3((n + 63) / 64), dim3(64), 0, h->stream, cap_threshold_of(full_prob), cap_seed, (const uint32_t*)bs.p,
-                       (const uint32_t*)bd.p, n, (uint8_t*)bo.p);
-    HIPCHK(h, hipGetLastError());
-    D2H(h, full_out, bo.p, (size_t)n);
-    SYNC(h);
+    Stage st(h);
+    const uint32_t *ds = st.in(game_seed, (size_t)n), *dd = st.in(decision, (size_t)n);
+    uint8_t* full = st.out(full_out, (size_t)n);
+    STAGED_LAUNCH(st, k_debug_playout_cap, (n + 63) / 64, cap_threshold_of(full_prob), cap_seed, ds, dd, n, full);
     return AZR_OK;
 }
 

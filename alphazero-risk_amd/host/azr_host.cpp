@@ -19,7 +19,35 @@ Settings SETTINGS;
 
 // ---- Settings ---------------------------------------------------------------------------------------------------
 namespace {
-struct Opt { const char* name; const char* desc; std::string def; bool is_bool; };
+// How a flag's value reaches its Settings member.  TEXT: read by name in Settings::init (the reference's flags, parsed with bare atoi /
+// atof as the reference does, and the flags with rules of their own).  The other kinds are parsed, range-checked and assigned by one
+// loop, in table order: REAL lo <= v <= hi (lo_open: lo < v), WHOLE the same over whole numbers, SWITCH 0 or 1, SEED a whole number in
+// [0, 2^32 - 1], SEED_UNCHECKED whatever strtoul makes of the text (--seed, --dir-seed, --cap-seed: as they always were).
+enum Kind { TEXT, REAL, WHOLE, SWITCH, SEED, SEED_UNCHECKED };
+struct Opt {
+    const char* name; const char* desc; std::string def; bool is_bool;
+    Kind kind = TEXT;
+    float Settings::*f = nullptr; int Settings::*i = nullptr; uint32_t Settings::*u = nullptr;   // the member it fills: the one of its kind
+    double lo = 0, hi = 0; bool lo_open = false;
+    const char* what = "";      // the tail of "--name: 'value' ..." when the value is refused
+    bool after_next = false;    // checked after the row below it (--resign-streak is checked before --resign-q)
+};
+Opt real(const char* name, const char* desc, const char* def, float Settings::*m, double lo, double hi, const char* what, bool lo_open = false, bool after_next = false)
+{
+    return {name, desc, def, false, REAL, m, nullptr, nullptr, lo, hi, lo_open, what, after_next};
+}
+Opt whole(const char* name, const char* desc, const char* def, int Settings::*m, double lo, double hi, const char* what)
+{
+    return {name, desc, def, false, WHOLE, nullptr, m, nullptr, lo, hi, false, what};
+}
+Opt onoff(const char* name, const char* desc, const char* def, int Settings::*m)
+{
+    return {name, desc, def, false, SWITCH, nullptr, m, nullptr, 0, 1, false, "is neither 0 nor 1"};
+}
+Opt seed(const char* name, const char* desc, const std::string& def, uint32_t Settings::*m, Kind kind)
+{
+    return {name, desc, def, false, kind, nullptr, nullptr, m, 0, 0, false, "is not a 32-bit seed"};
+}
 
 bool parse_bool(const std::string& v) { return !(v == "0" || v == "false" || v == "False" || v == "no"); }
 
@@ -95,28 +123,28 @@ void Settings::init(int argc, char* argv[])
         {"dtype2", "[this build] arithmetic of player 2's net in -m play --p1 az --p2 az", "--dtype", false},
         {"mcts2", "[this build] MCTS simulations of player 2 in -m play --p1 az --p2 az (a search budget per side)", "--mcts", false},
         {"hp2", "[this build] exploration factor of player 2 in -m play --p1 az --p2 az", "--hp", false},
-        {"seed", "[this build] base seed of the per-game RNG streams", std::to_string(BASE_SEED), false},
+        seed("seed", "[this build] base seed of the per-game RNG streams", std::to_string(BASE_SEED), &Settings::BASE_SEED, SEED_UNCHECKED),
         {"devices", "[this build] HIP device of every logical gpu, comma separated (default 0,1,..; \"0,0\" rehearses --gpus 2 on one card)", "", false},
         {"pair-halves", "[this build] mirrored pairs: 1 = both games of a pair at the same time on two slots, 0 = one after the other on one slot", std::to_string(CONCURRENT_PAIR_HALVES), true},
-        {"dir-alpha", "[this build] self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision (0 = the reference's constant --dnv; at most 10)", "0", false},
-        {"dir-seed", "[this build] seed of the self-play root noise (independent of --seed: the games' dice and deals do not move)", std::to_string(DIR_SEED), false},
-        {"cap-prob", "[this build] self-play playout cap: share of decisions that get the whole --mcts search, root noise and a training record; the others search --cap-fast simulations and write none (1 = off: every decision)", "1", false},
-        {"cap-fast", "[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])", "0", false},
-        {"cap-seed", "[this build] seed of the playout cap's coin (independent of --seed and --dir-seed: dice, deals and noise do not move)", std::to_string(CAP_SEED), false},
-        {"forced-k", "[this build] self-play forced playouts: a tried root move of a full decision is searched until it has sqrt(k * prior * visits) visits (0 = off; at most 8; KataGo runs 2)", "0", false},
-        {"prune-target", "[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits PUCT would not have spent (0 = off)", "0", false},
-        {"psw-share", "[this build] self-play policy surprise weighting: share of a finished game's record weight handed out in proportion to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off: every record once; at most 1; KataGo runs 0.5)", "0", false},
-        {"psw-max", "[this build] cap on one record's weight under --psw-share (within [1, 64])", "4", false},
-        {"psw-seed", "[this build] seed of the coin that rounds a record's weight to its copy count (independent of --seed, --dir-seed and --cap-seed)", std::to_string(PSW_SEED), false},
-        {"q-share", "[this build] self-play value mix: share of the search's root value q in the records' value target, z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1; Lc0's q_ratio)", "0", false},
-        {"resign-q", "[this build] self-play resignation: the bound on the search's root value q; a player whose q stays below it for --resign-streak of its own recorded decisions in a row gives the game up (within [-1, 1]; AlphaGo Zero, KataGo)", "-0.9", false},
-        {"resign-streak", "[this build] decisions in a row below --resign-q after which their player resigns (0 = off: every game is played to its end; at most 255)", "0", false},
-        {"resign-holdout", "[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose (within [0, 1])", "0.1", false},
-        {"resign-seed", "[this build] seed of the coin that holds a game out of resignation (independent of --seed, --dir-seed, --cap-seed and --psw-seed)", std::to_string(RESIGN_SEED), false},
-        {"gumbel-m", "[this build] self-play Gumbel root search with sequential halving: moves considered at a root, sampled without replacement through Gumbel noise; the winner is played and softmax(logit + sigma(completed Q)) recorded (0 = off: PUCT at the root, the visit distribution as pi; at most 43; not with --dir-alpha, --cap-prob or --forced-k; Danihelka et al. 2022)", "0", false},
-        {"gumbel-cvisit", "[this build] c_visit of sigma = ((c_visit + max N) * c_scale) * completed Q under --gumbel-m (at least 0)", "50", false},
-        {"gumbel-cscale", "[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1]: half the paper's, whose values lie in [0, 1] (above 0)", "0.5", false},
-        {"gumbel-seed", "[this build] seed of the Gumbel vectors (independent of --seed: the games' dice and deals do not move)", std::to_string(GUMBEL_SEED), false},
+        real("dir-alpha", "[this build] self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision (0 = the reference's constant --dnv; at most 10)", "0", &Settings::DIR_ALPHA, 0, 10, "is not a Dirichlet parameter (0 = off, at most 10)"),
+        seed("dir-seed", "[this build] seed of the self-play root noise (independent of --seed: the games' dice and deals do not move)", std::to_string(DIR_SEED), &Settings::DIR_SEED, SEED_UNCHECKED),
+        real("cap-prob", "[this build] self-play playout cap: share of decisions that get the whole --mcts search, root noise and a training record; the others search --cap-fast simulations and write none (1 = off: every decision)", "1", &Settings::CAP_PROB, 0, 1, "is not a probability (a number in [0, 1]; 1 = off)"),
+        whole("cap-fast", "[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])", "0", &Settings::CAP_FAST, 0, HUGE_VAL, "is not a simulation count (0 = off)"),
+        seed("cap-seed", "[this build] seed of the playout cap's coin (independent of --seed and --dir-seed: dice, deals and noise do not move)", std::to_string(CAP_SEED), &Settings::CAP_SEED, SEED_UNCHECKED),
+        real("forced-k", "[this build] self-play forced playouts: a tried root move of a full decision is searched until it has sqrt(k * prior * visits) visits (0 = off; at most 8; KataGo runs 2)", "0", &Settings::FORCED_K, 0, 8, "is not a forced-playout factor (a number in [0, 8]; 0 = off)"),
+        onoff("prune-target", "[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits PUCT would not have spent (0 = off)", "0", &Settings::PRUNE_TARGET),
+        real("psw-share", "[this build] self-play policy surprise weighting: share of a finished game's record weight handed out in proportion to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off: every record once; at most 1; KataGo runs 0.5)", "0", &Settings::PSW_SHARE, 0, 1, "is not a share (a number in [0, 1]; 0 = off)"),
+        real("psw-max", "[this build] cap on one record's weight under --psw-share (within [1, 64])", "4", &Settings::PSW_MAX, 1, 64, "is not a weight cap (a number in [1, 64])"),
+        seed("psw-seed", "[this build] seed of the coin that rounds a record's weight to its copy count (independent of --seed, --dir-seed and --cap-seed)", std::to_string(PSW_SEED), &Settings::PSW_SEED, SEED),
+        real("q-share", "[this build] self-play value mix: share of the search's root value q in the records' value target, z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1; Lc0's q_ratio)", "0", &Settings::Q_SHARE, 0, 1, "is not a share (a number in [0, 1]; 0 = off)"),
+        real("resign-q", "[this build] self-play resignation: the bound on the search's root value q; a player whose q stays below it for --resign-streak of its own recorded decisions in a row gives the game up (within [-1, 1]; AlphaGo Zero, KataGo)", "-0.9", &Settings::RESIGN_Q, -1, 1, "is not a bound on the root value (a number in [-1, 1])", false, true),
+        whole("resign-streak", "[this build] decisions in a row below --resign-q after which their player resigns (0 = off: every game is played to its end; at most 255)", "0", &Settings::RESIGN_STREAK, 0, 255, "is not a streak (a whole number in [0, 255]; 0 = off)"),
+        real("resign-holdout", "[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose (within [0, 1])", "0.1", &Settings::RESIGN_HOLDOUT, 0, 1, "is not a share (a number in [0, 1])"),
+        seed("resign-seed", "[this build] seed of the coin that holds a game out of resignation (independent of --seed, --dir-seed, --cap-seed and --psw-seed)", std::to_string(RESIGN_SEED), &Settings::RESIGN_SEED, SEED),
+        whole("gumbel-m", "[this build] self-play Gumbel root search with sequential halving: moves considered at a root, sampled without replacement through Gumbel noise; the winner is played and softmax(logit + sigma(completed Q)) recorded (0 = off: PUCT at the root, the visit distribution as pi; at most 43; not with --dir-alpha, --cap-prob or --forced-k; Danihelka et al. 2022)", "0", &Settings::GUMBEL_M, 0, 43, "is not a number of root moves (a whole number in [0, 43]; 0 = off)"),
+        real("gumbel-cvisit", "[this build] c_visit of sigma = ((c_visit + max N) * c_scale) * completed Q under --gumbel-m (at least 0)", "50", &Settings::GUMBEL_CVISIT, 0, 1e30, "is not a c_visit (a finite number, at least 0)"),
+        real("gumbel-cscale", "[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1]: half the paper's, whose values lie in [0, 1] (above 0)", "0.5", &Settings::GUMBEL_CSCALE, 0, 1e30, "is not a c_scale (a finite number above 0)", true),
+        seed("gumbel-seed", "[this build] seed of the Gumbel vectors (independent of --seed: the games' dice and deals do not move)", std::to_string(GUMBEL_SEED), &Settings::GUMBEL_SEED, SEED),
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -230,159 +258,58 @@ void Settings::init(int argc, char* argv[])
         }
         HP_EXPLORATION2 = (float)h2;
     }
-    BASE_SEED = (uint32_t)strtoul(get("seed").c_str(), nullptr, 10);
     CONCURRENT_PAIR_HALVES = parse_bool(get("pair-halves"));
-    {
+    // the typed rows: parsed, range-checked and assigned in table order; the first value out of range ends the run
+    auto fill = [&](const Opt& o) {
+        if (o.kind == TEXT) return;
+        const std::string v = get(o.name);
         char* end = nullptr;
-        const std::string av = get("dir-alpha");
-        const double al = strtod(av.c_str(), &end);
-        if (av.empty() || *end != '\0' || !(al >= 0.0) || al > 10.0) {
-            fprintf(stderr, "--dir-alpha: '%s' is not a Dirichlet parameter (0 = off, at most 10)\n", av.c_str());
+        bool bad = v.empty();
+        if (o.kind == SEED_UNCHECKED) {
+            this->*o.u = (uint32_t)strtoul(v.c_str(), nullptr, 10);
+            return;
+        } else if (o.kind == SEED) {
+            const unsigned long long x = bad || v[0] == '-' ? 0 : strtoull(v.c_str(), &end, 10);
+            bad = bad || v[0] == '-' || *end != '\0' || x > 0xffffffffull;
+            if (!bad) this->*o.u = (uint32_t)x;
+        } else if (o.kind == REAL) {
+            const double x = strtod(v.c_str(), &end);
+            bad = bad || *end != '\0' || !(o.lo_open ? x > o.lo : x >= o.lo) || !(x <= o.hi);   // (a NaN fails)
+            if (!bad) this->*o.f = (float)x;
+        } else {   // WHOLE, SWITCH
+            const long x = strtol(v.c_str(), &end, 10);
+            bad = bad || *end != '\0' || (double)x < o.lo || (double)x > o.hi;
+            if (!bad) this->*o.i = (int)x;
+        }
+        if (bad) {
+            fprintf(stderr, "--%s: '%s' %s\n", o.name, v.c_str(), o.what);
             exit(2);
         }
-        DIR_ALPHA = (float)al;
-    }
-    DIR_SEED = (uint32_t)strtoul(get("dir-seed").c_str(), nullptr, 10);
+    };
+    size_t row = 0;
+    auto fill_through = [&](const char* last) {   // from where the previous call stopped to the row named `last` (none: to the end)
+        for (bool more = true; more && row < opts.size(); row++) {
+            if (opts[row].after_next) { fill(opts[row + 1]); fill(opts[row]); row++; }   // (never the two last rows of a call)
+            else fill(opts[row]);
+            more = strcmp(opts[row].name, last) != 0;
+        }
+    };
+    // the rules between flags, where they always stood among the range checks
+    fill_through("cap-fast");
     {
-        char* end = nullptr;
-        const std::string pv = get("cap-prob");
-        const double pr = strtod(pv.c_str(), &end);
-        if (pv.empty() || *end != '\0' || !(pr >= 0.0) || pr > 1.0) {
-            fprintf(stderr, "--cap-prob: '%s' is not a probability (a number in [0, 1]; 1 = off)\n", pv.c_str());
-            exit(2);
-        }
-        CAP_PROB = (float)pr;
-        const std::string fv = get("cap-fast");
-        const long fs = strtol(fv.c_str(), &end, 10);
-        if (fv.empty() || *end != '\0' || fs < 0) {
-            fprintf(stderr, "--cap-fast: '%s' is not a simulation count (0 = off)\n", fv.c_str());
-            exit(2);
-        }
+        const long fs = strtol(get("cap-fast").c_str(), nullptr, 10);   // (the whole number: CAP_FAST is its low 32 bits)
         const int threads = std::max(1, std::min(8, THREADS_PER_MCTS));
         if (CAP_PROB < 1.0f && fs > 0 && (fs < threads || fs > MCTS_SIMULATIONS)) {   // the cap is on: F - F % T descents, at most a full decision's
             fprintf(stderr, "--cap-fast: %ld simulations are outside [%d search threads (-t), %d simulations (--mcts)]\n", fs, threads, MCTS_SIMULATIONS);
             exit(2);
         }
-        CAP_FAST = (int)fs;
     }
-    CAP_SEED = (uint32_t)strtoul(get("cap-seed").c_str(), nullptr, 10);
-    {
-        char* end = nullptr;
-        const std::string kv = get("forced-k");
-        const double fk = strtod(kv.c_str(), &end);
-        if (kv.empty() || *end != '\0' || !(fk >= 0.0) || fk > 8.0) {
-            fprintf(stderr, "--forced-k: '%s' is not a forced-playout factor (a number in [0, 8]; 0 = off)\n", kv.c_str());
-            exit(2);
-        }
-        FORCED_K = (float)fk;
-        const std::string pv = get("prune-target");
-        const long pt = strtol(pv.c_str(), &end, 10);
-        if (pv.empty() || *end != '\0' || (pt != 0 && pt != 1)) {
-            fprintf(stderr, "--prune-target: '%s' is neither 0 nor 1\n", pv.c_str());
-            exit(2);
-        }
-        if (pt == 1 && !(FORCED_K > 0.0f)) {
-            fprintf(stderr, "--prune-target: 1 needs --forced-k above 0 (pruning subtracts forced playouts; there are none)\n");
-            exit(2);
-        }
-        PRUNE_TARGET = (int)pt;
+    fill_through("prune-target");
+    if (PRUNE_TARGET == 1 && !(FORCED_K > 0.0f)) {
+        fprintf(stderr, "--prune-target: 1 needs --forced-k above 0 (pruning subtracts forced playouts; there are none)\n");
+        exit(2);
     }
-    {
-        char* end = nullptr;
-        const std::string sv = get("psw-share");
-        const double sh = strtod(sv.c_str(), &end);
-        if (sv.empty() || *end != '\0' || !(sh >= 0.0) || sh > 1.0) {
-            fprintf(stderr, "--psw-share: '%s' is not a share (a number in [0, 1]; 0 = off)\n", sv.c_str());
-            exit(2);
-        }
-        PSW_SHARE = (float)sh;
-        const std::string mv = get("psw-max");
-        const double mx = strtod(mv.c_str(), &end);
-        if (mv.empty() || *end != '\0' || !(mx >= 1.0) || mx > 64.0) {
-            fprintf(stderr, "--psw-max: '%s' is not a weight cap (a number in [1, 64])\n", mv.c_str());
-            exit(2);
-        }
-        PSW_MAX = (float)mx;
-        const std::string dv = get("psw-seed");
-        const unsigned long long sd = dv.empty() || dv[0] == '-' ? 0 : strtoull(dv.c_str(), &end, 10);
-        if (dv.empty() || dv[0] == '-' || *end != '\0' || sd > 0xffffffffull) {
-            fprintf(stderr, "--psw-seed: '%s' is not a 32-bit seed\n", dv.c_str());
-            exit(2);
-        }
-        PSW_SEED = (uint32_t)sd;
-    }
-    {
-        char* end = nullptr;
-        const std::string sv = get("q-share");
-        const double sh = strtod(sv.c_str(), &end);
-        if (sv.empty() || *end != '\0' || !(sh >= 0.0) || sh > 1.0) {
-            fprintf(stderr, "--q-share: '%s' is not a share (a number in [0, 1]; 0 = off)\n", sv.c_str());
-            exit(2);
-        }
-        Q_SHARE = (float)sh;
-    }
-    {
-        char* end = nullptr;
-        const std::string kv = get("resign-streak");
-        const long sk = strtol(kv.c_str(), &end, 10);
-        if (kv.empty() || *end != '\0' || sk < 0 || sk > 255) {
-            fprintf(stderr, "--resign-streak: '%s' is not a streak (a whole number in [0, 255]; 0 = off)\n", kv.c_str());
-            exit(2);
-        }
-        RESIGN_STREAK = (int)sk;
-        const std::string qv = get("resign-q");
-        const double rq = strtod(qv.c_str(), &end);
-        if (qv.empty() || *end != '\0' || !(rq >= -1.0) || rq > 1.0) {
-            fprintf(stderr, "--resign-q: '%s' is not a bound on the root value (a number in [-1, 1])\n", qv.c_str());
-            exit(2);
-        }
-        RESIGN_Q = (float)rq;
-        const std::string hv = get("resign-holdout");
-        const double ho = strtod(hv.c_str(), &end);
-        if (hv.empty() || *end != '\0' || !(ho >= 0.0) || ho > 1.0) {
-            fprintf(stderr, "--resign-holdout: '%s' is not a share (a number in [0, 1])\n", hv.c_str());
-            exit(2);
-        }
-        RESIGN_HOLDOUT = (float)ho;
-        const std::string dv = get("resign-seed");
-        const unsigned long long sd = dv.empty() || dv[0] == '-' ? 0 : strtoull(dv.c_str(), &end, 10);
-        if (dv.empty() || dv[0] == '-' || *end != '\0' || sd > 0xffffffffull) {
-            fprintf(stderr, "--resign-seed: '%s' is not a 32-bit seed\n", dv.c_str());
-            exit(2);
-        }
-        RESIGN_SEED = (uint32_t)sd;
-    }
-    {
-        char* end = nullptr;
-        const std::string mv = get("gumbel-m");
-        const long gm = strtol(mv.c_str(), &end, 10);
-        if (mv.empty() || *end != '\0' || gm < 0 || gm > 43) {
-            fprintf(stderr, "--gumbel-m: '%s' is not a number of root moves (a whole number in [0, 43]; 0 = off)\n", mv.c_str());
-            exit(2);
-        }
-        GUMBEL_M = (int)gm;
-        const std::string vv = get("gumbel-cvisit");
-        const double cv = strtod(vv.c_str(), &end);
-        if (vv.empty() || *end != '\0' || !(cv >= 0.0) || !(cv <= 1e30)) {
-            fprintf(stderr, "--gumbel-cvisit: '%s' is not a c_visit (a finite number, at least 0)\n", vv.c_str());
-            exit(2);
-        }
-        GUMBEL_CVISIT = (float)cv;
-        const std::string sv = get("gumbel-cscale");
-        const double cs = strtod(sv.c_str(), &end);
-        if (sv.empty() || *end != '\0' || !(cs > 0.0) || !(cs <= 1e30)) {
-            fprintf(stderr, "--gumbel-cscale: '%s' is not a c_scale (a finite number above 0)\n", sv.c_str());
-            exit(2);
-        }
-        GUMBEL_CSCALE = (float)cs;
-        const std::string dv = get("gumbel-seed");
-        const unsigned long long sd = dv.empty() || dv[0] == '-' ? 0 : strtoull(dv.c_str(), &end, 10);
-        if (dv.empty() || dv[0] == '-' || *end != '\0' || sd > 0xffffffffull) {
-            fprintf(stderr, "--gumbel-seed: '%s' is not a 32-bit seed\n", dv.c_str());
-            exit(2);
-        }
-        GUMBEL_SEED = (uint32_t)sd;
-    }
+    fill_through("");   // (--gumbel-m with --dir-alpha is not refused here: azr_selfplay_start refuses it)
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
     DEVICE_MAP.clear();
@@ -824,6 +751,19 @@ void AlphaZeroPlayerGroup::takeTurns(int gpu, std::vector<State>& states, int8_t
 }
 
 // ---- trainer ------------------------------------------------------------------------------------------------------------
+// the self-play options of the command line (--help says what each does), in force for the games generated from here on
+static void applySelfplayOptions(Engine& e)
+{
+    const Settings& s = SETTINGS;
+    e.check(azr_selfplay_set_dirichlet(e.h, s.DIR_ALPHA, s.DIR_SEED), "selfplay_set_dirichlet");
+    e.check(azr_selfplay_set_playout_cap(e.h, s.CAP_PROB, s.CAP_FAST, s.CAP_SEED), "selfplay_set_playout_cap");
+    e.check(azr_selfplay_set_forced_playouts(e.h, s.FORCED_K, s.PRUNE_TARGET), "selfplay_set_forced_playouts");
+    e.check(azr_selfplay_set_surprise_weighting(e.h, s.PSW_SHARE, s.PSW_MAX, s.PSW_SEED), "selfplay_set_surprise_weighting");
+    e.check(azr_selfplay_set_value_mix(e.h, s.Q_SHARE), "selfplay_set_value_mix");
+    e.check(azr_selfplay_set_resign(e.h, s.RESIGN_Q, s.RESIGN_STREAK, s.RESIGN_HOLDOUT, s.RESIGN_SEED), "selfplay_set_resign");
+    e.check(azr_selfplay_set_gumbel(e.h, s.GUMBEL_M, s.GUMBEL_CVISIT, s.GUMBEL_CSCALE, s.GUMBEL_SEED), "selfplay_set_gumbel");
+}
+
 SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGroup> generate)
 {
     const int P = (int)generate->size();
@@ -850,20 +790,7 @@ SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGr
         Engine& e = *generate->getNN(i)->engine;
         // exactly `share` games are started and every one is played to its end (Counter::hasNext over
         // TRAIN_ITERATION_GAMES, alphazero_trainer.cpp:83)
-        // root noise of the generated games: --dir-alpha 0 (default) keeps the reference's constant
-        e.check(azr_selfplay_set_dirichlet(e.h, SETTINGS.DIR_ALPHA, SETTINGS.DIR_SEED), "selfplay_set_dirichlet");
-        // playout cap of the generated games: --cap-prob 1 / --cap-fast 0 (default) search and record every decision
-        e.check(azr_selfplay_set_playout_cap(e.h, SETTINGS.CAP_PROB, SETTINGS.CAP_FAST, SETTINGS.CAP_SEED), "selfplay_set_playout_cap");
-        // forced playouts / policy target pruning of the generated games: --forced-k 0 / --prune-target 0 (default) are the search and the records above
-        e.check(azr_selfplay_set_forced_playouts(e.h, SETTINGS.FORCED_K, SETTINGS.PRUNE_TARGET), "selfplay_set_forced_playouts");
-        // policy surprise weighting of the generated games' records: --psw-share 0 (default) writes every record once
-        e.check(azr_selfplay_set_surprise_weighting(e.h, SETTINGS.PSW_SHARE, SETTINGS.PSW_MAX, SETTINGS.PSW_SEED), "selfplay_set_surprise_weighting");
-        // value mix of the generated games' records: --q-share 0 (default) writes the bare game outcome
-        e.check(azr_selfplay_set_value_mix(e.h, SETTINGS.Q_SHARE), "selfplay_set_value_mix");
-        // resignation in the generated games: --resign-streak 0 (default) plays every game to its end
-        e.check(azr_selfplay_set_resign(e.h, SETTINGS.RESIGN_Q, SETTINGS.RESIGN_STREAK, SETTINGS.RESIGN_HOLDOUT, SETTINGS.RESIGN_SEED), "selfplay_set_resign");
-        // Gumbel root search in the generated games: --gumbel-m 0 (default) selects by PUCT at the root and records the visit distribution
-        e.check(azr_selfplay_set_gumbel(e.h, SETTINGS.GUMBEL_M, SETTINGS.GUMBEL_CVISIT, SETTINGS.GUMBEL_CSCALE, SETTINGS.GUMBEL_SEED), "selfplay_set_gumbel");
+        applySelfplayOptions(e);
         e.check(azr_selfplay_start_games(e.h, seed, share), "selfplay_start_games");
         azr_counters c{};
         std::vector<uint8_t> buf((size_t)e.games * 512 * AZR_RECORD_BYTES);

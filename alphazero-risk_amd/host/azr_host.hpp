@@ -24,8 +24,8 @@ namespace azrhost {
 
 // ------------------------------------------------------------------------------------------------------------------
 // Settings — same field names, flags, defaults and side effects (log/settings.txt) as src/settings.h:19-211.
-// `-m learn` is accepted as an alias of the reference's `-m train`.  Extra flags of this build: --blocks, --dtype (and --blocks2, --dtype2,
-// --mcts2, --hp2 for player 2's net and search in `-m play --p1 az --p2 az`; --dir-alpha, --dir-seed for sampled root noise in self-play; --cap-prob, --cap-fast, --cap-seed for its playout cap; --forced-k, --prune-target for forced playouts and policy target pruning; --psw-share, --psw-max, --psw-seed for policy surprise weighting of its records; --q-share for the value mix of their z; --resign-q, --resign-streak, --resign-holdout, --resign-seed for resignation with a no-resign holdout; --gumbel-m, --gumbel-cvisit, --gumbel-cscale, --gumbel-seed for the Gumbel root search with sequential halving), the others marked "[this build]" in --help.
+// `-m learn` is accepted as an alias of the reference's `-m train`.  The flags this build adds are marked "[this build]" in --help, which says
+// what each does: the net's shape and arithmetic, player 2's net and search in `-m play --p1 az --p2 az`, and the self-play options.
 // ------------------------------------------------------------------------------------------------------------------
 class Settings {
 public:

@@ -18,6 +18,7 @@ steps of an iteration are: all_gather of the new (s, pi, z) records, broadcast o
 reference trains on GPU 0 and hands the weights over through temp.bin), all_reduce of the six GameResults counters.
 """
 import argparse
+import collections
 import importlib
 import os
 import sys
@@ -29,6 +30,64 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 P = importlib.import_module("alphazero-risk_amd")
 shard_mod = importlib.import_module("alphazero-risk_amd.shard")
+
+
+# one self-play flag: for argparse, then its range lo <= v <= hi (lo_open: lo < v) and the tail of "--name: value ..." for a value outside it
+Flag = collections.namedtuple("Flag", "name type default help lo hi tail lo_open", defaults=(None, None, None, False))
+SEED = dict(lo=0, hi=0xFFFFFFFF, tail="is not a 32-bit seed")
+# The self-play options of the generated games (compare and benchmark games have none): the engine's setter of each and the flags that
+# are its arguments, in its order.  One row drives add_argument, the range check and the setter call.  --dir-alpha, --dir-seed and
+# --cap-seed have no range check here (the C++ host checks --dir-alpha); --cap-fast and --prune-target are checked in main(), with
+# the rules that tie them to other flags.
+SELFPLAY_OPTIONS = (
+    ("selfplay_set_dirichlet", (
+        Flag("--dir-alpha", float, 0.0, "self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision on the device "
+             "(0 = the reference's constant DIR_NOISE_VALUE; at most 10); compare and benchmark games have none"),
+        Flag("--dir-seed", int, 0, "seed of the self-play root noise (the games' dice and deals do not move)"))),
+    ("selfplay_set_playout_cap", (
+        Flag("--cap-prob", float, 1.0, "[this build] self-play playout cap: share of decisions that get the whole --mcts search, root noise and a training "
+             "record; the others search --cap-fast simulations and write none (1 = off)",
+             0.0, 1.0, "is not a probability (a number in [0, 1]; 1 = off)"),
+        Flag("--cap-fast", int, 0, "[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])"),
+        Flag("--cap-seed", int, 0, "[this build] seed of the playout cap's coin (dice, deals and root noise do not move)"))),
+    ("selfplay_set_forced_playouts", (
+        Flag("--forced-k", float, 0.0, "[this build] self-play forced playouts: a tried root move of a full decision is searched until it has "
+             "sqrt(k * prior * visits) visits (0 = off; at most 8)",
+             0.0, 8.0, "is not a forced-playout factor (a number in [0, 8]; 0 = off)"),
+        Flag("--prune-target", int, 0, "[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits "
+             "PUCT would not have spent (0 = off)"))),
+    ("selfplay_set_surprise_weighting", (
+        Flag("--psw-share", float, 0.0, "[this build] self-play policy surprise weighting: share of a finished game's record weight handed out in proportion "
+             "to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off; at most 1)",
+             0.0, 1.0, "is not a share (a number in [0, 1]; 0 = off)"),
+        Flag("--psw-max", float, 4.0, "[this build] cap on one record's weight under --psw-share (within [1, 64])",
+             1.0, 64.0, "is not a weight cap (a number in [1, 64])"),
+        Flag("--psw-seed", int, 0, "[this build] seed of the coin that rounds a record's weight to its copy count", **SEED))),
+    ("selfplay_set_value_mix", (
+        Flag("--q-share", float, 0.0, "[this build] self-play value mix: share of the search's root value q in the records' value target, "
+             "z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1)",
+             0.0, 1.0, "is not a share (a number in [0, 1]; 0 = off)"),)),
+    ("selfplay_set_resign", (
+        Flag("--resign-q", float, -0.9, "[this build] self-play resignation: the bound on the search's root value q; a player whose q stays below it for "
+             "--resign-streak of its own recorded decisions in a row gives the game up (within [-1, 1])",
+             -1.0, 1.0, "is not a bound on the root value (a number in [-1, 1])"),
+        Flag("--resign-streak", int, 0, "[this build] decisions in a row below --resign-q after which their player resigns (0 = off; at most 255)",
+             0, 255, "is not a streak (a whole number in [0, 255]; 0 = off)"),
+        Flag("--resign-holdout", float, 0.1, "[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose "
+             "(within [0, 1])", 0.0, 1.0, "is not a share (a number in [0, 1])"),
+        Flag("--resign-seed", int, 0, "[this build] seed of the coin that holds a game out of resignation", **SEED))),
+    ("selfplay_set_gumbel", (
+        Flag("--gumbel-m", int, 0, "[this build] self-play Gumbel root search with sequential halving: moves considered at a root, sampled without "
+             "replacement through Gumbel noise; the winner is played and softmax(logit + sigma(completed Q)) recorded "
+             "(0 = off; at most 43; not with --dir-alpha, --cap-prob or --forced-k)",
+             0, 43, "is not a number of root moves (a whole number in [0, 43]; 0 = off)"),
+        Flag("--gumbel-cvisit", float, 50.0, "[this build] c_visit of sigma = ((c_visit + max N) * c_scale) * completed Q under --gumbel-m (at least 0)",
+             0.0, 1e30, "is not a c_visit (a finite number, at least 0)"),
+        Flag("--gumbel-cscale", float, 0.5, "[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1] (above 0)",
+             0.0, 1e30, "is not a c_scale (a finite number above 0)", lo_open=True),
+        Flag("--gumbel-seed", int, 0, "[this build] seed of the Gumbel vectors", **SEED))),
+)
+SELFPLAY_FLAGS = {f.name[2:].replace("-", "_"): f for _, flags in SELFPLAY_OPTIONS for f in flags}   # by argparse's attribute name
 
 
 def arena_device(eng_new, eng_old, games, mirror=P.MIRROR_CONCURRENT, base_seed=1, collect=False):
@@ -166,6 +225,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
     os.makedirs("checkpoints", exist_ok=True)
     dtype = {"bf16": P.NET_BF16, "f16": P.NET_F16, "f32x": P.NET_F32X, "f32": P.NET_F32}[a.dtype]
     t = getattr(a, "t", 2)
+    opt = {f.name: getattr(a, dest, f.default) for dest, f in SELFPLAY_FLAGS.items()}   # (a caller's namespace may lack them: the defaults)
     # MIRROR_GAMES (settings.h:52): mirrored pairs; --pair-halves 1 plays a pair's two games at the same time on two slots
     mirror = P.MIRROR_CONCURRENT if getattr(a, "pair_halves", 1) and a.gpu_games >= 2 else P.MIRROR_SEQUENTIAL
     if rank != 0:
@@ -200,20 +260,13 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         share = shard_mod.split_count(a.tg, world, rank)   # one self-play shard per GPU (alphazero_trainer.cpp:41-57)
         new_recs = [np.zeros((0, 265), np.uint8)]
         c = dict(games_finished=0, simulations=0, errors=0)
-        resign_on = getattr(a, "resign_streak", 0) > 0
+        resign_on = opt["--resign-streak"] > 0
         rs = dict(resigned=0, holdout_games=0, holdout_would_resign=0, holdout_not_lost=0)
         if share > 0:
             # exactly `share` games, each played to its end (Counter::hasNext, alphazero_trainer.cpp:83); this rank's seed
             # stream continues where its previous iteration stopped, so no (iteration, rank) pair ever replays a game
-            gen.selfplay_set_dirichlet(getattr(a, "dir_alpha", 0.0), getattr(a, "dir_seed", 0))   # root noise of the generated games only (0 = the reference's constant)
-            gen.selfplay_set_playout_cap(getattr(a, "cap_prob", 1.0), getattr(a, "cap_fast", 0), getattr(a, "cap_seed", 0))   # playout cap of the generated games only (1 / 0 = off)
-            gen.selfplay_set_forced_playouts(getattr(a, "forced_k", 0.0), getattr(a, "prune_target", 0))   # forced playouts / target pruning of the generated games only (0 / 0 = off)
-            gen.selfplay_set_surprise_weighting(getattr(a, "psw_share", 0.0), getattr(a, "psw_max", 4.0), getattr(a, "psw_seed", 0))   # surprise weighting of the generated games' records only (0 = every record once)
-            gen.selfplay_set_value_mix(getattr(a, "q_share", 0.0))   # value mix of the generated games' records only (0 = the bare game outcome)
-            gen.selfplay_set_resign(getattr(a, "resign_q", -0.9), getattr(a, "resign_streak", 0), getattr(a, "resign_holdout", 0.1),
-                                    getattr(a, "resign_seed", 0))   # resignation in the generated games only (streak 0 = every game to its end)
-            gen.selfplay_set_gumbel(getattr(a, "gumbel_m", 0), getattr(a, "gumbel_cvisit", 50.0), getattr(a, "gumbel_cscale", 0.5),
-                                    getattr(a, "gumbel_seed", 0))   # Gumbel root search in the generated games only (m 0 = PUCT at the root)
+            for setter, flags in SELFPLAY_OPTIONS:   # the options of the generated games only
+                getattr(gen, setter)(*(opt[f.name] for f in flags))
             gen.selfplay_start_games(shard_mod.selfplay_seed(a.seed, rank, games_started), share)
             games_started += share
             while c["games_finished"] + c["errors"] < share:
@@ -234,8 +287,8 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         dt = time.time() - t0
         log(f"Generated {len(new_recs)} new samples for total {len(records) + len(new_recs)}  "
             f"[{c['games_finished']} games, {c['simulations'] / dt:.0f} simulations/s, {c['games_finished'] / dt:.2f} games/s]")
-        if getattr(a, "gumbel_m", 0) > 0:
-            log(f"Gumbel root search: m {a.gumbel_m}, c_visit {a.gumbel_cvisit:g}, c_scale {a.gumbel_cscale:g}, seed {a.gumbel_seed}")
+        if opt["--gumbel-m"] > 0:
+            log(f"Gumbel root search: m {opt['--gumbel-m']}, c_visit {opt['--gumbel-cvisit']:g}, c_scale {opt['--gumbel-cscale']:g}, seed {opt['--gumbel-seed']}")
         if resign_on:   # the holdout's false positives: would-be resigners that went on not to lose
             fp = f"{rs['holdout_not_lost'] / rs['holdout_would_resign']:.3f}" if rs["holdout_would_resign"] else "n/a"
             log(f"Resignation: {rs['resigned']} resigned, {rs['holdout_games']} held out, {rs['holdout_would_resign']} of them would have resigned, "
@@ -352,47 +405,8 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32x", "f32"])
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--include-compare-samples", type=int, default=1)   # INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES
-    ap.add_argument("--dir-alpha", type=float, default=0.0,
-                    help="self-play root noise: Dirichlet(alpha) over the root's legal moves, drawn per decision on the device "
-                         "(0 = the reference's constant DIR_NOISE_VALUE; at most 10); compare and benchmark games have none")
-    ap.add_argument("--dir-seed", type=int, default=0, help="seed of the self-play root noise (the games' dice and deals do not move)")
-    ap.add_argument("--cap-prob", type=float, default=1.0,
-                    help="[this build] self-play playout cap: share of decisions that get the whole --mcts search, root noise and a training "
-                         "record; the others search --cap-fast simulations and write none (1 = off)")
-    ap.add_argument("--cap-fast", type=int, default=0, help="[this build] simulations of a fast decision under --cap-prob (0 = off; else within [-t, --mcts])")
-    ap.add_argument("--cap-seed", type=int, default=0, help="[this build] seed of the playout cap's coin (dice, deals and root noise do not move)")
-    ap.add_argument("--forced-k", type=float, default=0.0,
-                    help="[this build] self-play forced playouts: a tried root move of a full decision is searched until it has "
-                         "sqrt(k * prior * visits) visits (0 = off; at most 8)")
-    ap.add_argument("--prune-target", type=int, default=0,
-                    help="[this build] self-play policy target pruning under --forced-k: 1 = the recorded pi leaves out the forced visits "
-                         "PUCT would not have spent (0 = off)")
-    ap.add_argument("--psw-share", type=float, default=0.0,
-                    help="[this build] self-play policy surprise weighting: share of a finished game's record weight handed out in proportion "
-                         "to KL(recorded pi || net prior); a record is then written floor(w) or ceil(w) times (0 = off; at most 1)")
-    ap.add_argument("--psw-max", type=float, default=4.0, help="[this build] cap on one record's weight under --psw-share (within [1, 64])")
-    ap.add_argument("--psw-seed", type=int, default=0, help="[this build] seed of the coin that rounds a record's weight to its copy count")
-    ap.add_argument("--q-share", type=float, default=0.0,
-                    help="[this build] self-play value mix: share of the search's root value q in the records' value target, "
-                         "z' = (1 - share) * z + share * q (0 = off: the bare game outcome; at most 1)")
-    ap.add_argument("--resign-q", type=float, default=-0.9,
-                    help="[this build] self-play resignation: the bound on the search's root value q; a player whose q stays below it for "
-                         "--resign-streak of its own recorded decisions in a row gives the game up (within [-1, 1])")
-    ap.add_argument("--resign-streak", type=int, default=0,
-                    help="[this build] decisions in a row below --resign-q after which their player resigns (0 = off; at most 255)")
-    ap.add_argument("--resign-holdout", type=float, default=0.1,
-                    help="[this build] share of the self-play games that never resign and report how often the would-be resigner did not lose "
-                         "(within [0, 1])")
-    ap.add_argument("--resign-seed", type=int, default=0, help="[this build] seed of the coin that holds a game out of resignation")
-    ap.add_argument("--gumbel-m", type=int, default=0,
-                    help="[this build] self-play Gumbel root search with sequential halving: moves considered at a root, sampled without "
-                         "replacement through Gumbel noise; the winner is played and softmax(logit + sigma(completed Q)) recorded "
-                         "(0 = off; at most 43; not with --dir-alpha, --cap-prob or --forced-k)")
-    ap.add_argument("--gumbel-cvisit", type=float, default=50.0,
-                    help="[this build] c_visit of sigma = ((c_visit + max N) * c_scale) * completed Q under --gumbel-m (at least 0)")
-    ap.add_argument("--gumbel-cscale", type=float, default=0.5,
-                    help="[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1] (above 0)")
-    ap.add_argument("--gumbel-seed", type=int, default=0, help="[this build] seed of the Gumbel vectors")
+    for f in SELFPLAY_FLAGS.values():
+        ap.add_argument(f.name, type=f.type, default=f.default, help=f.help)
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -406,40 +420,21 @@ def main():
                     help="1 = the data-parallel step's sums go through torch.distributed (one host hand-over each) instead of the engine's own "
                          "in-stream RCCL communicator")
     a = ap.parse_args()
-    if not 0.0 <= a.cap_prob <= 1.0:   # (a NaN fails both comparisons)
-        ap.error(f"--cap-prob: {a.cap_prob} is not a probability (a number in [0, 1]; 1 = off)")
+    def check(*names):   # the table's range checks of these flags, in this order (a NaN fails every comparison)
+        for f, v in ((SELFPLAY_FLAGS[n], getattr(a, n)) for n in names):
+            if not ((f.lo < v if f.lo_open else f.lo <= v) and v <= f.hi):
+                ap.error(f"{f.name}: {v} {f.tail}")
+
+    check("cap_prob")
     if a.cap_fast < 0 or (a.cap_prob < 1.0 and a.cap_fast > 0 and not a.t <= a.cap_fast <= a.mcts):
         ap.error(f"--cap-fast: {a.cap_fast} simulations are outside [{a.t} search threads (-t), {a.mcts} simulations (--mcts)]")
-    if not 0.0 <= a.forced_k <= 8.0:   # (a NaN fails both comparisons)
-        ap.error(f"--forced-k: {a.forced_k} is not a forced-playout factor (a number in [0, 8]; 0 = off)")
+    check("forced_k")
     if a.prune_target not in (0, 1) or (a.prune_target == 1 and not a.forced_k > 0.0):
         ap.error(f"--prune-target: {a.prune_target} is neither 0 nor 1, or is 1 without --forced-k above 0")
-    if not 0.0 <= a.psw_share <= 1.0:   # (a NaN fails both comparisons)
-        ap.error(f"--psw-share: {a.psw_share} is not a share (a number in [0, 1]; 0 = off)")
-    if not 1.0 <= a.psw_max <= 64.0:
-        ap.error(f"--psw-max: {a.psw_max} is not a weight cap (a number in [1, 64])")
-    if not 0 <= a.psw_seed <= 0xFFFFFFFF:
-        ap.error(f"--psw-seed: {a.psw_seed} is not a 32-bit seed")
-    if not 0.0 <= a.q_share <= 1.0:   # (a NaN fails both comparisons)
-        ap.error(f"--q-share: {a.q_share} is not a share (a number in [0, 1]; 0 = off)")
-    if not 0 <= a.gumbel_m <= 43:
-        ap.error(f"--gumbel-m: {a.gumbel_m} is not a number of root moves (a whole number in [0, 43]; 0 = off)")
-    if not 0.0 <= a.gumbel_cvisit <= 1e30:   # (a NaN fails both comparisons)
-        ap.error(f"--gumbel-cvisit: {a.gumbel_cvisit} is not a c_visit (a finite number, at least 0)")
-    if not 0.0 < a.gumbel_cscale <= 1e30:
-        ap.error(f"--gumbel-cscale: {a.gumbel_cscale} is not a c_scale (a finite number above 0)")
-    if not 0 <= a.gumbel_seed <= 0xFFFFFFFF:
-        ap.error(f"--gumbel-seed: {a.gumbel_seed} is not a 32-bit seed")
+    check("psw_share", "psw_max", "psw_seed", "q_share", "gumbel_m", "gumbel_cvisit", "gumbel_cscale", "gumbel_seed")
     if a.gumbel_m > 0 and (a.dir_alpha > 0 or (a.cap_prob < 1 and a.cap_fast > 0) or a.forced_k > 0):
         ap.error("--gumbel-m: the Gumbel root search does not go with --dir-alpha, --cap-prob / --cap-fast or --forced-k")
-    if not 0 <= a.resign_streak <= 255:
-        ap.error(f"--resign-streak: {a.resign_streak} is not a streak (a whole number in [0, 255]; 0 = off)")
-    if not -1.0 <= a.resign_q <= 1.0:
-        ap.error(f"--resign-q: {a.resign_q} is not a bound on the root value (a number in [-1, 1])")
-    if not 0.0 <= a.resign_holdout <= 1.0:
-        ap.error(f"--resign-holdout: {a.resign_holdout} is not a share (a number in [0, 1])")
-    if not 0 <= a.resign_seed <= 0xFFFFFFFF:
-        ap.error(f"--resign-seed: {a.resign_seed} is not a 32-bit seed")
+    check("resign_streak", "resign_q", "resign_holdout", "resign_seed")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():
         learn(a)

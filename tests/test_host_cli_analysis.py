@@ -11,17 +11,9 @@ import numpy as np
 import pytest
 
 from gpu_common import ROOT, have_gpu, pkg
+from host_cli import exe  # noqa: F401  (a fixture)
 
-HOST = os.path.join(ROOT, "alphazero-risk_amd", "host")
-EXE = os.path.join(HOST, "AlphaZero_Risk_hip")
 F = r"-?(?:\d+\.\d{6}|nan|inf)"
-
-
-@pytest.fixture(scope="module")
-def exe():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "alphazero-risk_amd", "csrc")])
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    return EXE
 
 
 def test_analysis_fails_loudly_without_samples_or_device(exe, tmp_path):

@@ -1,26 +1,16 @@
 """`-m play --p1 az --p2 az` with a search budget of its own for player 2 (--mcts2 / --hp2).  CPU part: the flags are listed, written to
 log/settings.txt with the value in force, a value that is no budget is rejected, and without them the start line is the one the CLI
 printed before they existed.  GPU part: an arena of 8 simulations against 2 runs to its end through the CLI."""
-import os
 import subprocess
 
 import pytest
 
-from gpu_common import ROOT
+from host_cli import exe  # noqa: F401  (a fixture)
 
-HOST = os.path.join(ROOT, "alphazero-risk_amd", "host")
-EXE = os.path.join(HOST, "AlphaZero_Risk_hip")
 
 # what the CLI built from the commit before --mcts2 / --hp2 printed first for ARGS (Settings::describe, recorded from that build)
 ARGS = ["-m", "play", "--p1", "az", "--p2", "az", "--mcts", "8", "--blocks", "1", "--blocks2", "1", "--cg", "4", "--gpu-games", "6", "-t", "2"]
 START_LINE = "===> Starting program with GPUs: 1, Games per GPU 6, MCTS threads: 2, MCTS simulations 8"
-
-
-@pytest.fixture(scope="module")
-def exe():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "alphazero-risk_amd", "csrc")])
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    return EXE
 
 
 def _settings(tmp_path):

@@ -3,22 +3,12 @@ listed and written to log/settings.txt, and default to --blocks / --dtype.  GPU 
 the command line without the new flags still plays the games it played before them — checked against the same arena played through the
 binding with two handles of equal shape (same checkpoints, same seed), not against a string of the CLI's own."""
 import importlib
-import os
 import subprocess
 
 import pytest
 
-from gpu_common import ROOT
+from host_cli import exe  # noqa: F401  (a fixture)
 
-HOST = os.path.join(ROOT, "alphazero-risk_amd", "host")
-EXE = os.path.join(HOST, "AlphaZero_Risk_hip")
-
-
-@pytest.fixture(scope="module")
-def exe():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "alphazero-risk_amd", "csrc")])
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    return EXE
 
 
 def test_help_lists_the_second_nets_flags(exe):

@@ -2,91 +2,50 @@
 the flags are listed, written to log/settings.txt, and a probability outside [0, 1] or a fast budget outside [-t, --mcts] is rejected.
 GPU part: a learn iteration with the cap runs to its end and writes fewer samples than without, its samples are a function of
 --cap-seed, and --cap-prob 1 is the run without the flags."""
-import os
-import subprocess
-import sys
-
 import pytest
 
-from gpu_common import ROOT
+import host_cli as H
+from host_cli import exe  # noqa: F401  (a fixture)
 
-HOST = os.path.join(ROOT, "alphazero-risk_amd", "host")
-EXE = os.path.join(HOST, "AlphaZero_Risk_hip")
 FLAGS = ("--cap-prob", "--cap-fast", "--cap-seed")
 
 
-@pytest.fixture(scope="module")
-def exe():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "alphazero-risk_amd", "csrc")])
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    return EXE
-
-
 def test_help_and_settings_file_carry_the_flags(exe, tmp_path):
-    out = subprocess.run([exe, "--help"], capture_output=True, text=True, check=True).stdout
-    for flag in FLAGS:
-        line = [l for l in out.split("\n") if l.strip().startswith(flag)]
-        assert len(line) == 1 and "[this build]" in line[0], flag
-    # the settings file is written before the first engine is created: it exists whether or not the run finds a device
-    subprocess.run([exe, "-m", "play", "--p1", "sp", "--p2", "rp", "--cg", "2", "--gpu-games", "2", "--cap-prob", "0.25", "--cap-fast", "20",
-                    "--cap-seed", "7"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
-    s = open(tmp_path / "log" / "settings.txt").read().splitlines()
-    for flag, value in zip(FLAGS, ("0.25", "20", "7")):
-        assert [l.rsplit(")=", 1)[1] for l in s if l.startswith(flag[2:] + "(")] == [value]
+    H.check_flags_carried(exe, tmp_path, FLAGS, ("0.25", "20", "7"))
 
 
 def test_the_defaults_are_off(exe, tmp_path):
-    subprocess.run([exe, "-m", "play", "--p1", "sp", "--p2", "rp", "--cg", "2", "--gpu-games", "2"], cwd=tmp_path, capture_output=True, text=True,
-                   timeout=600)
-    s = open(tmp_path / "log" / "settings.txt").read().splitlines()
-    for flag, value in zip(FLAGS, ("1", "0", "0")):
-        assert [l.rsplit(")=", 1)[1] for l in s if l.startswith(flag[2:] + "(")] == [value]
+    H.check_defaults(exe, tmp_path, FLAGS, ("1", "0", "0"))
 
 
 @pytest.mark.parametrize("bad", ["-0.1", "1.5", "nan", "x", ""])
 def test_a_value_that_is_no_probability_is_rejected(exe, tmp_path, bad):
-    r = subprocess.run([exe, "-m", "learn", "--cap-prob=" + bad, "--cap-fast=2"], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 2 and "--cap-prob" in r.stderr
+    H.check_host_rejects(exe, tmp_path, ["--cap-prob=" + bad, "--cap-fast=2"], "--cap-prob")
 
 
 @pytest.mark.parametrize("bad", ["1", "9", "-2", "x"])
 def test_a_fast_budget_outside_threads_and_mcts_is_rejected(exe, tmp_path, bad):
-    r = subprocess.run([exe, "-m", "learn", "--mcts=8", "-t", "2", "--cap-prob=0.5", "--cap-fast=" + bad], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 2 and "--cap-fast" in r.stderr
+    H.check_host_rejects(exe, tmp_path, ["--mcts=8", "-t", "2", "--cap-prob=0.5", "--cap-fast=" + bad], "--cap-fast")
 
 
 @pytest.mark.parametrize("args,flag", [(["--cap-prob", "1.5", "--cap-fast", "2"], "--cap-prob"), (["--cap-prob", "nan", "--cap-fast", "2"], "--cap-prob"),
                                        (["--mcts", "8", "-t", "2", "--cap-prob", "0.5", "--cap-fast", "9"], "--cap-fast"),
                                        (["--mcts", "8", "-t", "2", "--cap-prob", "0.5", "--cap-fast", "1"], "--cap-fast")])
 def test_learn_py_rejects_the_same_values(tmp_path, args, flag):
-    """learn.py checks its arguments before it creates an engine: no device needed"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "alphazero-risk_amd", "learn.py"), *args], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 2 and flag in r.stderr.splitlines()[-1]
-
-
-def _learn(exe, path, *extra):
-    os.makedirs(path)
-    r = subprocess.run([exe, "-m", "learn", "--mcts=8", "--gpu-games=16", "--blocks=1", "--ti=1", "--tg=2", "--dtype=bf16",
-                        "--bs=64", "-e", "1", "--cg=2", "--ct=0", *extra],
-                       cwd=path, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr + r.stdout[-2000:]
-    assert "Self-play: 2 games" in r.stdout
-    raw = open(os.path.join(path, "data", "training_samples.bin"), "rb").read()
-    assert len(raw) > 8 + 265
-    return raw
+    H.check_learn_py_rejects(tmp_path, args, flag)
 
 
 @pytest.fixture(scope="module")
 def plain(exe, tmp_path_factory):
     """the run without the flags, shared"""
-    return _learn(exe, tmp_path_factory.mktemp("plain") / "run")
+    return H.learn_records(exe, tmp_path_factory.mktemp("plain") / "run").raw
 
 
 @pytest.mark.gpu
 def test_learn_with_a_cap_writes_fewer_samples_as_a_function_of_cap_seed(exe, tmp_path, plain):
-    a = _learn(exe, tmp_path / "a", "--cap-prob", "0.5", "--cap-fast", "2", "--cap-seed", "7")
-    b = _learn(exe, tmp_path / "b", "--cap-prob", "0.5", "--cap-fast", "2", "--cap-seed", "7")
-    c = _learn(exe, tmp_path / "c", "--cap-prob", "0.5", "--cap-fast", "2", "--cap-seed", "8")
+    a = H.learn_records(exe, tmp_path / "a", "--cap-prob", "0.5", "--cap-fast", "2", "--cap-seed", "7").raw
+    b = H.learn_records(exe, tmp_path / "b", "--cap-prob", "0.5", "--cap-fast", "2", "--cap-seed", "7").raw
+    c = H.learn_records(exe, tmp_path / "c", "--cap-prob", "0.5", "--cap-fast", "2", "--cap-seed", "8").raw
     assert len(a) < len(plain)
     assert a == b
     assert a != c
@@ -94,5 +53,5 @@ def test_learn_with_a_cap_writes_fewer_samples_as_a_function_of_cap_seed(exe, tm
 
 @pytest.mark.gpu
 def test_cap_prob_one_is_the_run_without_the_flags(exe, tmp_path, plain):
-    off = _learn(exe, tmp_path / "off", "--cap-prob", "1", "--cap-fast", "2", "--cap-seed", "7")
+    off = H.learn_records(exe, tmp_path / "off", "--cap-prob", "1", "--cap-fast", "2", "--cap-seed", "7").raw
     assert off == plain

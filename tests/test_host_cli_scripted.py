@@ -7,18 +7,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from gpu_common import ROOT
+from host_cli import exe  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
-HOST = os.path.join(ROOT, "alphazero-risk_amd", "host")
-EXE = os.path.join(HOST, "AlphaZero_Risk_hip")
-
-
-@pytest.fixture(scope="module")
-def exe():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "alphazero-risk_amd", "csrc")])
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    return EXE
 
 
 def test_train_data_mode(exe, tmp_path):
