@@ -99,6 +99,7 @@ EXPORTS = [
     "azr_selfplay_set_resign", "azr_selfplay_resign_stats", "azr_selfplay_resign_state", "azr_debug_resign",
     "azr_selfplay_set_gumbel", "azr_mcts_set_gumbel", "azr_mcts_set_root_gumbel", "azr_mcts_root_gumbel", "azr_mcts_gumbel_policy",
     "azr_mcts_gumbel_pick", "azr_debug_root_gumbel", "azr_debug_gumbel_select", "azr_debug_exp32",
+    "azr_selfplay_set_gumbel_tree", "azr_mcts_set_gumbel_tree", "azr_debug_gumbel_tree_select", "azr_mcts_node_stats",
 ]
 
 
@@ -197,6 +198,10 @@ def load_library(test_hooks=False):
         L.azr_mcts_gumbel_pick.argtypes = [C.c_void_p, C.c_void_p]
         L.azr_debug_root_gumbel.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.azr_debug_gumbel_select.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.azr_selfplay_set_gumbel_tree.argtypes = [C.c_void_p, C.c_int]
+        L.azr_mcts_set_gumbel_tree.argtypes = [C.c_void_p, C.c_int]
+        L.azr_debug_gumbel_tree_select.argtypes = [C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.azr_mcts_node_stats.argtypes = [C.c_void_p] * 8
         L.azr_debug_exp32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _libs[test_hooks] = L
         if not test_hooks:
@@ -445,6 +450,17 @@ class Engine:
         self._chk(self.L.azr_mcts_root_stats(self.h, _p(n), _p(q), _p(p)))
         return n, q, p
 
+    def node_stats(self, data160):
+        """the rows of the node of state g of data160 [G, 160] in game g's tree: (N, act, Q, P [G, 43], vhat [G], found [G] bool); zero
+        rows where the state is not in the tree.  Reads only."""
+        d = np.ascontiguousarray(data160, np.uint8)
+        assert d.shape == (self.G, 160)
+        n, act = np.zeros((self.G, 43), np.uint32), np.zeros((self.G, 43), np.uint32)
+        q, p = np.zeros((self.G, 43), np.float32), np.zeros((self.G, 43), np.float32)
+        vhat, found = np.zeros(self.G, np.float32), np.zeros(self.G, np.uint8)
+        self._chk(self.L.azr_mcts_node_stats(self.h, _p(d), _p(n), _p(act), _p(q), _p(p), _p(vhat), _p(found)))
+        return n, act, q, p, vhat, found.astype(bool)
+
     def policy(self):
         pi = np.zeros((self.G, 43), np.float32)
         self._chk(self.L.azr_mcts_policy(self.h, _p(pi)))
@@ -672,6 +688,27 @@ class Engine:
         self._chk(self.L.azr_debug_gumbel_select(self.h, int(m), int(n), float(c_visit), float(c_scale), _p(N), _p(N0), _p(act), _p(Q), _p(P),
                                                  _p(g), _p(vhat), _p(v), _p(c), rows, _p(mv), _p(cv)))
         return mv, cv
+
+    def selfplay_set_gumbel_tree(self, on):
+        """device self-play under selfplay_set_gumbel: 1 = below the root every node spends its visits in proportion to
+        softmax(logit + sigma(completed Q)) of its own rows, 0 (default) = PUCT there; read by selfplay_start*"""
+        self._chk(self.L.azr_selfplay_set_gumbel_tree(self.h, int(on)))
+
+    def set_gumbel_tree(self, on):
+        """host-stepped searches under set_gumbel: the same switch; the trees stay"""
+        self._chk(self.L.azr_mcts_set_gumbel_tree(self.h, int(on)))
+
+    def debug_gumbel_tree_select(self, c_visit, c_scale, N, act, Q, P, vhat, valid):
+        """the selection below the root alone on synthetic rows: N, act, Q, P [rows, 43], vhat, valid [rows] -> (move, score [rows, 43])"""
+        N, act = (np.ascontiguousarray(a, np.uint32) for a in (N, act))
+        Q, P, vhat = (np.ascontiguousarray(a, np.float32) for a in (Q, P, vhat))
+        v = np.ascontiguousarray(valid, np.uint64)
+        rows = len(v)
+        assert N.shape == act.shape == Q.shape == P.shape == (rows, MOVES) and vhat.shape == (rows,)
+        mv, score = np.zeros(rows, np.uint8), np.zeros((rows, MOVES), np.float32)
+        self._chk(self.L.azr_debug_gumbel_tree_select(self.h, float(c_visit), float(c_scale), _p(N), _p(act), _p(Q), _p(P), _p(vhat), _p(v), rows,
+                                                      _p(mv), _p(score)))
+        return mv, score
 
     def debug_exp32(self, x):
         """the engine's exponential alone, on the device"""

@@ -72,10 +72,9 @@ __global__ __launch_bounds__(64) void k_encode(Dev E, uint8_t* out /*[G][88]*/)
 
 // reference `Data` image (160 B) -> 64-B record.  The five masks / totalArmy of the image are derived data and
 // are ignored on import (recomputed on export).
-__global__ __launch_bounds__(64) void k_import160(Dev E, const uint8_t* data160)
+// the byte of the 64-B record this lane holds, from the image `d`
+__device__ __forceinline__ uint32_t import160_byte(const uint8_t* d)
 {
-    const int g = blockIdx.x;
-    const uint8_t* d = data160 + (size_t)g * 160;
     const uint32_t l = lane_id();
     uint32_t b = 0;
     if (l < LANDS) b = d[l];
@@ -91,7 +90,12 @@ __global__ __launch_bounds__(64) void k_import160(Dev E, const uint8_t* data160)
     b = l == GR_ROUND_HI ? d[145] : b;
     b = l == GR_CARDS0 ? d[48 + 40] : b;
     b = l == GR_CARDS1 ? d[96 + 40] : b;
-    E.state[(size_t)g * GREC + l] = (uint8_t)b;
+    return b;
+}
+__global__ __launch_bounds__(64) void k_import160(Dev E, const uint8_t* data160)
+{
+    const int g = blockIdx.x;
+    E.state[(size_t)g * GREC + lane_id()] = (uint8_t)import160_byte(data160 + (size_t)g * 160);
 }
 
 __global__ __launch_bounds__(64) void k_export160(Dev E, const uint8_t* records, uint8_t* data160)
@@ -189,11 +193,14 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev E)
 // gumbel_select_root under the root's vector g (E.root_g; self-play: a draw per new root), an expanded node keeps the net's value, and
 // a self-play decision takes gumbel_move and stages gumbel_policy, without an rFloat.  Staging, z back-fill, turnover, quota, surprise
 // weighting, value mix and resignation work on what they are handed.
-template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false, bool QMIX = false, bool GUMBEL = false>
+// GTREE (with GUMBEL only): below the root the descents select by gumbel_select_tree, the improved policy of each node's own rows, in
+// place of tree_select's PUCT; the root-level selection, the decision and the record are GUMBEL's.
+template <bool SELFPLAY, bool NOISE, bool CAP, bool FORCED, bool SURPRISE = false, bool QMIX = false, bool GUMBEL = false, bool GTREE = false>
 __global__ __launch_bounds__(64) void k_tree_step(Dev E)
 {
-    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED) && (SELFPLAY || !SURPRISE) && (SELFPLAY || !QMIX) && (!GUMBEL || (!NOISE && !CAP && !FORCED)),
-                  "CAP, SURPRISE and QMIX need SELFPLAY, FORCED implies NOISE, GUMBEL excludes NOISE, CAP and FORCED: launch_tree_step lists the thirty-two");
+    static_assert((SELFPLAY || !CAP) && (NOISE || !FORCED) && (SELFPLAY || !SURPRISE) && (SELFPLAY || !QMIX) && (!GUMBEL || (!NOISE && !CAP && !FORCED)) &&
+                      (GUMBEL || !GTREE),
+                  "CAP, SURPRISE and QMIX need SELFPLAY, FORCED implies NOISE, GUMBEL excludes NOISE, CAP and FORCED, GTREE needs GUMBEL: launch_tree_step lists the thirty-seven");
     __shared__ int8_t scratch[128];
     const int g = blockIdx.x;
     TP_BEGIN();
@@ -293,7 +300,7 @@ __global__ __launch_bounds__(64) void k_tree_step(Dev E)
             TP(14);
         }
         uint32_t err = 0;
-        int r = search_round<NOISE, FORCED, GUMBEL>(E, CAP ? Sd : S, g, t, c, root, scratch, k, err, eta, (FORCED && (!CAP || full)) ? E.forced_k : 0.0f);
+        int r = search_round<NOISE, FORCED, GUMBEL, GTREE>(E, CAP ? Sd : S, g, t, c, root, scratch, k, err, eta, (FORCED && (!CAP || full)) ? E.forced_k : 0.0f);
         if (r == RD_LEAF) break;
         if (r == RD_FAIL) {
             k.err++;
@@ -377,6 +384,39 @@ __global__ __launch_bounds__(64) void k_root_stats(Dev E, uint32_t* n_out, float
         if (q_out) q_out[(size_t)g * MOVES + l] = Q;
         if (p_out) p_out[(size_t)g * MOVES + l] = P;
         if (pi_out) pi_out[(size_t)g * MOVES + l] = pi;
+    }
+}
+
+// azr_mcts_node_stats: the rows of the node of state g of `data160` in game g's tree; the state lives in registers only, nothing is written
+// but the outputs
+__global__ __launch_bounds__(64) void k_node_stats(Dev E, const uint8_t* data160, uint32_t* n_out, uint32_t* act_out, float* q_out, float* p_out,
+                                                   float* vhat_out, uint8_t* found_out)
+{
+    const int g = blockIdx.x;
+    const Tree t = tree_of(E, g);
+    WS s;
+    ws_from_byte(s, import160_byte(data160 + (size_t)g * 160));
+    const uint32_t kd = ws_record_dword(s);
+    const uint32_t idx = tree_lookup(t, kd, key_hash(t, kd));
+    const uint32_t l = lane_id(), ll = l < MOVES ? l : 0;
+    uint32_t W = 0;
+    float Q = 0.0f, P = 0.0f, vhat = 0.0f;
+    if (idx != NO_NODE) {
+        const uint8_t* n = node_ptr(t, idx);
+        W = reinterpret_cast<const uint32_t*>(n + ND_N)[ll];
+        Q = reinterpret_cast<const float*>(n + ND_Q)[ll];
+        P = reinterpret_cast<const float*>(n + ND_P)[ll];
+        vhat = node_vhat(t, idx);
+    }
+    if (l < MOVES) {
+        n_out[(size_t)g * MOVES + l] = W & N_MASK;
+        if (act_out) act_out[(size_t)g * MOVES + l] = W >> 24;
+        q_out[(size_t)g * MOVES + l] = Q;
+        p_out[(size_t)g * MOVES + l] = P;
+    }
+    if (l == 0) {
+        if (vhat_out) vhat_out[g] = vhat;
+        found_out[g] = idx != NO_NODE ? 1 : 0;
     }
 }
 
@@ -663,6 +703,20 @@ __global__ __launch_bounds__(64) void k_debug_gumbel_select(uint32_t m, uint32_t
         move_out[i] = (uint8_t)mv;
         cv_out[i] = cv;
     }
+}
+
+// azr_debug_gumbel_tree_select: the selection below the root alone on synthetic rows, one wave per row
+__global__ __launch_bounds__(64) void k_debug_gumbel_tree_select(float c_visit, float c_scale, const uint32_t* N, const uint32_t* act, const float* Q,
+                                                                 const float* P, const float* vhat, const uint64_t* valid, uint8_t* move_out, float* score_out)
+{
+    const size_t i = blockIdx.x;
+    const uint32_t l = lane_id(), ll = l < MOVES ? l : 0;
+    const size_t at = i * MOVES + ll;
+    float score;
+    const uint32_t W = (N[at] & N_MASK) | (act[at] << 24);
+    const uint32_t mv = gumbel_select_tree(W, Q[at], P[at], rdlf(vhat[i], 0), rfl64(valid[i]), c_visit, c_scale, nullptr, nullptr, 0u, &score);
+    if (l < MOVES) score_out[at] = score;
+    if (l == 0) move_out[i] = (uint8_t)mv;
 }
 
 // azr_debug_exp32: the exponential alone, one lane per argument
@@ -1110,37 +1164,39 @@ extern "C" int azr_mcts_begin(azr_engine* h)
     return AZR_OK;
 }
 
-// The thirty-two k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
-// self-play also under a CAP, which doubles its three, each of those six with SURPRISE, and each of those twelve with QMIX; and the five
-// with GUMBEL: host-stepped, and self-play with and without SURPRISE and QMIX.  CAP, SURPRISE and QMIX need SELFPLAY, FORCED implies
-// NOISE, GUMBEL excludes NOISE, CAP and FORCED (k_tree_step asserts all five).
+// The thirty-seven k_tree_step instantiations, named here only: host-stepped or self-play, each plain, with NOISE and with NOISE + FORCED;
+// self-play also under a CAP, which doubles its three, each of those six with SURPRISE, and each of those twelve with QMIX; the five
+// with GUMBEL: host-stepped, and self-play with and without SURPRISE and QMIX; and those five again with GTREE.  CAP, SURPRISE and QMIX
+// need SELFPLAY, FORCED implies NOISE, GUMBEL excludes NOISE, CAP and FORCED, GTREE needs GUMBEL (k_tree_step asserts all six).
 // Callers say what is in force; forced playouts without root noise run the NOISE instantiation, on the constant vector.
 static int launch_tree_step(azr_engine* h, const Dev& d, bool selfplay, const StepOpts& o)
 {
     void (*step)(Dev) = nullptr;
 #define AZR_STEP(SP, N, C, F, W, M) \
     case (M) << 5 | (W) << 4 | (SP) << 3 | (N) << 2 | (C) << 1 | (F): step = k_tree_step<SP, N, C, F, W, M>; break
-#define AZR_STEP_GUMBEL(SP, W, M) \
-    case 1 << 6 | (M) << 5 | (W) << 4 | (SP) << 3: step = k_tree_step<SP, 0, 0, 0, W, M, 1>; break
+#define AZR_STEP_GUMBEL(SP, W, M, GT) \
+    case (GT) << 7 | 1 << 6 | (M) << 5 | (W) << 4 | (SP) << 3: step = k_tree_step<SP, 0, 0, 0, W, M, 1, GT>; break
 #define AZR_STEP_SP(W, M) \
     AZR_STEP(1, 0, 0, 0, W, M); AZR_STEP(1, 1, 0, 0, W, M); AZR_STEP(1, 1, 0, 1, W, M); \
     AZR_STEP(1, 0, 1, 0, W, M); AZR_STEP(1, 1, 1, 0, W, M); AZR_STEP(1, 1, 1, 1, W, M)
     // (the fifteen without QMIX first, in the order they always had, then their self-play twelve again with QMIX)
-    switch (o.gumbel << 6 | o.qmix << 5 | o.surprise << 4 | selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
+    switch (o.gtree << 7 | o.gumbel << 6 | o.qmix << 5 | o.surprise << 4 | selfplay << 3 | (o.noise || o.forced) << 2 | o.cap << 1 | o.forced) {
         AZR_STEP(0, 0, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 0, 0, 0); AZR_STEP(0, 1, 0, 1, 0, 0);
         AZR_STEP_SP(0, 0);
         AZR_STEP_SP(1, 0);
         AZR_STEP_SP(0, 1);
         AZR_STEP_SP(1, 1);
-        AZR_STEP_GUMBEL(0, 0, 0);
-        AZR_STEP_GUMBEL(1, 0, 0); AZR_STEP_GUMBEL(1, 1, 0); AZR_STEP_GUMBEL(1, 0, 1); AZR_STEP_GUMBEL(1, 1, 1);
+        AZR_STEP_GUMBEL(0, 0, 0, 0);
+        AZR_STEP_GUMBEL(1, 0, 0, 0); AZR_STEP_GUMBEL(1, 1, 0, 0); AZR_STEP_GUMBEL(1, 0, 1, 0); AZR_STEP_GUMBEL(1, 1, 1, 0);
+        AZR_STEP_GUMBEL(0, 0, 0, 1);
+        AZR_STEP_GUMBEL(1, 0, 0, 1); AZR_STEP_GUMBEL(1, 1, 0, 1); AZR_STEP_GUMBEL(1, 0, 1, 1); AZR_STEP_GUMBEL(1, 1, 1, 1);
     }
 #undef AZR_STEP_GUMBEL
 #undef AZR_STEP_SP
 #undef AZR_STEP
     if (!step) {
-        h->err = "launch_tree_step: a playout cap, surprise weighting or a value mix on a host-stepped search, or a Gumbel search with root "
-                 "noise, a playout cap or forced playouts: there is no such k_tree_step";
+        h->err = "launch_tree_step: a playout cap, surprise weighting or a value mix on a host-stepped search, a Gumbel search with root "
+                 "noise, a playout cap or forced playouts, or the Gumbel selection below the root without a Gumbel search: there is no such k_tree_step";
         return AZR_E_LOGIC;
     }
     hipLaunchKernelGGL(step, dim3(d.G), dim3(64), 0, h->stream, d);
@@ -1154,7 +1210,7 @@ static StepOpts options_in_force(const azr_engine* h, int mode)
 {
     if (mode == 2) return h->sp;
     if (mode == 3) return StepOpts{};
-    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f, false, false, h->host.gumbel_m > 0};
+    return StepOpts{h->host.noise, false, h->host.forced_k > 0.0f, false, false, h->host.gumbel_m > 0, h->host.gumbel_m > 0 && h->host.gumbel_tree};
 }
 // ... and the device view a search-related launch sees with it.  eta_const: no root vector is there to read (a self-play whose steps
 // carry NOISE keeps one per root).  Outside a self-play: the handle's without a self-play's leftovers, with azr_mcts_set_forced_playouts /
@@ -1249,6 +1305,20 @@ extern "C" int azr_mcts_root_stats(azr_engine* h, uint32_t* n, float* q, float* 
     return AZR_OK;
 }
 
+extern "C" int azr_mcts_node_stats(azr_engine* h, const void* data160, uint32_t* n, uint32_t* act, float* q, float* p, float* vhat, uint8_t* found)
+{
+    ENTER(h);
+    if (!data160 || !n || !q || !p || !found) return AZR_E_INVALID_ARGUMENT;
+    const size_t G = (size_t)h->d.G, sz = G * MOVES;
+    Stage st(h);
+    const uint8_t* dd = st.in((const uint8_t*)data160, G * 160);
+    uint32_t *dn = st.out(n, sz), *da = act ? st.out(act, sz) : nullptr;
+    float *dq = st.out(q, sz), *dp = st.out(p, sz), *dv = vhat ? st.out(vhat, G) : nullptr;
+    uint8_t* df = st.out(found, G);
+    STAGED_LAUNCH(st, k_node_stats, h->d.G, h->d, dd, dn, da, dq, dp, dv, df);
+    return AZR_OK;
+}
+
 extern "C" int azr_mcts_root_value(azr_engine* h, float* q, uint8_t* has_q)
 {
     ENTER(h);
@@ -1293,7 +1363,7 @@ static void resolve_selfplay_options(azr_engine* h)
     const SelfplayOpts& o = h->sp_set;
     Dev& d = h->d;
     h->host = HostOpts{};
-    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f, o.psw_share > 0.0f, o.q_share > 0.0f, o.gumbel_m > 0};
+    h->sp = StepOpts{o.alpha > 0.0f, o.cap_prob < 1.0f && o.cap_fast_sims > 0, o.forced_k > 0.0f, o.psw_share > 0.0f, o.q_share > 0.0f, o.gumbel_m > 0, o.gumbel_m > 0 && o.gumbel_tree != 0};
     d.noise_alpha = o.alpha;
     d.noise_seed = o.noise_seed;
     d.cap_threshold = cap_threshold_of(o.cap_prob);
@@ -1341,7 +1411,9 @@ static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long 
                             o.forced_k > 0.0f ? "forced playouts (azr_selfplay_set_forced_playouts)" : nullptr;
         if (other) return bad_argument(h, std::string("azr_selfplay_start: the Gumbel root search (azr_selfplay_set_gumbel) does not go with ") + other + ": switch one of them off");
         if (int rc = gumbel_alloc(h)) return rc;
-    }
+    } else if (h->sp_set.gumbel_tree)
+        return bad_argument(h, "azr_selfplay_start: the Gumbel selection below the root (azr_selfplay_set_gumbel_tree) needs the Gumbel root search "
+                               "(azr_selfplay_set_gumbel with m > 0): switch the one off or the other on");
     // the surprises' buffer, with the first self-play that weights its records: an engine that never does allocates none
     if (h->sp_set.psw_share > 0.0f && !h->d.stage_kl) HIPCHK(h, dmalloc(&h->d.stage_kl, (size_t)h->d.G * h->d.SCAP));
     // ... and the root values' buffer, with the first self-play that blends them into z
@@ -1687,11 +1759,35 @@ extern "C" int azr_mcts_set_gumbel(azr_engine* h, int m, float c_visit, float c_
     h->host.gumbel_m = m;
     h->host.gumbel_cvisit = m > 0 ? c_visit : 0.0f;
     h->host.gumbel_cscale = m > 0 ? c_scale : 0.0f;
+    if (m == 0) h->host.gumbel_tree = false;
     if (toggles) {   // no node without the net's value is searched by a Gumbel search: the trees start empty
         LAUNCH(h, k_tree_clear, h->d);
         if (h->mode == 2) h->mode = 0;   // (a running self-play's trees are gone with them)
     }
     SYNC(h);
+    return AZR_OK;
+}
+
+// 0 or 1, or the refusal
+static int gumbel_tree_check(azr_engine* h, const char* who, int on)
+{
+    return on == 0 || on == 1 ? AZR_OK : bad_argument(h, std::string(who) + ": on = " + std::to_string(on) + " is not 0 or 1");
+}
+
+extern "C" int azr_selfplay_set_gumbel_tree(azr_engine* h, int on)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (int rc = gumbel_tree_check(h, "azr_selfplay_set_gumbel_tree", on)) return rc;
+    h->sp_set.gumbel_tree = on;
+    return AZR_OK;
+}
+
+extern "C" int azr_mcts_set_gumbel_tree(azr_engine* h, int on)
+{
+    ENTER(h);
+    if (int rc = gumbel_tree_check(h, "azr_mcts_set_gumbel_tree", on)) return rc;
+    if (h->host.gumbel_m <= 0) return bad_argument(h, "azr_mcts_set_gumbel_tree: no host-stepped Gumbel search is in force (azr_mcts_set_gumbel with m > 0)");
+    h->host.gumbel_tree = on != 0;   // the trees stay: every node a GUMBEL step expanded has its vhat either way
     return AZR_OK;
 }
 
@@ -1786,6 +1882,24 @@ extern "C" int azr_debug_gumbel_select(azr_engine* h, int m, int n, float c_visi
     uint8_t* om = st.out(move_out, r);
     uint32_t* oc = st.out(cv_out, r);
     STAGED_LAUNCH(st, k_debug_gumbel_select, rows, (uint32_t)m, (uint32_t)n, c_visit, c_scale, dN, dN0, dact, dQ, dP, dg, dvh, dv, dc, om, oc);
+    return AZR_OK;
+}
+
+extern "C" int azr_debug_gumbel_tree_select(azr_engine* h, float c_visit, float c_scale, const uint32_t* N, const uint32_t* act, const float* Q,
+                                            const float* P, const float* vhat, const uint64_t* valid, int rows, uint8_t* move_out, float* score_out)
+{
+    ENTER(h);
+    if (int rc = gumbel_check(h, "azr_debug_gumbel_tree_select", 1, c_visit, c_scale)) return rc;
+    if (rows < 0 || (rows > 0 && (!N || !act || !Q || !P || !vhat || !valid || !move_out || !score_out))) return AZR_E_INVALID_ARGUMENT;
+    if (rows == 0) return AZR_OK;
+    const size_t r = (size_t)rows;
+    Stage st(h);
+    const uint32_t *dN = st.in(N, r * MOVES), *dact = st.in(act, r * MOVES);
+    const float *dQ = st.in(Q, r * MOVES), *dP = st.in(P, r * MOVES), *dvh = st.in(vhat, r);
+    const uint64_t* dv = st.in(valid, r);
+    uint8_t* om = st.out(move_out, r);
+    float* os = st.out(score_out, r * MOVES);
+    STAGED_LAUNCH(st, k_debug_gumbel_tree_select, rows, c_visit, c_scale, dN, dact, dQ, dP, dvh, dv, om, os);
     return AZR_OK;
 }
 

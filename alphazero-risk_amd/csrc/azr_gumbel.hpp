@@ -5,7 +5,8 @@
 // At path depth 0 the search visits the root's m best moves by g + logit — g a Gumbel vector drawn per root, so the m moves are a
 // sample without replacement from the prior — and halves the set as the budget is spent: the claim with index i goes to a move whose
 // search-local visit count equals the considered-visit number cv(i), the best of them by g + logit + sigma(completed Q).  The decision
-// plays the most visited of them and records softmax(logit + sigma(completed Q)).  Deeper levels keep tree_select's PUCT.
+// plays the most visited of them and records softmax(logit + sigma(completed Q)).  Deeper levels keep tree_select's PUCT, or, in a GTREE step, spend
+// their visits in proportion to that softmax of their own rows (gumbel_select_tree, the paper's deterministic non-root selection).
 //
 // g is a function of (gumbel seed, game seed, decision, move) alone — the counter-based hash of azr_noise.hpp under domain constants of
 // its own; nothing is taken from the game's minstd_rand0.  The net's value of a node (vhat) lives in the 44th float of its P row, written
@@ -193,6 +194,29 @@ __device__ __forceinline__ uint32_t gumbel_select_root(const Tree& t, uint32_t i
     const uint32_t mv = gumbel_select(W, N0, nr.Q, nr.P, g, node_vhat(t, idx), valid, i, m, n, c_visit, c_scale, cv);
     if (mv != NONE && l == mv) reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(nd) + ND_N)[l] = W + ACT_ONE;
     wave_mem_sync();
+    return mv;
+}
+
+// tree_select's place at path depth >= 1 of a GTREE step: the node's visits follow pi' = gumbel_policy of its own rows (W its N word),
+// the move = the legal one with the largest pi' - cnt / (1 + sum cnt), cnt the completed visits and those in flight.  Nothing is drawn.
+// nrow, touch: the node's N row and touch stamp for tree_select's bookkeeping (stamp, active_N++ on the chosen move); both null on
+// synthetic rows.  score[lane] goes out through `score_out` where somebody asks, 0 on an illegal move.
+__device__ __forceinline__ uint32_t gumbel_select_tree(uint32_t W, float Q, float P, float vhat, uint64_t valid, float c_visit, float c_scale,
+                                                       uint32_t* nrow, uint32_t* touch, uint32_t stamp, float* score_out = nullptr)
+{
+    const uint32_t l = lane_id();
+    const bool ok = l < (uint32_t)MOVES && ((valid >> l) & 1ULL);
+    if (touch && l == 0) *touch = stamp;
+    const float pi = gumbel_policy(gumbel_score(W & N_MASK, Q, P, vhat, valid, c_visit, c_scale), valid);
+    const uint32_t cnt = (W & N_MASK) + (W >> 24);
+    const float den = __fadd_rn(1.0f, (float)wave_sum_u32(ok ? cnt : 0u));
+    const float score = __fsub_rn(pi, __fdiv_rn((float)cnt, den));
+    if (score_out) *score_out = ok ? score : 0.0f;
+    const uint32_t mv = gumbel_best(ok, score);
+    if (nrow) {
+        if (mv != NONE && l == mv) nrow[l] = W + ACT_ONE;
+        wave_mem_sync();
+    }
     return mv;
 }
 

@@ -161,8 +161,9 @@ constexpr int ALOG = 16;
 
 // The options of the search variants (host side).  Which of them a tree step carries: root noise, a playout cap (self-play only),
 // forced playouts, policy surprise weighting of the records and the value mix of their z (both self-play only) — the template
-// arguments of k_tree_step after SELFPLAY; and the Gumbel root search, which excludes the first three.
-struct StepOpts { bool noise = false, cap = false, forced = false, surprise = false, qmix = false, gumbel = false; };
+// arguments of k_tree_step after SELFPLAY; the Gumbel root search, which excludes the first three; and its selection below the root
+// (gtree), which needs it.
+struct StepOpts { bool noise = false, cap = false, forced = false, surprise = false, qmix = false, gumbel = false, gtree = false; };
 // Host-stepped searches (azr_mcts_*): in force from the setter's call until the next azr_selfplay_start*.
 struct HostOpts {
     bool noise = false;        // azr_mcts_set_root_noise: a vector per game is set in d.root_eta
@@ -170,6 +171,7 @@ struct HostOpts {
     int sims = 0;              // azr_mcts_set_simulations: the budget (0 = the settings')
     int gumbel_m = 0;          // azr_mcts_set_gumbel (0 = off)
     float gumbel_cvisit = 0.0f, gumbel_cscale = 0.0f;
+    bool gumbel_tree = false;  // azr_mcts_set_gumbel_tree
 };
 // Device self-play, as the azr_selfplay_set_* setters leave them.  A running self-play never sees a change: azr_selfplay_start* resolves
 // them into a StepOpts and Dev's noise_*, cap_*, forced_k, prune, psw_*, q_share, resign_* and gumbel_*.
@@ -192,6 +194,7 @@ struct SelfplayOpts {
     int gumbel_m = 0;          // azr_selfplay_set_gumbel (0 = off)
     float gumbel_cvisit = 0.0f, gumbel_cscale = 0.0f;
     uint32_t gumbel_seed = 0;
+    int gumbel_tree = 0;       // azr_selfplay_set_gumbel_tree (0 = PUCT below the root)
 };
 
 // folded network parameters on device

@@ -266,7 +266,8 @@ enum : int { RD_DONE = 0, RD_LEAF = 1, RD_FAIL = 2 };
 // NOISE: the game's root noise vector `eta` (lane i <-> move i) enters the first selection of every descent (tree_select).
 // FORCED: that selection forces playouts with the factor `fk` (0 = not in this search: a fast decision under a playout cap).
 // GUMBEL: that selection is gumbel_select_root's (azr_gumbel.hpp) for the claim index sims_started - 1; `eta` carries the root's g.
-template <bool NOISE, bool FORCED = false, bool GUMBEL = false>
+// GTREE (with GUMBEL): every later selection of the descent is gumbel_select_tree's, under the root's c_visit and c_scale.
+template <bool NOISE, bool FORCED = false, bool GUMBEL = false, bool GTREE = false>
 __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
                                             StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
 {
@@ -315,6 +316,9 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
             if (GUMBEL && plen == 0)
                 mv = gumbel_select_root(t, idx, nr, c.search_id, E.root_n0 + (size_t)g * MOVES, c.sims_started - 1u, (uint32_t)E.gumbel_m,
                                         (uint32_t)S.simulations, E.gumbel_cvisit, E.gumbel_cscale, eta);
+            else if (GTREE)
+                mv = gumbel_select_tree(nr.W, nr.Q, nr.P, node_vhat(t, idx), (uint64_t)rfl(nr.valid_lo) | ((uint64_t)rfl(nr.valid_hi) << 32),
+                                        E.gumbel_cvisit, E.gumbel_cscale, reinterpret_cast<uint32_t*>(node_ptr(t, idx) + ND_N), t.touch + idx, c.search_id);
             else mv = tree_select<NOISE, FORCED>(t, idx, nr, S, c.search_id, scratch, plen == 0, E.noise_eps, eta, fk);
             TP(12);
             if (mv == NONE) { fail = true; s.err = E_LOGIC; break; }
@@ -346,13 +350,13 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
 // One round of AlphaZeroMCTS::simulate for all T search threads of the game, in thread order: every thread without a
 // pending leaf runs descents until it blocks on the net.  RD_LEAF = at least one leaf is waiting; RD_DONE = the counter
 // is exhausted and every claimed simulation is backed up.
-template <bool NOISE, bool FORCED = false, bool GUMBEL = false>
+template <bool NOISE, bool FORCED = false, bool GUMBEL = false, bool GTREE = false>
 __device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
                                             StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
 {
     for (int th = 0; th < E.T; th++) {
         if ((c.pending >> th) & 1u) continue;
-        int r = run_descents<NOISE, FORCED, GUMBEL>(E, S, g, t, th, c, root, scratch, k, err_out, eta, fk);
+        int r = run_descents<NOISE, FORCED, GUMBEL, GTREE>(E, S, g, t, th, c, root, scratch, k, err_out, eta, fk);
         if (r == RD_FAIL) { c.pending = 0; return RD_FAIL; }
         if (r == RD_LEAF && plen_get(c, th) == 0) break;  // root expansion: the threads start after setRootState
     }

@@ -179,10 +179,10 @@ __device__ __forceinline__ void ws_blank(WS& s)  // `State()` (state/state.h:86-
 }
 
 // ---- 64-byte record <-> wave ------------------------------------------------------------------------------
-__device__ __forceinline__ void ws_load(WS& s, const uint8_t* rec)
+// b: the record's byte `lane`
+__device__ __forceinline__ void ws_from_byte(WS& s, uint32_t b)
 {
     uint32_t l = lane_id();
-    uint32_t b = rec[l];
     s.la = l < LANDS ? b : 0xC0u;
     s.pk = lane_nbpack();
     s.nbm = nbmask_of(s.pk);
@@ -193,6 +193,7 @@ __device__ __forceinline__ void ws_load(WS& s, const uint8_t* rec)
     s.cards0 = rdl(b, GR_CARDS0); s.cards1 = rdl(b, GR_CARDS1);
     s.err = 0;
 }
+__device__ __forceinline__ void ws_load(WS& s, const uint8_t* rec) { ws_from_byte(s, rec[lane_id()]); }
 
 // the byte lane `l` contributes to the 64-byte record
 __device__ __forceinline__ uint32_t ws_record_byte(const WS& s)

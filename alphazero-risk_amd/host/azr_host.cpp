@@ -145,6 +145,7 @@ void Settings::init(int argc, char* argv[])
         real("gumbel-cvisit", "[this build] c_visit of sigma = ((c_visit + max N) * c_scale) * completed Q under --gumbel-m (at least 0)", "50", &Settings::GUMBEL_CVISIT, 0, 1e30, "is not a c_visit (a finite number, at least 0)"),
         real("gumbel-cscale", "[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1]: half the paper's, whose values lie in [0, 1] (above 0)", "0.5", &Settings::GUMBEL_CSCALE, 0, 1e30, "is not a c_scale (a finite number above 0)", true),
         seed("gumbel-seed", "[this build] seed of the Gumbel vectors (independent of --seed: the games' dice and deals do not move)", std::to_string(GUMBEL_SEED), &Settings::GUMBEL_SEED, SEED),
+        onoff("gumbel-tree", "[this build] under --gumbel-m, the selection below the root: 1 = every interior node spends its visits in proportion to softmax(logit + sigma(completed Q)) of its own rows, the paper's full search (0 = PUCT there)", "0", &Settings::GUMBEL_TREE),
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -309,7 +310,12 @@ void Settings::init(int argc, char* argv[])
         fprintf(stderr, "--prune-target: 1 needs --forced-k above 0 (pruning subtracts forced playouts; there are none)\n");
         exit(2);
     }
-    fill_through("");   // (--gumbel-m with --dir-alpha is not refused here: azr_selfplay_start refuses it)
+    fill_through("gumbel-tree");   // (--gumbel-m with --dir-alpha is not refused here: azr_selfplay_start refuses it)
+    if (GUMBEL_TREE == 1 && GUMBEL_M == 0) {
+        fprintf(stderr, "--gumbel-tree: 1 needs --gumbel-m above 0 (the selection below the root belongs to the Gumbel root search)\n");
+        exit(2);
+    }
+    fill_through("");
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
     DEVICE_MAP.clear();
@@ -762,6 +768,7 @@ static void applySelfplayOptions(Engine& e)
     e.check(azr_selfplay_set_value_mix(e.h, s.Q_SHARE), "selfplay_set_value_mix");
     e.check(azr_selfplay_set_resign(e.h, s.RESIGN_Q, s.RESIGN_STREAK, s.RESIGN_HOLDOUT, s.RESIGN_SEED), "selfplay_set_resign");
     e.check(azr_selfplay_set_gumbel(e.h, s.GUMBEL_M, s.GUMBEL_CVISIT, s.GUMBEL_CSCALE, s.GUMBEL_SEED), "selfplay_set_gumbel");
+    e.check(azr_selfplay_set_gumbel_tree(e.h, s.GUMBEL_TREE), "selfplay_set_gumbel_tree");
 }
 
 SelfPlayReport AlphaZeroTrainer::generateTrainData(std::shared_ptr<AlphaZeroNNGroup> generate)
@@ -835,8 +842,8 @@ void AlphaZeroTrainer::train(std::shared_ptr<AlphaZeroNNGroup> trainGroup, std::
                (unsigned long long)r.games, (unsigned long long)r.decisions, (unsigned long long)r.simulations, r.seconds,
                r.simulations / r.seconds, r.games / r.seconds);
         if (SETTINGS.GUMBEL_M > 0)
-            printf("Gumbel root search: m %d, c_visit %g, c_scale %g, seed %u\n", SETTINGS.GUMBEL_M, SETTINGS.GUMBEL_CVISIT, SETTINGS.GUMBEL_CSCALE,
-                   SETTINGS.GUMBEL_SEED);
+            printf("Gumbel root search: m %d, c_visit %g, c_scale %g, seed %u%s\n", SETTINGS.GUMBEL_M, SETTINGS.GUMBEL_CVISIT, SETTINGS.GUMBEL_CSCALE,
+                   SETTINGS.GUMBEL_SEED, SETTINGS.GUMBEL_TREE ? ", improved-policy selection below the root" : "");
         if (SETTINGS.RESIGN_STREAK > 0) {  // the holdout's false positives: would-be resigners that went on not to lose
             const azr_resign_stats& s = r.resign;
             printf("Resignation: %llu resigned, %llu held out, %llu of them would have resigned, %llu of those did not lose  =>  false-positive share ",

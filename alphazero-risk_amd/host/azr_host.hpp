@@ -93,6 +93,7 @@ public:
     float GUMBEL_CVISIT = 50.0f;         // --gumbel-cvisit, --gumbel-cscale: ... sigma = ((c_visit + max N) * c_scale) * completed Q, values in [-1, 1] ...
     float GUMBEL_CSCALE = 0.5f;
     uint32_t GUMBEL_SEED = 0;            // --gumbel-seed: ... and the seed of the Gumbel vectors (self-play generation of -m train only, like --dir-alpha; not with --dir-alpha, --cap-prob or --forced-k)
+    int GUMBEL_TREE = 0;                 // --gumbel-tree: ... and its selection below the root, by the improved policy of each node (0 = PUCT there)
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 

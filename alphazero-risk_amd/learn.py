@@ -86,6 +86,10 @@ SELFPLAY_OPTIONS = (
         Flag("--gumbel-cscale", float, 0.5, "[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1] (above 0)",
              0.0, 1e30, "is not a c_scale (a finite number above 0)", lo_open=True),
         Flag("--gumbel-seed", int, 0, "[this build] seed of the Gumbel vectors", **SEED))),
+    ("selfplay_set_gumbel_tree", (
+        Flag("--gumbel-tree", int, 0, "[this build] under --gumbel-m, the selection below the root: 1 = every interior node spends its visits in "
+             "proportion to softmax(logit + sigma(completed Q)) of its own rows, the paper's full search (0 = PUCT there)",
+             0, 1, "is not 0 or 1"),)),
 )
 SELFPLAY_FLAGS = {f.name[2:].replace("-", "_"): f for _, flags in SELFPLAY_OPTIONS for f in flags}   # by argparse's attribute name
 
@@ -288,7 +292,8 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         log(f"Generated {len(new_recs)} new samples for total {len(records) + len(new_recs)}  "
             f"[{c['games_finished']} games, {c['simulations'] / dt:.0f} simulations/s, {c['games_finished'] / dt:.2f} games/s]")
         if opt["--gumbel-m"] > 0:
-            log(f"Gumbel root search: m {opt['--gumbel-m']}, c_visit {opt['--gumbel-cvisit']:g}, c_scale {opt['--gumbel-cscale']:g}, seed {opt['--gumbel-seed']}")
+            log(f"Gumbel root search: m {opt['--gumbel-m']}, c_visit {opt['--gumbel-cvisit']:g}, c_scale {opt['--gumbel-cscale']:g}, seed {opt['--gumbel-seed']}"
+                + (", improved-policy selection below the root" if opt["--gumbel-tree"] else ""))
         if resign_on:   # the holdout's false positives: would-be resigners that went on not to lose
             fp = f"{rs['holdout_not_lost'] / rs['holdout_would_resign']:.3f}" if rs["holdout_would_resign"] else "n/a"
             log(f"Resignation: {rs['resigned']} resigned, {rs['holdout_games']} held out, {rs['holdout_would_resign']} of them would have resigned, "
@@ -431,9 +436,11 @@ def main():
     check("forced_k")
     if a.prune_target not in (0, 1) or (a.prune_target == 1 and not a.forced_k > 0.0):
         ap.error(f"--prune-target: {a.prune_target} is neither 0 nor 1, or is 1 without --forced-k above 0")
-    check("psw_share", "psw_max", "psw_seed", "q_share", "gumbel_m", "gumbel_cvisit", "gumbel_cscale", "gumbel_seed")
+    check("psw_share", "psw_max", "psw_seed", "q_share", "gumbel_m", "gumbel_cvisit", "gumbel_cscale", "gumbel_seed", "gumbel_tree")
     if a.gumbel_m > 0 and (a.dir_alpha > 0 or (a.cap_prob < 1 and a.cap_fast > 0) or a.forced_k > 0):
         ap.error("--gumbel-m: the Gumbel root search does not go with --dir-alpha, --cap-prob / --cap-fast or --forced-k")
+    if a.gumbel_tree == 1 and a.gumbel_m == 0:
+        ap.error("--gumbel-tree: the selection below the root needs the Gumbel root search (--gumbel-m above 0)")
     check("resign_streak", "resign_q", "resign_holdout", "resign_seed")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():

@@ -185,6 +185,14 @@ int azr_mcts_leaves(azr_engine* h, void* in88_host, uint8_t* need_eval_host, int
 int azr_mcts_apply(azr_engine* h, const float* pi_host, const float* v_host);
 /* root statistics of the last search: N[G][43]; Q,P optional */
 int azr_mcts_root_stats(azr_engine* h, uint32_t* n_host, float* q_host, float* p_host);
+/* The rows of any node of a game's tree: state g of data160_host [G][160] is imported as azr_engine_set_states imports it, into
+ * registers only, and looked up in game g's tree.  n_host = the completed visits, act_host (optional) = the visits in flight, q_host,
+ * p_host [G][43]; vhat_host [G] (optional) = the net's value kept by a Gumbel search (0 in a node any other search expanded);
+ * found_host [G] = 1 where the state is in the tree, else 0 with zero rows.  Read-only: the games' states, the search's bookkeeping and
+ * the nodes stay as they are, so it is valid between azr_mcts_leaves and azr_mcts_apply too.  For a game's own current state it returns
+ * azr_mcts_root_stats' numbers. */
+int azr_mcts_node_stats(azr_engine* h, const void* data160_host, uint32_t* n_host, uint32_t* act_host /*optional*/, float* q_host,
+                        float* p_host, float* vhat_host /*optional*/, uint8_t* found_host);
 /* StateSimulations::calculateMoveProbability(1.0f) (alphazero_mcts.cpp:121-149) */
 int azr_mcts_policy(azr_engine* h, float* pi_host);
 /* pickHigestWeightedMove / pickRandomWeightedMove (alphazero_mcts.cpp:379-412) on the last search's policy;
@@ -462,8 +470,8 @@ int azr_debug_resign(azr_engine* h, float q_resign, int streak, float holdout_sh
  * that target is a coarse copy of the prior, and nothing makes it an improvement on the prior.  Gumbel AlphaZero (Danihelka, Guez,
  * Schrittwieser, Silver, "Policy improvement by planning with Gumbel", ICLR 2022) samples the root's candidate moves without
  * replacement through Gumbel noise, spends the budget on them by sequential halving, plays the winner and records
- * softmax(logit + sigma(completed Q)).  Here it replaces the selection at path depth 0 and the decision; deeper levels keep PUCT (the
- * paper's deterministic non-root selection is not built), and the arena (azr_arena_*) never sees it.
+ * softmax(logit + sigma(completed Q)).  Here it replaces the selection at path depth 0 and the decision; deeper levels keep PUCT
+ * unless "selection below the root" (further down) is switched on, and the arena (azr_arena_*) never sees it.
  * All arithmetic below is fp32, each operation rounded on its own (no fused multiply-add), in the order written; lane i <-> move i.
  *
  * Per root.  P = the node's stored prior row (azr_mcts_root_stats);  logit[a] = ln32(max(P[a], 1.17549435e-38f)) with the ln32 of
@@ -525,16 +533,39 @@ int azr_debug_resign(azr_engine* h, float q_resign, int streak, float holdout_sh
  * Staging, z back-fill, game turnover, quota, surprise weighting (on this pi), the value mix and resignation (on the node's N and Q)
  * work as without the feature.
  *
+ * Selection below the root (the paper's deterministic non-root selection, its "Full Gumbel" search; off by default).  On, it takes the
+ * PUCT selection's place at every node met at path depth >= 1 of a descent — the root's own state included, when a transposition
+ * reaches it from below; path depth 0 keeps the root-level selection above.  The node spends its visits in proportion to its own
+ * improved policy.  N, act, Q, P, vhat, valid = this node's rows:
+ *     pi'[a]   = the record's pi above, computed on this node's rows (logit, the completed Q with the node's own vhat, sigma with the
+ *                node's largest N, exp32, the 43-term sums in index order); 0 on an illegal move
+ *     cnt[a]   = N[a] + act[a];   tot = the integer sum of cnt over the legal moves
+ *     den      = 1.0f + (float)tot
+ *     score[a] = pi'[a] - (float)cnt[a] / den                                    (a divide, then a subtract)
+ *     the move = the legal move with the largest score, the lowest index on ties
+ * with the bookkeeping of the PUCT selection (the in-flight count of the move goes up, the node counts as visited).  No N0 is
+ * involved: below the root the node's all-time counts are the paper's N.  Nothing is drawn, no rFloat is taken, and c_visit and
+ * c_scale are the root's.  Applied n times from empty counts under a fixed pi', the rule keeps |N[a] - n pi'[a]| below 1
+ * (tests/test_gumbel_tree_ref.py).
+ *
  * Device self-play: m = 0 = off (default); read by azr_selfplay_start*, a running self-play never sees a change.
  * AZR_E_INVALID_ARGUMENT, with a reason in azr_last_error, for m outside [0, 43], a c_visit or c_scale that is not finite, or — when
  * on — c_visit < 0 or c_scale <= 0.  azr_selfplay_start* returns AZR_E_INVALID_ARGUMENT, with a reason, when the Gumbel search is set
  * together with Dirichlet noise, a playout cap or forced playouts; the handle stays as it was. */
 int azr_selfplay_set_gumbel(azr_engine* h, int m, float c_visit, float c_scale, uint32_t seed);
+/* the selection below the root of a device self-play: on = 0 (default) = PUCT, 1 = the rule above.  Read by azr_selfplay_start*, a
+ * running self-play never sees a change.  AZR_E_INVALID_ARGUMENT for any other value; azr_selfplay_start* returns
+ * AZR_E_INVALID_ARGUMENT, with a reason, when it is 1 while azr_selfplay_set_gumbel's m is 0, and the handle stays as it was. */
+int azr_selfplay_set_gumbel_tree(azr_engine* h, int on);
 /* host-stepped searches (azr_mcts_simulate / azr_mcts_begin..apply): the same search under the vector of azr_mcts_set_root_gumbel.
  * Holds until set again; azr_selfplay_start* ends it.  Switching it on or off clears the trees, and so does the first azr_mcts_begin /
  * azr_mcts_simulate after an arena while it is on (the arena's searches expand nodes without a vhat).  Refused
  * (AZR_E_INVALID_ARGUMENT) while a root noise vector or forced playouts are in force, as those two setters are while it is. */
 int azr_mcts_set_gumbel(azr_engine* h, int m, float c_visit, float c_scale);
+/* ... and its selection below the root: on = 0 or 1.  Refused (AZR_E_INVALID_ARGUMENT) while no host-stepped Gumbel search is in force;
+ * azr_mcts_set_gumbel(h, 0, ...) puts it back to 0.  Toggling it does not clear the trees: every node a Gumbel search expanded has its
+ * vhat either way. */
+int azr_mcts_set_gumbel_tree(azr_engine* h, int on);
 /* g_host [G][43]: the vector of each game's root for the searches that follow, used as given; NULL = zeros */
 int azr_mcts_set_root_gumbel(azr_engine* h, const float* g_host);
 /* the vector in force at each game's current root, g_host [G][43] (a running self-play's draws, or what was set); zeros when no
@@ -553,6 +584,11 @@ int azr_debug_root_gumbel(azr_engine* h, uint32_t seed, const uint32_t* game_see
 int azr_debug_gumbel_select(azr_engine* h, int m, int n, float c_visit, float c_scale, const uint32_t* N, const uint32_t* N0,
                             const uint32_t* act, const float* Q, const float* P, const float* g, const float* vhat,
                             const uint64_t* valid, const uint32_t* claim, int rows, uint8_t* move_out, uint32_t* cv_out);
+/* the selection below the root alone, on the device, one wavefront per synthetic row: N, act, Q, P [rows][43], vhat, valid [rows] ->
+ * the move (43 = none) and score [rows][43], 0 on an illegal move.  c_visit >= 0, c_scale > 0. */
+int azr_debug_gumbel_tree_select(azr_engine* h, float c_visit, float c_scale, const uint32_t* N, const uint32_t* act, const float* Q,
+                                 const float* P /*[rows][43]*/, const float* vhat, const uint64_t* valid /*[rows]*/, int rows,
+                                 uint8_t* move_out /*[rows]*/, float* score_out /*[rows][43]*/);
 /* exp32 alone, on the device: out[i] = exp32(x[i]), i < n */
 int azr_debug_exp32(azr_engine* h, const float* x, int n, float* out);
 

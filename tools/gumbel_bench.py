@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """What the Gumbel root search costs and what it writes in device self-play (azr_selfplay_set_gumbel): the same quota of games with it
-off and on at --mcts 16 and 100 (T = 2, 20 blocks, bf16, random-init net), --repeat runs each, alternating off, on, off, on, ...;
+off, on, and on with the improved-policy selection below the root (azr_selfplay_set_gumbel_tree; the arm "on + tree") at --mcts 16 and
+100 (T = 2, 20 blocks, bf16, random-init net), --repeat runs each, alternating off, on, on + tree, off, ...;
 games/s and simulations/s (wall clock around the whole quota run, ring drained after every run), the tree step's average launch
 (azr_profile_last_run, averaged over the quota's runs) and the mean entropy of the recorded pi in nats.  The lines are also written to
 --out.
 
-A RANDOM-INIT NET'S NUMBERS DESCRIBE THE MACHINERY: what the root-level selection and the decision cost per tree step, and how flat the
-recorded target is.  Whether the target trains a stronger net is not measured here.  There is no threshold.
+A RANDOM-INIT NET'S NUMBERS DESCRIBE THE MACHINERY: what the root-level selection, the selection below the root and the decision cost
+per tree step, and how flat the recorded target is.  Whether the target trains a stronger net is not measured here.  There is no threshold.
     python tools/gumbel_bench.py [--slots 512] [--games 512] [-t 2] [--blocks 20] [--budgets 16,100] [--gumbel-m 16] [--gumbel-cvisit 50]
                                  [--gumbel-cscale 0.5] [--gumbel-seed 7] [--repeat 3] [--out profiles/gumbel_bench.txt]"""
 import argparse
@@ -43,10 +44,11 @@ def main():
         eng.init_random(5)
         passes = 4 * (mcts + 2)
         warm_up(eng, a.slots)
-        rows = {"off": [], "on": []}
+        rows = {"off": [], "on": [], "on + tree": []}
         for rep in range(a.repeat):
-            for name, m in (("off", 0), ("on", a.gumbel_m)):
+            for name, m, tree in (("off", 0, 0), ("on", a.gumbel_m, 0), ("on + tree", a.gumbel_m, 1)):
                 eng.selfplay_set_gumbel(m, a.gumbel_cvisit, a.gumbel_cscale, a.gumbel_seed)
+                eng.selfplay_set_gumbel_tree(tree)
                 dt, c, out = run_quota(eng, a.games, passes, entropy_sum)
                 n = max(1, sum(o[1] for o in out))
                 rows[name].append(dict(mcts=mcts, gumbel=name, m=m, run=rep, games=c["games_finished"], decisions=c["decisions"], records=c["samples"],
@@ -57,7 +59,8 @@ def main():
                 print(lines[-1], flush=True)
         eng.close()
         med = {k: {f: float(np.median([r[f] for r in v])) for f in ("games_per_s", "simulations_per_s", "tree_step_ms", "mean_pi_entropy")} for k, v in rows.items()}
-        lines.append(json.dumps(dict(mcts=mcts, medians=med, on_over_off={f: round(med["on"][f] / med["off"][f], 3) for f in med["on"]})))
+        lines.append(json.dumps(dict(mcts=mcts, medians=med, on_over_off={f: round(med["on"][f] / med["off"][f], 3) for f in med["on"]},
+                                     tree_over_on={f: round(med["on + tree"][f] / med["on"][f], 3) for f in med["on"]})))
         print(lines[-1], flush=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
