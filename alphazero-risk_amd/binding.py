@@ -89,7 +89,7 @@ EXPORTS = [
     "azr_mcts_apply", "azr_mcts_root_stats", "azr_mcts_policy", "azr_mcts_pick", "azr_selfplay_start", "azr_selfplay_start_games", "azr_selfplay_start_from_states",
     "azr_selfplay_run", "azr_selfplay_counters", "azr_samples_drain", "azr_samples_device_view", "azr_samples_copy_device", "azr_profile_last_run",
     "azr_device_synchronize", "azr_debug_tower_clock", "azr_debug_tower_trace", "azr_debug_tower_plan", "azr_arena_start", "azr_arena_run", "azr_arena_results", "azr_arena_log",
-    "azr_arena_set_opponent_net", "azr_arena_set_opponent_search", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
+    "azr_arena_set_opponent_net", "azr_arena_set_opponent_search", "azr_arena_set_gumbel", "azr_arena_collect_samples", "azr_arena_collect_scripted_samples",
     "azr_mcts_set_root_noise", "azr_selfplay_set_dirichlet", "azr_mcts_root_noise", "azr_debug_root_noise",
     "azr_selfplay_set_playout_cap", "azr_selfplay_decision_kind", "azr_debug_playout_cap",
     "azr_mcts_set_forced_playouts", "azr_mcts_pruned_policy", "azr_selfplay_set_forced_playouts", "azr_mcts_set_simulations",
@@ -162,6 +162,7 @@ def load_library(test_hooks=False):
         L.azr_arena_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.azr_arena_set_opponent_net.argtypes = [C.c_void_p, C.c_void_p]
         L.azr_arena_set_opponent_search.argtypes = [C.c_void_p, C.c_int, C.c_float]
+        L.azr_arena_set_gumbel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]
         L.azr_arena_collect_samples.argtypes = [C.c_void_p, C.c_int]
         L.azr_arena_collect_scripted_samples.argtypes = [C.c_void_p, C.c_int]
         L.azr_arena_results.argtypes = [C.c_void_p, C.c_void_p]
@@ -795,6 +796,14 @@ class Engine:
         until it is set again or arena_set_opponent(None); refused while an arena runs, below `threads`, and above what the node pool
         holds (16 * (sims + 1) nodes: create the Engine with node_capacity for the larger of the two budgets)."""
         self._chk(self.L.azr_arena_set_opponent_search(self.h, -1 if sims is None else int(sims), -1.0 if hp is None else float(hp)))
+
+    def arena_set_gumbel(self, player, m, c_visit=50.0, c_scale=0.5, tree=0):
+        """the search of one AlphaZero player of this Engine's arenas (PLAYER_ALPHAZERO or PLAYER_ALPHAZERO_B): m > 0 = the Gumbel root
+        search with sequential halving over m moves, deterministic (g = 0), tree = 1 with the improved-policy selection below the root;
+        m = 0 = PUCT (the default).  With arena_collect_samples its records carry the improved policy.  Holds until it is set again
+        (player B's also until arena_set_opponent(None)); refused while an arena runs, and arena_start refuses a Gumbel side under
+        arena_collect_scripted_samples."""
+        self._chk(self.L.azr_arena_set_gumbel(self.h, int(player), int(m), float(c_visit), float(c_scale), int(tree)))
 
     def arena_collect_samples(self, on=True):
         self._chk(self.L.azr_arena_collect_samples(self.h, int(on)))

@@ -1,4 +1,4 @@
-// azr_arena.hpp — device code of the arena step (k_arena_step / k_arena_step_rec).  Included by azr_engine.hip only.
+// azr_arena.hpp — device code of the arena step (k_arena_step / k_arena_step_rec / k_arena_step_gumbel).  Included by azr_engine.hip only.
 #pragma once
 #include "azr_search.hpp"
 // (after azr_internal.hpp: StageRec uses its STAGE_BYTES)
@@ -51,8 +51,14 @@ __device__ __forceinline__ void arena_begin_game(const Tree& t, const Tree& t2, 
 }
 
 // SREC: ScriptPlayer / RandomPlayer record their moves (StageRec); without it they get NoRec and this is the arena as it was
-template <bool SREC>
-__device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
+// GUMBEL (without SREC): an AlphaZero side of this arena searches by the Gumbel root search with sequential halving
+// (azr_arena_set_gumbel, azr_gumbel.hpp; both sides' settings in `A`) under g = 0 — evaluation games draw nothing.  The side that searches is wave-uniform (w): its
+// descents take the SIDE round of azr_search.hpp, one loop for both sides, and its decision gumbel_move / gumbel_policy or, with m = 0,
+// root_policy / pick_highest as in a step without this.  Every expansion keeps the net's value in the node, in both trees, so that no
+// node without one is ever searched (arena_begin_game empties both at every deal).  N0 lives in the slot's root_n0 row: a slot runs
+// one search at a time, and claim 0 of every search rewrites it.
+template <bool SREC, bool GUMBEL = false>
+__device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch, const ArenaGumbel* A = nullptr)
 {
     const int g = blockIdx.x;
     if (E.lc_zero >= 0 && g == 0 && threadIdx.x < 2) E.leaf_count[E.lc_zero + threadIdx.x] = 0;   // the next pass's counts (the last readers are done)
@@ -78,8 +84,9 @@ __device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
         const uint32_t w = E.tctl2[(size_t)g * 4 + (lane_id() & 3u)];
         x2.search_id = rdl(w, 0); x2.nfree = rdl(w, 1); x2.hiwater = rdl(w, 2);
     }
-    if (c.search_tree) { swap_tree_ctl(c, x2); consume_pending(E, g, t2, c, k); swap_tree_ctl(c, x2); }
-    else consume_pending(E, g, t, c, k);
+    static_assert(!(SREC && GUMBEL), "scripted collection and a Gumbel side do not go together (azr_arena_start refuses the pair)");
+    if (c.search_tree) { swap_tree_ctl(c, x2); consume_pending<GUMBEL>(E, g, t2, c, k); swap_tree_ctl(c, x2); }
+    else consume_pending<GUMBEL>(E, g, t, c, k);
     for (;;) {
         if (c.arena_state == 0 && E.arena_mirror == AZR_MIRROR_CONCURRENT) {
             // Both games of a mirrored pair at the same time: slot 2j plays half 0 of slot pair j's k-th pair, slot 2j + 1 the
@@ -195,16 +202,27 @@ __device__ __forceinline__ void arena_step(const Dev& E, int8_t* scratch)
             // without root noise, whatever azr_mcts_set_root_noise / azr_selfplay_set_dirichlet say
             Search Sw = E.search;
             if (w) { Sw.simulations = E.search2_simulations; Sw.hp = E.search2_hp; }
-            int r = search_round<false>(E, Sw, g, tt, c, root, scratch, k, err, 0.0f);
+            const GumbelSide side = GUMBEL ? (w ? A->side[1] : A->side[0]) : GumbelSide{};
+            int r = GUMBEL ? search_round<false, false, false, false, true>(E, Sw, g, tt, c, root, scratch, k, err, 0.0f, 0.0f, &side)
+                           : search_round<false>(E, Sw, g, tt, c, root, scratch, k, err, 0.0f);
             root.rng = c.rng;
             if (r == RD_LEAF) { if (w) swap_tree_ctl(c, x2); break; }
             if (r == RD_FAIL) { fail = true; root.err = err; }
             else {
                 uint32_t N; uint64_t valid;
                 uint32_t mv = NONE;
-                if (root_node(tt, root, N, valid) != NO_NODE) {
-                    const float pi = root_policy(N, valid);
-                    mv = pick_highest(pi);
+                float Q = 0.0f, P = 0.0f;   // GUMBEL: the root's mean values and stored prior row
+                const uint32_t ridx = root_node(tt, root, N, valid, GUMBEL ? &Q : nullptr, GUMBEL ? &P : nullptr);
+                if (ridx != NO_NODE) {
+                    float pi;
+                    if (GUMBEL && side.m > 0) {   // one score serves the move and the record, as in a self-play GUMBEL step
+                        const GumbelScore sc = gumbel_score(N, Q, P, node_vhat(tt, ridx), valid, side.c_visit, side.c_scale);
+                        mv = gumbel_move(sc, N, E.root_n0[(size_t)g * MOVES + (lane_id() < MOVES ? lane_id() : 0)], 0.0f, valid);
+                        pi = gumbel_policy(sc, valid);
+                    } else {
+                        pi = root_policy(N, valid);
+                        mv = pick_highest(pi);
+                    }
                     if (E.arena_collect) stage_sample(E, g, c, root, pi, k);  // AlphaZeroPlayer::takeTurn with trainStorage set (alphazero_player.cpp:15-18)
                 }
                 if (mv != NONE) make_move(root, mv, R); else root.err = E_LOGIC;

@@ -342,6 +342,12 @@ __global__ __launch_bounds__(64) void k_arena_step_rec(Dev E)
     __shared__ int8_t scratch[128];
     arena_step<true>(E, scratch);
 }
+// an AlphaZero side of the arena searches by the Gumbel root search (azr_arena_set_gumbel)
+__global__ __launch_bounds__(64) void k_arena_step_gumbel(Dev E, ArenaGumbel A)
+{
+    __shared__ int8_t scratch[128];
+    arena_step<false, true>(E, scratch, &A);
+}
 
 __global__ __launch_bounds__(64) void k_arena_start(Dev E)
 {
@@ -958,8 +964,13 @@ struct DevBuf {
         hipLaunchKernelGGL(kern, dim3((h)->d.G), dim3(64), 0, (h)->stream, __VA_ARGS__); \
         HIPCHK(h, hipGetLastError());                                                 \
     } while (0)
-// the arena step of this handle: with the scripted players' recorder (azr_arena_collect_scripted_samples) or without
-#define ARENA_STEP(h, dev) LAUNCH(h, (h)->arena_rec ? k_arena_step_rec : k_arena_step, dev)
+// the arena step of this handle: with a Gumbel side (azr_arena_set_gumbel), with the scripted players' recorder
+// (azr_arena_collect_scripted_samples) or without either; azr_arena_start refuses the first two together
+#define ARENA_STEP(h, dev)                                                                  \
+    do {                                                                                    \
+        if ((h)->arena_gumbel) LAUNCH(h, k_arena_step_gumbel, dev, (h)->arena_gumbel_run);  \
+        else LAUNCH(h, (h)->arena_rec ? k_arena_step_rec : k_arena_step, dev);              \
+    } while (0)
 // a boundary call that hands back one array: `kern(args..., buf)` fills a temporary device buffer of `bytes`, copied out to `dst`
 #define LAUNCH_OUT(h, dst, bytes, T, kern, ...)              \
     do {                                                     \
@@ -1386,7 +1397,17 @@ static void resolve_selfplay_options(azr_engine* h)
     d.eta_const = 0;
 }
 
-// the Gumbel search's two per-game rows, with the first search that needs them: an engine that never runs one allocates none
+// the Gumbel search's two per-game rows, with the first search that needs them: an engine that never runs one allocates none.  The N0
+// rows alone serve an arena with a Gumbel side, whose g is 0.
+static int gumbel_alloc_n0(azr_engine* h)
+{
+    const size_t n = (size_t)h->d.G * MOVES;
+    if (!h->d.root_n0) {
+        HIPCHK(h, dmalloc(&h->d.root_n0, n));
+        HIPCHK(h, hipMemsetAsync(h->d.root_n0, 0, n * sizeof(uint32_t), h->stream));
+    }
+    return AZR_OK;
+}
 static int gumbel_alloc(azr_engine* h)
 {
     const size_t n = (size_t)h->d.G * MOVES;
@@ -1394,11 +1415,7 @@ static int gumbel_alloc(azr_engine* h)
         HIPCHK(h, dmalloc(&h->d.root_g, n));
         HIPCHK(h, hipMemsetAsync(h->d.root_g, 0, n * sizeof(float), h->stream));
     }
-    if (!h->d.root_n0) {
-        HIPCHK(h, dmalloc(&h->d.root_n0, n));
-        HIPCHK(h, hipMemsetAsync(h->d.root_n0, 0, n * sizeof(uint32_t), h->stream));
-    }
-    return AZR_OK;
+    return gumbel_alloc_n0(h);
 }
 
 static int selfplay_start(azr_engine* h, uint32_t base_seed, unsigned long long quota, int keep = 0)
@@ -2172,8 +2189,16 @@ extern "C" int azr_arena_start(azr_engine* h, int player1, int player2, int game
         h->err = "azr_arena_start: AZR_PLAYER_ALPHAZERO_B needs azr_arena_set_opponent_net with a handle that has weights";
         return AZR_E_STATE;
     }
+    // a Gumbel side of this arena (a setting for a player that does not play leaves the arena what it is)
+    const bool gumbel = (usesA && h->arena_gumbel_set.side[0].m > 0) || (usesB && h->arena_gumbel_set.side[1].m > 0);
+    if (gumbel && h->arena_script)
+        return bad_argument(h, "azr_arena_start: a Gumbel search (azr_arena_set_gumbel) does not go with scripted-sample collection "
+                               "(azr_arena_collect_scripted_samples): switch one of them off");
+    if (gumbel) { if (int rc = gumbel_alloc_n0(h)) return rc; }   // (g = 0: no root_g)
     Dev& d = h->d;
-    // player B's search settings as they stand now: a running arena never sees a later change
+    // both sides' Gumbel settings and player B's search settings as they stand now: a running arena never sees a later change
+    h->arena_gumbel = gumbel;
+    h->arena_gumbel_run = h->arena_gumbel_set;
     d.search2_simulations = h->opp_simulations >= 0 ? h->opp_simulations : d.search.simulations;
     d.search2_hp = h->opp_hp >= 0 ? h->opp_hp : d.search.hp;
     d.nodes2 = usesB ? h->tree2[0] ? (uint8_t*)h->tree2[0] : nullptr : nullptr;
@@ -2298,6 +2323,7 @@ extern "C" int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other)
         h->opponent = nullptr;
         h->opp_simulations = -1;   // azr_arena_set_opponent_search's setting goes with the opponent (read by the next azr_arena_start)
         h->opp_hp = -1.0f;
+        h->arena_gumbel_set.side[1] = GumbelSide{};   // ... and so does azr_arena_set_gumbel's for player B
         return AZR_OK;
     }
     // Depth and element type are the opponent's own business: its launches run with its own weights, context and activation buffers on
@@ -2355,6 +2381,27 @@ extern "C" int azr_arena_set_opponent_search(azr_engine* h, int mcts_simulations
     }
     h->opp_simulations = sims;   // azr_arena_start hands them to the kernels
     h->opp_hp = hp_exploration < 0 ? -1.0f : hp_exploration;
+    return AZR_OK;
+}
+
+extern "C" int azr_arena_set_gumbel(azr_engine* h, int player, int m, float c_visit, float c_scale, int tree)
+{
+    ENTER(h);
+    if (h->mode == 3 && h->arena_open) {
+        h->err = "azr_arena_set_gumbel: an arena is running (set it before azr_arena_start or after the arena has finished)";
+        return AZR_E_STATE;
+    }
+    if (player != AZR_PLAYER_ALPHAZERO && player != AZR_PLAYER_ALPHAZERO_B)
+        return bad_argument(h, "azr_arena_set_gumbel: player = " + std::to_string(player) + " is neither AZR_PLAYER_ALPHAZERO nor AZR_PLAYER_ALPHAZERO_B");
+    if (int rc = gumbel_check(h, "azr_arena_set_gumbel", m, c_visit, c_scale)) return rc;
+    if (tree != 0 && tree != 1) return bad_argument(h, "azr_arena_set_gumbel: tree = " + std::to_string(tree) + " is not 0 or 1");
+    if (tree && m == 0)
+        return bad_argument(h, "azr_arena_set_gumbel: the Gumbel selection below the root (tree = 1) needs the Gumbel root search (m > 0)");
+    GumbelSide& a = h->arena_gumbel_set.side[player == AZR_PLAYER_ALPHAZERO_B ? 1 : 0];   // azr_arena_start hands them to the kernels
+    a.m = m;
+    a.c_visit = m > 0 ? c_visit : 0.0f;
+    a.c_scale = m > 0 ? c_scale : 0.0f;
+    a.tree = tree;
     return AZR_OK;
 }
 

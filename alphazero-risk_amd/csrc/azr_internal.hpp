@@ -157,6 +157,15 @@ struct Dev {
     float gumbel_cscale;
     uint32_t gumbel_seed;      // device self-play: g is keyed by (gumbel_seed, game seed, decision, move)
 };
+// The arena's Gumbel search (azr_arena_set_gumbel): one AlphaZero side's settings, and both sides' as k_arena_step_gumbel takes them —
+// a kernel argument of its own behind Dev, which therefore does not grow (a larger Dev would move the trailing arguments of every kernel
+// that has some).  side[0] = AZR_PLAYER_ALPHAZERO, side[1] = AZR_PLAYER_ALPHAZERO_B.  g = 0: nothing is drawn.
+struct GumbelSide {
+    int m = 0;                 // moves considered at a root (0 = off: this side searches by PUCT)
+    float c_visit = 0.0f, c_scale = 0.0f;
+    int tree = 0;              // 1 = gumbel_select_tree below the root, 0 = PUCT with the side's own hp
+};
+struct ArenaGumbel { GumbelSide side[2]; };
 constexpr int ALOG = 16;
 
 // The options of the search variants (host side).  Which of them a tree step carries: root noise, a playout cap (self-play only),
@@ -254,6 +263,9 @@ struct azr_engine {
     bool arena_open = false;      // between azr_arena_start and the azr_arena_run that found every slot idle
     int opp_simulations = -1;     // azr_arena_set_opponent_search: player B's count per decision and PUCT constant (< 0 = the handle's own);
     float opp_hp = -1.0f;         // copied into d.search2_* by azr_arena_start
+    azr::ArenaGumbel arena_gumbel_set;   // azr_arena_set_gumbel, as it stands ...
+    azr::ArenaGumbel arena_gumbel_run;   // ... and as azr_arena_start found it: a running arena never sees a change
+    bool arena_gumbel = false;    // a side of this arena has m > 0: its steps run k_arena_step_gumbel(d, arena_gumbel_run)
     azr::HostOpts host;           // the host-stepped options as they stand
     azr::SelfplayOpts sp_set;     // the self-play options as set ...
     azr::StepOpts sp;             // ... and what azr_selfplay_start* found in force: this self-play's steps carry it (the values are in d)

@@ -267,13 +267,18 @@ enum : int { RD_DONE = 0, RD_LEAF = 1, RD_FAIL = 2 };
 // FORCED: that selection forces playouts with the factor `fk` (0 = not in this search: a fast decision under a playout cap).
 // GUMBEL: that selection is gumbel_select_root's (azr_gumbel.hpp) for the claim index sims_started - 1; `eta` carries the root's g.
 // GTREE (with GUMBEL): every later selection of the descent is gumbel_select_tree's, under the root's c_visit and c_scale.
-template <bool NOISE, bool FORCED = false, bool GUMBEL = false, bool GTREE = false>
+// SIDE (the arena's Gumbel step; without the four above): one descent loop serves both players.  Which of the three selections runs is
+// the searching side's setting `sd` (wave-uniform; the steps without SIDE pass none): m > 0 is GUMBEL's, with g = 0 where `eta` goes, and
+// tree GTREE's; a side with m = 0 selects by tree_select under `S`, as in a step without any of this.
+template <bool NOISE, bool FORCED = false, bool GUMBEL = false, bool GTREE = false, bool SIDE = false>
 __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g, const Tree& t0, int th, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
+                                            StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f, const GumbelSide* sd = nullptr)
 {
     const Rules R = E.rules;
     const Tree t = thread_tree(t0, th);
     const size_t slot = (size_t)g * E.T + th;
+    static_assert(!SIDE || (!NOISE && !FORCED && !GUMBEL && !GTREE), "SIDE takes the search from the arena's per-side settings alone");
+    const GumbelSide side = SIDE ? *sd : GumbelSide{};
     while ((int)c.sims_started < S.simulations) {
         c.sims_started++;  // Counter::hasNext
         WS s = root;
@@ -313,7 +318,13 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
             }
             k.levels++;
             uint32_t mv;
-            if (GUMBEL && plen == 0)
+            if (SIDE && side.m > 0 && plen == 0)
+                mv = gumbel_select_root(t, idx, nr, c.search_id, E.root_n0 + (size_t)g * MOVES, c.sims_started - 1u, (uint32_t)side.m, (uint32_t)S.simulations,
+                                        side.c_visit, side.c_scale, eta);
+            else if (SIDE && side.tree)
+                mv = gumbel_select_tree(nr.W, nr.Q, nr.P, node_vhat(t, idx), (uint64_t)rfl(nr.valid_lo) | ((uint64_t)rfl(nr.valid_hi) << 32),
+                                        side.c_visit, side.c_scale, reinterpret_cast<uint32_t*>(node_ptr(t, idx) + ND_N), t.touch + idx, c.search_id);
+            else if (GUMBEL && plen == 0)
                 mv = gumbel_select_root(t, idx, nr, c.search_id, E.root_n0 + (size_t)g * MOVES, c.sims_started - 1u, (uint32_t)E.gumbel_m,
                                         (uint32_t)S.simulations, E.gumbel_cvisit, E.gumbel_cscale, eta);
             else if (GTREE)
@@ -350,13 +361,13 @@ __device__ __forceinline__ int run_descents(const Dev& E, const Search& S, int g
 // One round of AlphaZeroMCTS::simulate for all T search threads of the game, in thread order: every thread without a
 // pending leaf runs descents until it blocks on the net.  RD_LEAF = at least one leaf is waiting; RD_DONE = the counter
 // is exhausted and every claimed simulation is backed up.
-template <bool NOISE, bool FORCED = false, bool GUMBEL = false, bool GTREE = false>
+template <bool NOISE, bool FORCED = false, bool GUMBEL = false, bool GTREE = false, bool SIDE = false>
 __device__ __forceinline__ int search_round(const Dev& E, const Search& S, int g, const Tree& t, Ctl& c, const WS& root, int8_t* scratch,
-                                            StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f)
+                                            StepCount& k, uint32_t& err_out, float eta, float fk = 0.0f, const GumbelSide* sd = nullptr)
 {
     for (int th = 0; th < E.T; th++) {
         if ((c.pending >> th) & 1u) continue;
-        int r = run_descents<NOISE, FORCED, GUMBEL, GTREE>(E, S, g, t, th, c, root, scratch, k, err_out, eta, fk);
+        int r = run_descents<NOISE, FORCED, GUMBEL, GTREE, SIDE>(E, S, g, t, th, c, root, scratch, k, err_out, eta, fk, sd);
         if (r == RD_FAIL) { c.pending = 0; return RD_FAIL; }
         if (r == RD_LEAF && plen_get(c, th) == 0) break;  // root expansion: the threads start after setRootState
     }

@@ -146,6 +146,10 @@ void Settings::init(int argc, char* argv[])
         real("gumbel-cscale", "[this build] c_scale of sigma under --gumbel-m, for values in [-1, 1]: half the paper's, whose values lie in [0, 1] (above 0)", "0.5", &Settings::GUMBEL_CSCALE, 0, 1e30, "is not a c_scale (a finite number above 0)", true),
         seed("gumbel-seed", "[this build] seed of the Gumbel vectors (independent of --seed: the games' dice and deals do not move)", std::to_string(GUMBEL_SEED), &Settings::GUMBEL_SEED, SEED),
         onoff("gumbel-tree", "[this build] under --gumbel-m, the selection below the root: 1 = every interior node spends its visits in proportion to softmax(logit + sigma(completed Q)) of its own rows, the paper's full search (0 = PUCT there)", "0", &Settings::GUMBEL_TREE),
+        whole("arena-gumbel-m", "[this build] arena games (compare and benchmark games of -m learn, -m play): Gumbel search with sequential halving of player 1 — the new net of the compare games, the AlphaZero side against Script and Random — over this many root moves, deterministic (no Gumbel noise), c_visit and c_scale of --gumbel-cvisit / --gumbel-cscale (0 = off: PUCT; at most 43)", "0", &Settings::ARENA_GUMBEL_M, 0, 43, "is not a number of root moves (a whole number in [0, 43]; 0 = off)"),
+        whole("arena-gumbel-m2", "[this build] the same for player 2, the old net of the compare games and player 2 of -m play --p1 az --p2 az (not given: the value of --arena-gumbel-m)", "0", &Settings::ARENA_GUMBEL_M2, 0, 43, "is not a number of root moves (a whole number in [0, 43]; 0 = off)"),
+        onoff("arena-gumbel-tree", "[this build] under --arena-gumbel-m, player 1's selection below the root: 1 = by the improved policy of each node (0 = PUCT there)", "0", &Settings::ARENA_GUMBEL_TREE),
+        onoff("arena-gumbel-tree2", "[this build] under --arena-gumbel-m2, the same for player 2 (not given: the value of --arena-gumbel-tree)", "0", &Settings::ARENA_GUMBEL_TREE2),
         {"cvk", "[this build] folds of -m analysis (the reference hard-codes 10)", std::to_string(CV_K), false},
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
@@ -313,6 +317,18 @@ void Settings::init(int argc, char* argv[])
     fill_through("gumbel-tree");   // (--gumbel-m with --dir-alpha is not refused here: azr_selfplay_start refuses it)
     if (GUMBEL_TREE == 1 && GUMBEL_M == 0) {
         fprintf(stderr, "--gumbel-tree: 1 needs --gumbel-m above 0 (the selection below the root belongs to the Gumbel root search)\n");
+        exit(2);
+    }
+    fill_through("arena-gumbel-tree2");
+    // player 2's search: player 1's unless given (the settings file then carries the value in force, as for --mcts2)
+    if (!given.count("arena-gumbel-m2")) { ARENA_GUMBEL_M2 = ARENA_GUMBEL_M; val["arena-gumbel-m2"] = get("arena-gumbel-m"); }
+    if (!given.count("arena-gumbel-tree2")) { ARENA_GUMBEL_TREE2 = ARENA_GUMBEL_TREE; val["arena-gumbel-tree2"] = get("arena-gumbel-tree"); }
+    if (ARENA_GUMBEL_TREE == 1 && ARENA_GUMBEL_M == 0) {
+        fprintf(stderr, "--arena-gumbel-tree: 1 needs --arena-gumbel-m above 0 (the selection below the root belongs to the Gumbel root search)\n");
+        exit(2);
+    }
+    if (ARENA_GUMBEL_TREE2 == 1 && ARENA_GUMBEL_M2 == 0) {
+        fprintf(stderr, "--arena-gumbel-tree2: 1 needs --arena-gumbel-m2 above 0 (the selection below the root belongs to the Gumbel root search)\n");
         exit(2);
     }
     fill_through("");
@@ -882,6 +898,22 @@ std::ostream& operator<<(std::ostream& os, const GameResults& gr)  // game.cpp:2
 // moves the base seed (a compare / benchmark round must not replay the previous iteration's deals)
 static std::atomic<uint32_t> arenaCallCounter{0};
 
+// the first arena of the run with a Gumbel side says so once
+static std::atomic<bool> arenaSearchLogged{false};
+
+void GameGroup::applyArenaSearch(Engine& e, bool two, bool scripted)
+{
+    const Settings& s = SETTINGS;
+    const int m1 = scripted ? 0 : s.ARENA_GUMBEL_M, m2 = two ? s.ARENA_GUMBEL_M2 : 0;
+    e.check(azr_arena_set_gumbel(e.h, AZR_PLAYER_ALPHAZERO, m1, s.GUMBEL_CVISIT, s.GUMBEL_CSCALE, m1 ? s.ARENA_GUMBEL_TREE : 0), "arena_set_gumbel");
+    if (two) e.check(azr_arena_set_gumbel(e.h, AZR_PLAYER_ALPHAZERO_B, m2, s.GUMBEL_CVISIT, s.GUMBEL_CSCALE, m2 ? s.ARENA_GUMBEL_TREE2 : 0), "arena_set_gumbel");
+    if ((m1 > 0 || m2 > 0) && !arenaSearchLogged.exchange(true)) {
+        auto side = [](int m, int tree) { return m > 0 ? "Gumbel m " + std::to_string(m) + (tree ? " (tree)" : "") : std::string("PUCT"); };
+        if (two) printf("Arena search: player 1 %s, player 2 %s\n", side(m1, s.ARENA_GUMBEL_TREE).c_str(), side(m2, s.ARENA_GUMBEL_TREE2).c_str());
+        else printf("Arena search: player 1 %s\n", side(m1, s.ARENA_GUMBEL_TREE).c_str());
+    }
+}
+
 GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup& pg2, int games, NNTrainDataStorage* tds, int mcts2, float hp2)
 {
     const uint32_t arenaCallsBase = ++arenaCallCounter;
@@ -902,6 +934,7 @@ GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup
         if (share == 0) return;
         e.check(azr_arena_set_opponent_net(e.h, o.h), "arena_set_opponent_net");
         if (mcts2 >= 0 || hp2 >= 0) e.check(azr_arena_set_opponent_search(e.h, mcts2, hp2), "arena_set_opponent_search");
+        applyArenaSearch(e, true);
         e.check(azr_arena_collect_samples(e.h, tds ? 1 : 0), "arena_collect_samples");
         const int passes = 4 * (std::max(SETTINGS.MCTS_SIMULATIONS, mcts2) + 2);   // the larger of the two budgets
         e.check(azr_arena_start(e.h, AZR_PLAYER_ALPHAZERO, AZR_PLAYER_ALPHAZERO_B, share, 0, mirror,
@@ -970,6 +1003,7 @@ GameResults GameGroup::playGames(AlphaZeroPlayerGroup& pg1, int otherKind, int g
         const int mirror = tds ? scriptedMirrorMode(e) : SETTINGS.arenaMirrorMode();
         e.check(azr_arena_collect_samples(e.h, tds ? 1 : 0), "arena_collect_samples");
         e.check(azr_arena_collect_scripted_samples(e.h, tds ? 1 : 0), "arena_collect_scripted_samples");
+        applyArenaSearch(e, false, tds != nullptr);
         e.check(azr_arena_start(e.h, AZR_PLAYER_ALPHAZERO, otherKind, share, 0, mirror,
                                 SETTINGS.BASE_SEED + 104729u * arenaCallsBase + (uint32_t)i * (1u << 24)), "arena_start");
         int fin = 0;

@@ -94,6 +94,10 @@ public:
     float GUMBEL_CSCALE = 0.5f;
     uint32_t GUMBEL_SEED = 0;            // --gumbel-seed: ... and the seed of the Gumbel vectors (self-play generation of -m train only, like --dir-alpha; not with --dir-alpha, --cap-prob or --forced-k)
     int GUMBEL_TREE = 0;                 // --gumbel-tree: ... and its selection below the root, by the improved policy of each node (0 = PUCT there)
+    int ARENA_GUMBEL_M = 0;              // --arena-gumbel-m: Gumbel search of player 1 in the arena games (the new net of the compare games, the AlphaZero side of the benchmark games and of -m play), deterministic; 0 = PUCT ...
+    int ARENA_GUMBEL_M2 = 0;             // --arena-gumbel-m2: ... of player 2 (the old net; default: --arena-gumbel-m) ...
+    int ARENA_GUMBEL_TREE = 0;           // --arena-gumbel-tree, --arena-gumbel-tree2: ... and each side's selection below the root (c_visit, c_scale: --gumbel-cvisit, --gumbel-cscale)
+    int ARENA_GUMBEL_TREE2 = 0;
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
 
@@ -273,6 +277,10 @@ std::ostream& operator<<(std::ostream& os, const GameResults& gr);
 // (alphazero_player.cpp:15-18,24-29), game by game.
 class GameGroup {
 public:
+    // --arena-gumbel-m / -m2 / -tree / -tree2 on engine e before its azr_arena_start: player 1 is AZR_PLAYER_ALPHAZERO, player 2 (`two`: the
+    // arena has one) AZR_PLAYER_ALPHAZERO_B.  `scripted`: the arena collects the scripted players' moves, which goes with PUCT only.
+    // The first call of a run that sets a Gumbel side prints the log line.
+    static void applyArenaSearch(Engine& e, bool two, bool scripted = false);
     // mcts2 / hp2: player group 2's own simulations per decision and PUCT constant (azr_arena_set_opponent_search; < 0 = group 1's)
     static GameResults playGames(AlphaZeroPlayerGroup& pg1, AlphaZeroPlayerGroup& pg2, int games, NNTrainDataStorage* tds = nullptr,
                                  int mcts2 = -1, float hp2 = -1.0f);

@@ -66,6 +66,7 @@ static void executePlay()
         memset(&res[i], 0, sizeof res[i]);
         const int share = 2 * (pairs / P + (i < pairs % P ? 1 : 0));
         if (share == 0) return;
+        GameGroup::applyArenaSearch(e, false);   // --arena-gumbel-m: the AlphaZero side, whichever seat it has
         e.check(azr_arena_start(e.h, k1, k2, share, 0, SETTINGS.arenaMirrorMode(), SETTINGS.BASE_SEED + (uint32_t)i * (1u << 24)),
                 "arena_start");
         int fin = 0;

@@ -94,11 +94,28 @@ SELFPLAY_OPTIONS = (
 SELFPLAY_FLAGS = {f.name[2:].replace("-", "_"): f for _, flags in SELFPLAY_OPTIONS for f in flags}   # by argparse's attribute name
 
 
-def arena_device(eng_new, eng_old, games, mirror=P.MIRROR_CONCURRENT, base_seed=1, collect=False):
+# The search of the arena games (compare and benchmark games; the generated games have SELFPLAY_OPTIONS): a Gumbel search with sequential
+# halving per side, deterministic.  m1 / tree1: player 1, the new net of the compare games and the AlphaZero side of the benchmark games;
+# m2 / tree2: player 2, the old net.  0 = PUCT, the arena as it always was.
+ArenaSearch = collections.namedtuple("ArenaSearch", "m1 tree1 m2 tree2 c_visit c_scale", defaults=(0, 0, 0, 0, 50.0, 0.5))
+
+
+def arena_search_line(s, two=True):
+    """the log line of an arena with a Gumbel side, None without one"""
+    side = lambda m, tree: f"Gumbel m {m}" + (" (tree)" if tree else "") if m > 0 else "PUCT"   # noqa: E731
+    if s is None or not (s.m1 > 0 or (two and s.m2 > 0)):
+        return None
+    return f"Arena search: player 1 {side(s.m1, s.tree1)}" + (f", player 2 {side(s.m2, s.tree2)}" if two else "")
+
+
+def arena_device(eng_new, eng_old, games, mirror=P.MIRROR_CONCURRENT, base_seed=1, collect=False, search=None):
     """the same arena resident on the device (azr_arena_* with AZR_PLAYER_ALPHAZERO_B = eng_old's network): every slot
     advances on its own, each network is evaluated on its own player's leaves; optionally returns the (s, pi, z)
-    records both players produced (INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES)"""
+    records both players produced (INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES).  search: an ArenaSearch (None: both sides as they stand)"""
     eng_new.arena_set_opponent(eng_old)
+    if search is not None:
+        eng_new.arena_set_gumbel(P.PLAYER_ALPHAZERO, search.m1, search.c_visit, search.c_scale, search.tree1 if search.m1 else 0)
+        eng_new.arena_set_gumbel(P.PLAYER_ALPHAZERO_B, search.m2, search.c_visit, search.c_scale, search.tree2 if search.m2 else 0)
     eng_new.arena_collect_samples(collect)
     eng_new.arena_start(P.PLAYER_ALPHAZERO, P.PLAYER_ALPHAZERO_B, games, 0, mirror, base_seed)
     while not eng_new.arena_run(4 * (eng_new.settings.mcts_simulations + 2)):
@@ -179,8 +196,11 @@ def load_training_samples(path):
     raise ValueError(f"unrecognised sample file {path}: {len(raw)} bytes")
 
 
-def run_arena(eng, p1, p2, games, mirror, seed):
-    """GameGroup::playGames of an AlphaZero player group against ScriptPlayer / RandomPlayer (the benchmark games)"""
+def run_arena(eng, p1, p2, games, mirror, seed, search=None):
+    """GameGroup::playGames of an AlphaZero player group against ScriptPlayer / RandomPlayer (the benchmark games).  search: an
+    ArenaSearch whose player 1 is the AlphaZero side (None: as it stands)"""
+    if search is not None:
+        eng.arena_set_gumbel(P.PLAYER_ALPHAZERO, search.m1, search.c_visit, search.c_scale, search.tree1 if search.m1 else 0)
     eng.arena_start(p1, p2, games, 0, mirror, seed)
     while not eng.arena_run(4 * (eng.settings.mcts_simulations + 2)):
         pass
@@ -230,6 +250,11 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
     dtype = {"bf16": P.NET_BF16, "f16": P.NET_F16, "f32x": P.NET_F32X, "f32": P.NET_F32}[a.dtype]
     t = getattr(a, "t", 2)
     opt = {f.name: getattr(a, dest, f.default) for dest, f in SELFPLAY_FLAGS.items()}   # (a caller's namespace may lack them: the defaults)
+    m1, tree1 = getattr(a, "arena_gumbel_m", 0), getattr(a, "arena_gumbel_tree", 0)
+    m2, tree2 = getattr(a, "arena_gumbel_m2", None), getattr(a, "arena_gumbel_tree2", None)
+    search = ArenaSearch(m1, tree1, m1 if m2 is None else m2, tree1 if tree2 is None else tree2, opt["--gumbel-cvisit"], opt["--gumbel-cscale"])
+    if arena_search_line(search):
+        log(arena_search_line(search))
     # MIRROR_GAMES (settings.h:52): mirrored pairs; --pair-halves 1 plays a pair's two games at the same time on two slots
     mirror = P.MIRROR_CONCURRENT if getattr(a, "pair_halves", 1) and a.gpu_games >= 2 else P.MIRROR_SEQUENTIAL
     if rank != 0:
@@ -354,7 +379,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         if a.cg > 0:
             share = 2 * shard_mod.split_count(a.cg // 2, world, rank)
             aseed = shard_mod.rank_base_seed(a.seed + 7919 * (it + 1), rank)
-            gr, arecs = arena_device(new, gen, share, mirror, aseed, collect=bool(getattr(a, "include_compare_samples", 1)))
+            gr, arecs = arena_device(new, gen, share, mirror, aseed, collect=bool(getattr(a, "include_compare_samples", 1)), search=search)
             if dist is not None:
                 gr = reduce_results(gr, dist, cdev)
                 import torch
@@ -372,9 +397,9 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
             gen.set_weights(new.get_weights())   # generateGroup->loadCheckpoint(best): every rank already holds them
             t_bench = time.time()
             r = run_arena(gen, P.PLAYER_ALPHAZERO, P.PLAYER_RANDOM, 2 * shard_mod.split_count(5, world, rank), mirror,
-                          shard_mod.rank_base_seed(a.seed + 11 + 104729 * (it + 1), rank))
+                          shard_mod.rank_base_seed(a.seed + 11 + 104729 * (it + 1), rank), search=search)
             s = run_arena(gen, P.PLAYER_ALPHAZERO, P.PLAYER_SCRIPT, 2 * shard_mod.split_count(50, world, rank), mirror,
-                          shard_mod.rank_base_seed(a.seed + 13 + 15485863 * (it + 1), rank))
+                          shard_mod.rank_base_seed(a.seed + 13 + 15485863 * (it + 1), rank), search=search)
             if dist is not None:
                 r, s = reduce_results(r, dist, cdev), reduce_results(s, dist, cdev)
             bench_log.write(benchmark_line(it, r, s)); bench_log.flush()
@@ -412,6 +437,15 @@ def main():
     ap.add_argument("--include-compare-samples", type=int, default=1)   # INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES
     for f in SELFPLAY_FLAGS.values():
         ap.add_argument(f.name, type=f.type, default=f.default, help=f.help)
+    # the arena games' search (separate from the table above, which is the generated games'): player 2's default is player 1's value
+    ap.add_argument("--arena-gumbel-m", type=int, default=0,
+                    help="[this build] compare and benchmark games: Gumbel search with sequential halving of player 1 (the new net; the AlphaZero side "
+                         "against Script and Random) over this many root moves, deterministic, c_visit and c_scale of --gumbel-cvisit / --gumbel-cscale "
+                         "(0 = off: PUCT; at most 43)")
+    ap.add_argument("--arena-gumbel-m2", type=int, default=None, help="[this build] the same for player 2, the old net (default: --arena-gumbel-m)")
+    ap.add_argument("--arena-gumbel-tree", type=int, default=0,
+                    help="[this build] under --arena-gumbel-m, player 1's selection below the root: 1 = by the improved policy of each node (0 = PUCT there)")
+    ap.add_argument("--arena-gumbel-tree2", type=int, default=None, help="[this build] the same for player 2 (default: --arena-gumbel-tree)")
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -442,6 +476,17 @@ def main():
     if a.gumbel_tree == 1 and a.gumbel_m == 0:
         ap.error("--gumbel-tree: the selection below the root needs the Gumbel root search (--gumbel-m above 0)")
     check("resign_streak", "resign_q", "resign_holdout", "resign_seed")
+    if a.arena_gumbel_m2 is None:
+        a.arena_gumbel_m2 = a.arena_gumbel_m
+    if a.arena_gumbel_tree2 is None:
+        a.arena_gumbel_tree2 = a.arena_gumbel_tree
+    for flag, m, tree in (("--arena-gumbel-m", a.arena_gumbel_m, a.arena_gumbel_tree), ("--arena-gumbel-m2", a.arena_gumbel_m2, a.arena_gumbel_tree2)):
+        if not 0 <= m <= 43:
+            ap.error(f"{flag}: {m} is not a number of root moves (a whole number in [0, 43]; 0 = off)")
+        if tree not in (0, 1):
+            ap.error(f"{flag.replace('-m', '-tree')}: {tree} is not 0 or 1")
+        if tree == 1 and m == 0:
+            ap.error(f"{flag.replace('-m', '-tree')}: the selection below the root needs the Gumbel root search ({flag} above 0)")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if world == 1 and not shard_mod.force_dist():
         learn(a)

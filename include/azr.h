@@ -682,6 +682,32 @@ int azr_arena_set_opponent_net(azr_engine* h, azr_engine* other);
  * the reset through azr_arena_set_opponent_net(h, NULL) included.  The setting holds over later azr_arena_start calls until it is
  * set again.  Player AZR_PLAYER_ALPHAZERO, self-play, the one-net arenas and azr_mcts_* keep the handle's settings. */
 int azr_arena_set_opponent_search(azr_engine* h, int mcts_simulations, float hp_exploration);
+/* The Gumbel search of azr_selfplay_set_gumbel (every definition is the one stated there) for one AlphaZero player of this handle's
+ * arenas: player = AZR_PLAYER_ALPHAZERO or AZR_PLAYER_ALPHAZERO_B.  m = 0 (default) = off, the side searches by PUCT and plays bit for
+ * bit what it plays without this call, whatever the other side does.  A side with m > 0 plays every one of its decisions like this:
+ *   root vector   g = 0 on every move, as at a self-play root above temperature_threshold: nothing is drawn, there is no seed, and
+ *                 the arena stays a function of its arguments.
+ *   search        the root-level selection for the claim index i = the descents this search has started before.  n = this side's
+ *                 simulations per decision (S - S % T; player B's of azr_arena_set_opponent_search), m_eff = min(m, legal moves), N0 =
+ *                 the root's N row at this search's first root-level selection — the arena keeps a player's tree inside a turn, so
+ *                 N0 is non-zero from a turn's second decision on.  Below the root: PUCT with the side's own hp (tree = 0), or the
+ *                 selection below the root stated above (tree = 1), under this side's c_visit and c_scale.
+ *   vhat          in an arena with a Gumbel side every expansion stores the net's value in the node, in both players' trees; both
+ *                 trees are emptied at every deal, so no node without a vhat is ever searched.
+ *   decision      the move = the Decision above with g = 0; with azr_arena_collect_samples on, the record's pi is the record's pi
+ *                 above (what a self-play Gumbel record carries) in place of the visit distribution.  z, the flush order and every
+ *                 counter are what they are without the feature.
+ * From the same state, RNG word and tree contents a decision gives the root's N and Q, the move and the pi of a host-stepped search
+ * under azr_mcts_set_gumbel(m, c_visit, c_scale), azr_mcts_set_gumbel_tree(tree), azr_mcts_set_root_gumbel(NULL),
+ * azr_mcts_set_simulations(n) and the side's hp (tests/arena_retrace.py).
+ * AZR_E_INVALID_ARGUMENT, with a reason in azr_last_error, for another player, m outside [0, 43], a c_visit or c_scale that is not
+ * finite, with m > 0 a c_visit < 0 or c_scale <= 0, a tree other than 0 or 1, and tree = 1 with m = 0.  Lifetime as
+ * azr_arena_set_opponent_search's: read by azr_arena_start; AZR_E_STATE between azr_arena_start and the arena's finish; holds over later
+ * arenas until set again; player B's goes back to off with azr_arena_set_opponent_net(h, NULL).  A setting for a player that an arena
+ * does not have leaves that arena as it is.  azr_arena_start returns AZR_E_INVALID_ARGUMENT, with a reason and the handle unchanged,
+ * when a side of the arena has m > 0 while azr_arena_collect_scripted_samples is on.  Independent of azr_selfplay_set_gumbel and
+ * azr_mcts_set_gumbel, which keep their meaning; the first host-stepped Gumbel search after an arena still clears the trees. */
+int azr_arena_set_gumbel(azr_engine* h, int player, int m, float c_visit, float c_scale, int tree);
 /* INCLUDE_COMPARE_GAMES_TRAIN_SAMPLES (alphazero_trainer.cpp:143-146): AlphaZero players push (s, pi) at every decision
  * (alphazero_player.cpp:15-18); a finished game's records get their z and go to the record ring (azr_samples_drain),
  * game by game in decision order (the reference appends player by player).  Set before azr_arena_start.  Its sibling

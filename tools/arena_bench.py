@@ -3,8 +3,10 @@
 device: `games` mirrored games on `slots` engine slots, S simulations per move, THREADS_PER_MCTS T, B blocks, bf16 — or, with
 --blocks-b / --dtype-b, an opponent net of another depth and / or arithmetic (random-init nets: a timing, not a strength).
     python tools/arena_bench.py [--games 100] [--slots 128] [--sims 100] [--threads 2] [--blocks 20] [--dtype bf16]
-                                [--blocks-b N] [--dtype-b bf16|f16|f32x|f32] [--mcts-b S] [--hp-b C]
+                                [--blocks-b N] [--dtype-b bf16|f16|f32x|f32] [--mcts-b S] [--hp-b C] [--gumbel-m M [--gumbel-tree 1]]
 --mcts-b / --hp-b: the opponent player's own simulations per move and PUCT constant (azr_arena_set_opponent_search).
+--gumbel-m / --gumbel-tree: both players search by the Gumbel search with sequential halving over M root moves (azr_arena_set_gumbel),
+with the improved-policy selection below the root under --gumbel-tree 1; 0 (default) = PUCT, the arena's plain step.
 AZR_EXP_LIB=<library>: time that build of the same sources instead (e.g. libazr_hip_test.so with one of its environment hooks)."""
 import argparse
 import importlib
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--dtype-b", default=None, choices=sorted(DTYPES), help="arithmetic of the opponent handle's net (default: --dtype)")
     ap.add_argument("--mcts-b", type=int, default=None, help="simulations per move of the opponent player (default: --sims)")
     ap.add_argument("--hp-b", type=float, default=None, help="PUCT constant of the opponent player (default: the engine's 1.1)")
+    ap.add_argument("--gumbel-m", type=int, default=0, help="root moves of both players' Gumbel search (0 = PUCT)")
+    ap.add_argument("--gumbel-tree", type=int, default=0, choices=(0, 1), help="1: the improved-policy selection below the root (needs --gumbel-m)")
     ap.add_argument("--pair-halves", type=int, default=1, help="1: a mirrored pair's two games at the same time on two slots; 0: one after the other on one slot")
     a = ap.parse_args()
     blocks_b = a.blocks if a.blocks_b is None else a.blocks_b
@@ -47,6 +51,10 @@ def main():
     if a.mcts_b is not None or a.hp_b is not None:
         new.arena_set_opponent_search(a.mcts_b, a.hp_b)
         budget = f" (S={a.sims if a.mcts_b is None else a.mcts_b} hp={1.1 if a.hp_b is None else a.hp_b})"
+    if a.gumbel_m > 0:
+        for player in (P.PLAYER_ALPHAZERO, P.PLAYER_ALPHAZERO_B):
+            new.arena_set_gumbel(player, a.gumbel_m, tree=a.gumbel_tree)
+        budget += f" Gumbel m={a.gumbel_m}" + (" tree" if a.gumbel_tree else "")
     new.arena_start(P.PLAYER_ALPHAZERO, P.PLAYER_ALPHAZERO_B, a.games, 0, P.MIRROR_CONCURRENT if a.pair_halves else P.MIRROR_SEQUENTIAL, 20260001)
     t0 = time.time()
     while not new.arena_run(256):

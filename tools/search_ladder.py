@@ -7,6 +7,10 @@ win share against simulation count of the AlphaZero papers.  --blocks-b / --dtyp
     python tools/search_ladder.py [--checkpoint FILE [--checkpoint-b FILE] | --seed N] [--mcts-a 32] [--mcts-b 2,4,8,16,32,64,128]
                                   [--hp-a 1.1] [--hp-b 1.1] [--blocks 20] [--dtype bf16] [--blocks-b N] [--dtype-b bf16|f16|f32x|f32]
                                   [--games 100] [--threads 2] [--slots 128] [--base-seed 20260001]
+                                  [--gumbel-m-a M] [--gumbel-m-b M] [--gumbel-tree-a 1] [--gumbel-tree-b 1] [--gumbel-cvisit 50] [--gumbel-cscale 0.5]
+--gumbel-m-a / --gumbel-m-b give a side the Gumbel search with sequential halving over M root moves in place of PUCT (azr_arena_set_gumbel;
+deterministic), --gumbel-tree-a / -b its improved-policy selection below the root: PUCT against Gumbel at one net and equal budgets is
+`--mcts-a 16 --mcts-b 16 --gumbel-m-b 16`.
 A checkpoint holds one depth: with --blocks-b other than --blocks name B's own (--checkpoint-b).  Without a checkpoint the nets are
 random-init from --seed; such a net knows nothing about the game, so the table then shows the tool, not a strength."""
 import argparse
@@ -39,6 +43,12 @@ def main():
     ap.add_argument("--threads", type=int, default=2)
     ap.add_argument("--slots", type=int, default=128)
     ap.add_argument("--base-seed", type=int, default=20260001)
+    ap.add_argument("--gumbel-m-a", type=int, default=0, help="root moves of A's Gumbel search (0 = PUCT)")
+    ap.add_argument("--gumbel-m-b", type=int, default=0, help="root moves of B's Gumbel search (0 = PUCT)")
+    ap.add_argument("--gumbel-tree-a", type=int, default=0, choices=(0, 1), help="1: A selects below the root by the improved policy (needs --gumbel-m-a)")
+    ap.add_argument("--gumbel-tree-b", type=int, default=0, choices=(0, 1), help="1: B selects below the root by the improved policy (needs --gumbel-m-b)")
+    ap.add_argument("--gumbel-cvisit", type=float, default=50.0)
+    ap.add_argument("--gumbel-cscale", type=float, default=0.5)
     a = ap.parse_args()
     rungs = [int(x) for x in a.mcts_b.split(",") if x]
     blocks_b = a.blocks if a.blocks_b is None else a.blocks_b
@@ -59,9 +69,12 @@ def main():
         else:
             eb.init_random(a.seed)
     ea.arena_set_opponent(eb)
+    ea.arena_set_gumbel(P.PLAYER_ALPHAZERO, a.gumbel_m_a, a.gumbel_cvisit, a.gumbel_cscale, a.gumbel_tree_a)
+    ea.arena_set_gumbel(P.PLAYER_ALPHAZERO_B, a.gumbel_m_b, a.gumbel_cvisit, a.gumbel_cscale, a.gumbel_tree_b)
+    search = lambda m, tree: f"Gumbel m {m}" + (" (tree)" if tree else "") + f" c_visit {a.gumbel_cvisit:g} c_scale {a.gumbel_cscale:g}" if m > 0 else "PUCT"   # noqa: E731
     what = f"checkpoint {a.checkpoint}" if a.checkpoint else f"random-init seed {a.seed}"
-    print(f"A = {a.dtype} {a.blocks} blocks at {a.mcts_a} simulations, hp {a.hp_a}; B = {dtype_b} {blocks_b} blocks, hp "
-          f"{a.hp_a if a.hp_b is None else a.hp_b}; {what}, T = {a.threads}, {a.games} games per rung on {a.slots} slots")
+    print(f"A = {a.dtype} {a.blocks} blocks at {a.mcts_a} simulations, hp {a.hp_a}, {search(a.gumbel_m_a, a.gumbel_tree_a)}; B = {dtype_b} {blocks_b} blocks, hp "
+          f"{a.hp_a if a.hp_b is None else a.hp_b}, {search(a.gumbel_m_b, a.gumbel_tree_b)}; {what}, T = {a.threads}, {a.games} games per rung on {a.slots} slots")
     print(f"{'B sims':>7} {'count':>6} {'draw':>5} {'A wins':>7} {'B wins':>7} {'B share':>8}  95 % Wilson      wall s   dropped")
     for s in rungs:
         ea.arena_set_opponent_search(s, a.hp_b)
