@@ -13,45 +13,8 @@ from gpu_common import pkg, records
 
 pytestmark = pytest.mark.gpu
 import torch_train_ref as train
+from torch_train_ref import torch_step
 from train_replay import epoch_loop_against_single_steps, kinds, tf_adam
-
-
-def torch_step(blocks, flat, rec, margin=None):
-    """loss, gradients (AZRW layout, without the L2 term) and post-step BN moving statistics from the PyTorch graph.
-    margin (a list): receives the smallest non-zero |ReLU input| of the float64 forward — an fp32 forward whose rounding
-    lands on the other side of such an input flips one mask, a discrete change of the gradients (measured: flips at
-    2.5e-7 .. 6.4e-7, none at 1.1e-6, with either conv kernel)"""
-    net = train.AzrNet(blocks, flat).double()
-    net.train()
-    in88, pi, z = train.unpack_records(rec)
-    x = torch.from_numpy(train.planes_from_in88(in88)).double()
-    relu0 = train.F.relu
-
-    def relu(t, *a, **k):
-        if margin is not None:
-            v = t.detach().abs()
-            v = v[v > 0]
-            if v.numel():
-                margin.append(float(v.min()))
-        return relu0(t, *a, **k)
-
-    train.F.relu = relu
-    try:
-        lp, lv, _ = net.losses(x, torch.from_numpy(pi).double(), torch.from_numpy(z).double())
-    finally:
-        train.F.relu = relu0
-    (lp + lv).backward()
-    g = np.zeros(net.count, np.float64)
-    for name, off, shape in net.lay:
-        n = int(np.prod(shape))
-        if name.endswith("_bn"):
-            key = name[:-3]
-            c = shape[1]
-            g[off:off + c] = net.p[key + "_g"].grad.numpy()
-            g[off + c:off + 2 * c] = net.p[key + "_b"].grad.numpy()
-        else:
-            g[off:off + n] = net.p[name].grad.numpy().reshape(-1)
-    return float(lp.detach()), float(lv.detach()), g, net.to_flat()
 
 
 @pytest.mark.parametrize("blocks,bs,gemm", [(1, 16, "split"), (2, 64, "split"), (2, 64, "r2"), (2, 64, "f32"), (1, 10, "split"),

@@ -4,7 +4,16 @@ Two (and four) ranks over gloo share this box's one GPU; each takes its slice of
 losses / gradients are all-reduced through the callback, every rank takes the same Adam step.  The reference trains on
 GPU 0 only (alphazero_gpu_cluster.cpp:221-231); what is being replaced is its weight hand-over through temp.bin.
 Tolerances are those of tests/test_gpu_train.py for the step itself: losses 2e-5, per-tensor gradients 2e-3 of the
-tensor's largest gradient, weights after Adam 2e-6 absolute per step taken."""
+tensor's largest gradient, weights after Adam 2e-6 absolute per step taken.
+
+What this file is for: the multi-PROCESS path — torch.distributed's launcher, make_allreduce staged through gloo, one HIP
+context per rank on a shared card, the refusal of a batch that does not split evenly.  Its shares are 16, 32 and 64 records
+(one kernel family, t_conv_q), it compares with the single-GPU step of the same library only, and its 6-step run asserts no
+more than "epoch losses within 1e-3 relative" — two trajectories whose summation orders differ drift apart through Adam's
+first steps, so nothing tighter holds between them.  The arithmetic of the data-parallel step is pinned elsewhere, on groups
+of ranks in one process whose all-reduce sums in rank order (tests/dp_group.py): tests/test_gpu_train_dp_steps.py — the first
+step in every kernel family against the float64 graph, which records a rank takes, every later step replayed bit for bit on
+a fresh group, the epoch loop against single steps — and the world-8 step of tests/test_gpu_rehearsal.py."""
 import os
 import socket
 import subprocess

@@ -148,6 +148,57 @@ class AzrNet(torch.nn.Module):
         return flat
 
 
+def torch_step(blocks, flat, rec, margin=None, per_record=None, backward=True):
+    """loss, gradients (AZRW layout, without the L2 term) and post-step BN moving statistics from the PyTorch graph in float64: the
+    reference of tests/test_gpu_train.py and tests/test_gpu_train_dp_steps.py.
+    margin (a list): receives the smallest non-zero |ReLU input| of the float64 forward — an fp32 forward whose rounding
+    lands on the other side of such an input flips one mask, a discrete change of the gradients (measured: flips at
+    2.5e-7 .. 6.4e-7, none at 1.1e-6, with either conv kernel);
+    per_record (a list): receives the per-record cross-entropy and squared error (train-mode BN: batch statistics of the WHOLE
+    minibatch), whose means are the two losses; backward=False: the forward pass only (the gradient vector returned is None)"""
+    net = AzrNet(blocks, flat).double()
+    net.train()
+    in88, pi, z = unpack_records(rec)
+    x = torch.from_numpy(planes_from_in88(in88)).double()
+    relu0 = F.relu
+
+    def relu(t, *a, **k):
+        if margin is not None:
+            v = t.detach().abs()
+            v = v[v > 0]
+            if v.numel():
+                margin.append(float(v.min()))
+        return relu0(t, *a, **k)
+
+    pi_t, z_t = torch.from_numpy(pi).double(), torch.from_numpy(z).double()
+    F.relu = relu
+    try:
+        with torch.set_grad_enabled(backward):
+            logits, v = net(x)
+    finally:
+        F.relu = relu0
+    with torch.set_grad_enabled(backward):
+        ce = -(pi_t * F.log_softmax(logits, dim=1)).sum(1)
+        lp, lv = ce.mean(), F.mse_loss(v, z_t)
+    if per_record is not None:
+        per_record.append(ce.detach().numpy().copy())
+        per_record.append(((v - z_t) ** 2).detach().numpy().copy())
+    if not backward:
+        return float(lp.detach()), float(lv.detach()), None, net.to_flat()
+    (lp + lv).backward()
+    g = np.zeros(net.count, np.float64)
+    for name, off, shape in net.lay:
+        n = int(np.prod(shape))
+        if name.endswith("_bn"):
+            key = name[:-3]
+            c = shape[1]
+            g[off:off + c] = net.p[key + "_g"].grad.numpy()
+            g[off + c:off + 2 * c] = net.p[key + "_b"].grad.numpy()
+        else:
+            g[off:off + n] = net.p[name].grad.numpy().reshape(-1)
+    return float(lp.detach()), float(lv.detach()), g, net.to_flat()
+
+
 class Trainer:
     """AlphaZeroNNId::train (alphazero_gpu_cluster.h:31) for one net; keeps the Adam state across iterations like the
     TF session does."""

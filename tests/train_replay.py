@@ -6,7 +6,8 @@ stream's events), whichever batch size or call came before.  What the replay can
 a fresh engine does not have — adam_trajectory restates on the host across the whole schedule.  Nothing here compares with float64:
 that is test_gpu_train.py::test_step_matches_torch_graph, on the first step of any weights.
 epoch_loop_against_single_steps is the other proof two test files share: azr_nn_train's queue of steps against single train_batch calls.
-An engine is anything with set_weights / get_weights / train_batch / train_grads / train_reset / validate / predict (and close)."""
+An engine is anything with set_weights / get_weights / train_batch / train_grads / train_reset / validate / predict (and close); a
+group of data-parallel ranks (tests/dp_group.py::DpGroup) is one, and adds solo_batch for the schedule kind "solo"."""
 import os
 import subprocess
 from typing import NamedTuple, Optional, Tuple
@@ -18,6 +19,7 @@ import torch_train_ref as train
 f32 = np.float32
 ADAM_BOUND = 5e-7    # per step on the trainable slots: a lost moment or a restarted step count moves weights by about the learning rate, 1e-3
 E_STATE = 7          # AZR_E_STATE (include/azr.h): azr_nn_train_grads without a training context
+TRAIN_KINDS = ("train", "solo")   # the schedule entries that take an optimiser step
 
 
 class Step(NamedTuple):
@@ -66,6 +68,8 @@ def _call(eng, kind, bs, rec):
     """the single call of one schedule step; returns (out, grads)"""
     if kind == "train":
         return tuple(eng.train_batch(rec)), eng.train_grads()
+    if kind == "solo":      # a group of ranks (tests/dp_group.py): every rank takes the plain single-GPU step itself
+        return tuple(eng.solo_batch(rec)), eng.train_grads()
     if kind == "validate":
         return tuple(eng.validate(rec, batch_size=bs, per_record=True)), None
     if kind == "predict":
@@ -80,8 +84,8 @@ def _call(eng, kind, bs, rec):
 
 
 def run_schedule(make_engine, flat, schedule, rec):
-    """drive ONE engine through the schedule — ("train", bs), ("validate", bs, nb), ("predict", n), ("reset",) — on consecutive, disjoint
-    slices of rec; returns the trace, a Step per schedule entry"""
+    """drive ONE engine through the schedule — ("train", bs), ("solo", bs), ("validate", bs, nb), ("predict", n), ("reset",) — on
+    consecutive, disjoint slices of rec; returns the trace, a Step per schedule entry.  "solo" is a train step too (TRAIN_KINDS)"""
     eng = make_engine()
     eng.set_weights(flat)
     trace, at, fresh = [], 0, True
@@ -97,7 +101,7 @@ def run_schedule(make_engine, flat, schedule, rec):
             w0 = eng.get_weights()
             out, grads = _call(eng, kind, bs, r)
             trace.append(Step(kind, bs, w0, r if n else None, out, grads, eng.get_weights(), fresh))
-            fresh = kind == "reset" or (fresh and kind != "train")
+            fresh = kind == "reset" or (fresh and kind not in TRAIN_KINDS)
     finally:
         if hasattr(eng, "close"):
             eng.close()
@@ -149,7 +153,7 @@ def _layout_of(count):
 
 def assert_pure(trace, replayed, layout=None, moving=None):
     """the engine under test did at every step what a fresh engine does with the same weights and inputs.
-    train:    the loss pairs are ==, the gradient vectors equal as uint32 (neither the moving statistics' history nor the Adam state
+    train, solo: the loss pairs are ==, the gradient vectors equal as uint32 (neither the moving statistics' history nor the Adam state
               enter them); the moving statistics behind the step (slots where `moving` is set) are equal too: momentum 0.99 on the
               batch statistics, again weights and minibatch alone.  The trained slots behind the step are compared only where the
               step is `fresh` — the first one, and the first behind a reset: there the engine's m, v and step count are what the
@@ -173,7 +177,7 @@ def assert_pure(trace, replayed, layout=None, moving=None):
             assert a.out == (E_STATE,), "%s: train_grads behind a reset must fail with AZR_E_STATE, got %r" % (where, a.out)
             continue
         assert b is not None and first_difference(a.w0, b.w0, layout) is None, where
-        if a.kind == "train":
+        if a.kind in TRAIN_KINDS:
             assert a.out == b.out, "%s: losses %r, on a fresh engine %r" % (where, a.out, b.out)
             d = first_difference(a.grads, b.grads, layout)
             assert d is None, "%s: gradients differ from a fresh engine's, first in %s, %d entries in all" % ((where,) + d)
@@ -203,12 +207,12 @@ def adam_trajectory(trace, kinds):
     for i, s in enumerate(trace):
         if s.kind == "reset":
             m, v, t = np.zeros(n, f32), np.zeros(n, f32), 0
-        if s.kind != "train":
+        if s.kind not in TRAIN_KINDS:
             continue
         t += 1
         w, m, v = tf_adam(s.w0, s.grads, m, v, t, kinds)
         dev = float(np.abs(s.w1[tr] - w[tr]).max())
-        assert dev <= ADAM_BOUND, "step %d (train, batch %d), Adam step %d: weights %.3g away from Adam on the carried moments" % (i, s.bs, t, dev)
+        assert dev <= ADAM_BOUND, "step %d (%s, batch %d), Adam step %d: weights %.3g away from Adam on the carried moments" % (i, s.kind, s.bs, t, dev)
         worst = max(worst, dev)
     return worst
 
