@@ -53,6 +53,26 @@ class ResignStats(C.Structure):   # azr_resign_stats
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+LR_CONSTANT, LR_COSINE, LR_STEP = 0, 1, 2   # azr_train_options.lr_schedule (include/azr.h)
+LR_SCHEDULES = {"constant": LR_CONSTANT, "cosine": LR_COSINE, "step": LR_STEP}
+
+
+class TrainOptions(C.Structure):   # azr_train_options
+    _fields_ = [("lr", C.c_float), ("l2", C.c_float), ("lr_schedule", C.c_int32), ("warmup_steps", C.c_int32), ("total_steps", C.c_int32),
+                ("decay_period", C.c_int32), ("decay_gamma", C.c_float), ("lr_min", C.c_float), ("clip_norm", C.c_float), ("ema_decay", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class TrainStats(C.Structure):   # azr_train_stats
+    _fields_ = [("step", C.c_int64), ("lr", C.c_float), ("lr_t", C.c_float), ("grad_norm", C.c_float), ("clip_scale", C.c_float),
+                ("clipped_steps", C.c_int64), ("ema_steps", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)   # azr_allreduce_fn
 
 
@@ -100,6 +120,7 @@ EXPORTS = [
     "azr_selfplay_set_gumbel", "azr_mcts_set_gumbel", "azr_mcts_set_root_gumbel", "azr_mcts_root_gumbel", "azr_mcts_gumbel_policy",
     "azr_mcts_gumbel_pick", "azr_debug_root_gumbel", "azr_debug_gumbel_select", "azr_debug_exp32",
     "azr_selfplay_set_gumbel_tree", "azr_mcts_set_gumbel_tree", "azr_debug_gumbel_tree_select", "azr_mcts_node_stats",
+    "azr_default_train_options", "azr_nn_train_set_options", "azr_nn_train_get_options", "azr_nn_train_stats", "azr_nn_get_ema_weights",
 ]
 
 
@@ -137,6 +158,12 @@ def load_library(test_hooks=False):
         L.azr_dp_shutdown.argtypes = [C.c_void_p]
         L.azr_nn_train_grads.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.azr_nn_train_reset.argtypes = [C.c_void_p]
+        L.azr_default_train_options.argtypes = [C.c_void_p]
+        L.azr_default_train_options.restype = None
+        L.azr_nn_train_set_options.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_nn_train_get_options.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_nn_train_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.azr_nn_get_ema_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.azr_selfplay_start.argtypes = [C.c_void_p, C.c_uint32]
         L.azr_selfplay_start_games.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
         L.azr_selfplay_start_from_states.argtypes = [C.c_void_p, C.c_uint32]
@@ -417,6 +444,35 @@ class Engine:
 
     def train_reset(self):
         self._chk(self.L.azr_nn_train_reset(self.h))
+
+    def train_set_options(self, **kw):
+        """azr_nn_train_set_options: the defaults (azr_default_train_options) with the given fields of azr_train_options replaced;
+        lr_schedule is LR_CONSTANT / LR_COSINE / LR_STEP or its name.  Read when the next training call is entered."""
+        o = TrainOptions()
+        self.L.azr_default_train_options(C.byref(o))
+        for k, v in kw.items():
+            if k not in dict(TrainOptions._fields_):
+                raise TypeError(f"unknown training option {k}")
+            setattr(o, k, LR_SCHEDULES[v] if k == "lr_schedule" and isinstance(v, str) else v)
+        self._chk(self.L.azr_nn_train_set_options(self.h, C.byref(o)))
+
+    def train_options(self):
+        """azr_nn_train_get_options as a dict of azr_train_options' fields"""
+        o = TrainOptions()
+        self._chk(self.L.azr_nn_train_get_options(self.h, C.byref(o)))
+        return o.as_dict()
+
+    def train_stats(self):
+        """azr_nn_train_stats of the last step as a dict of azr_train_stats' fields (AZR_E_STATE before the first step)"""
+        s = TrainStats()
+        self._chk(self.L.azr_nn_train_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def get_ema_weights(self):
+        """azr_nn_get_ema_weights: the EMA vector in AZRW layout (AZR_E_STATE while there is none)"""
+        f = np.zeros(self.param_count(), np.float32)
+        self._chk(self.L.azr_nn_get_ema_weights(self.h, _p(f), f.size))
+        return f
 
     # ---- search
     def mcts_clear(self):

@@ -237,6 +237,9 @@ struct ProfEvents {
 };
 constexpr int PROF_MAX = 24;   // sampled passes per run
 
+// azr_default_train_options: the reference's graph (build_graph.py:30-31,103) — Adam at a constant 1e-3, L2 1e-3, no clipping, no EMA
+constexpr azr_train_options TRAIN_OPT_DEFAULT = {1e-3f, 1e-3f, AZR_LR_CONSTANT, 0, 0, 1, 1.0f, 0.0f, 0.0f, 0.0f};
+
 }  // namespace azr
 
 struct azr_engine {
@@ -271,6 +274,8 @@ struct azr_engine {
     azr::StepOpts sp;             // ... and what azr_selfplay_start* found in force: this self-play's steps carry it (the values are in d)
     bool sp_tail = false;         // quota self-play: no game is left to start, slots go idle -> compacted net batches
     void* train = nullptr;        // azr_train.hip: optimiser state + activation slabs, created by the first azr_nn_train*
+    // azr_nn_train_set_options: on the handle, not in the training context — a reset, a rebuild and a failed health check leave them
+    azr_train_options train_opt = azr::TRAIN_OPT_DEFAULT;
     void* dp_comm = nullptr;      // azr_dp_init: this handle's RCCL communicator (ncclComm_t), rank and world
     int dp_rank = 0, dp_world = 0;
 };

@@ -168,6 +168,119 @@ __global__ void t_adam(float* __restrict__ w, const float* __restrict__ g, float
 }
 
 // =====================================================================================================================
+// The step with options (azr_nn_train_set_options; formulae in include/azr.h).  With every option at its default the step
+// launches t_tick_lr and t_adam above and none of these; with neutral options (lr = LR, l2 = L2_C, s = 1) these give the
+// same bits: the arithmetic below is t_tick_lr's and t_adam's, with factors that are exactly 1.
+// =====================================================================================================================
+// what the kernels leave for azr_nn_train_stats: one row in device memory, so that azr_nn_train's queue of steps never waits for the host
+struct StatRow {
+    float lr;            // t_tick_lr_sched: the scheduled rate lr_eff of the last step
+    float norm;          // t_grad_sqsum_final: the global gradient norm (t_tick_lr_sched: NaN while clipping is off)
+    float scale;         // ... and the clip scale s that t_adam_opt multiplies by (1 while clipping is off)
+    int pad;
+    long long clipped;   // steps with s < 1 since the optimiser state was created
+};
+struct Sched {
+    double lr, r, gamma;   // base rate, lr_min / lr, STEP's factor
+    int schedule, W, N, period;
+    int clip;              // clipping is on: t_grad_sqsum_final has written norm and scale
+};
+
+__global__ void t_tick_lr_sched(int* __restrict__ cur, float* __restrict__ lr, StatRow* __restrict__ row, Sched a)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int ti = ++cur[1];
+    const double t = (double)ti;
+    const double warm = a.W > 0 ? fmin(1.0, t / (double)a.W) : 1.0;
+    double f = 1.0;
+    if (a.schedule == AZR_LR_COSINE) {
+        const double p = fmin(1.0, fmax(0.0, (t - (double)a.W) / (double)(a.N - a.W)));
+        f = a.r + (1.0 - a.r) * 0.5 * (1.0 + cos(M_PI * p));
+    } else if (a.schedule == AZR_LR_STEP) {
+        f = pow(a.gamma, (double)((ti - 1) / a.period));
+    }
+    const double lr_eff = a.lr * warm * f;
+    *lr = (float)(lr_eff * sqrt(1.0 - pow((double)ADAM_B2, t)) / (1.0 - pow((double)ADAM_B1, t)));
+    row->lr = (float)lr_eff;
+    if (!a.clip) { row->norm = __builtin_nanf(""); row->scale = 1.0f; }
+}
+
+// sum of g^ ^2 over the trained slots, g^ in fp32 as t_adam_opt forms it, squares and sums in double.  A FIXED grid (the order of the
+// partials does not depend on the device): thread j of SQ_BLOCKS * 256 takes slots j, j + SQ_BLOCKS * 256, ...; its sum goes
+// down the wavefront by cross-lane moves (32, 16, ... 1), the block's four wave sums through LDS, in wave order -> part[block].
+constexpr int SQ_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void t_grad_sqsum(const float* __restrict__ w, const float* __restrict__ g, const uint8_t* __restrict__ kind,
+                                                    size_t n, float l2x2, double* __restrict__ part)
+{
+    __shared__ double ws[4];
+    constexpr size_t SWEEP = (size_t)SQ_BLOCKS * 256;
+    auto sq = [l2x2](int k, float gi, float wi) {
+        if (k == 1) gi += l2x2 * wi;
+        return k == 0 ? 0.0 : (double)gi * (double)gi;
+    };
+    double acc = 0.0;
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    // four sweeps per trip: twelve loads in flight per lane, the squares added in slot order as the one-sweep loop below adds them
+    for (; i + 3 * SWEEP < n; i += 4 * SWEEP) {
+        const int k0 = kind[i], k1 = kind[i + SWEEP], k2 = kind[i + 2 * SWEEP], k3 = kind[i + 3 * SWEEP];
+        const float g0 = g[i], g1 = g[i + SWEEP], g2 = g[i + 2 * SWEEP], g3 = g[i + 3 * SWEEP];
+        const float w0 = w[i], w1 = w[i + SWEEP], w2 = w[i + 2 * SWEEP], w3 = w[i + 3 * SWEEP];
+        acc += sq(k0, g0, w0);
+        acc += sq(k1, g1, w1);
+        acc += sq(k2, g2, w2);
+        acc += sq(k3, g3, w3);
+    }
+    for (; i < n; i += SWEEP) acc += sq(kind[i], g[i], w[i]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+// one block: the partials in index order -> norm, s = clip / max(norm, clip), the count of clipped steps
+__global__ __launch_bounds__(256) void t_grad_sqsum_final(const double* __restrict__ part, double clip, StatRow* __restrict__ row)
+{
+    __shared__ double ps[SQ_BLOCKS];
+    for (int i = threadIdx.x; i < SQ_BLOCKS; i += 256) ps[i] = part[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (int i = 0; i < SQ_BLOCKS; i++) sum += ps[i];
+    const double norm = sqrt(sum);
+    const float s = (float)(clip / fmax(norm, clip));
+    row->norm = (float)norm;
+    row->scale = s;
+    if (s < 1.0f) row->clipped += 1;
+}
+
+// t_adam on s * g^ at the scheduled rate, and the EMA of the new weights in the same pass (no second sweep over the vectors)
+template <bool EMA>
+__global__ void t_adam_opt(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float* __restrict__ e,
+                           const uint8_t* __restrict__ kind, size_t n, const float* __restrict__ lr, const StatRow* __restrict__ row, float l2x2,
+                           float d)
+{
+    const float lr_t = *lr, s = row->scale;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int k = kind[i];
+    if (k == 0) {   // BN moving statistics: the forward pass of this step has updated them, and they are averages already
+        if (EMA) e[i] = w[i];
+        return;
+    }
+    float wi = w[i];
+    float gi = g[i];
+    if (k == 1) gi += l2x2 * wi;
+    gi *= s;
+    const float mi = ADAM_B1 * m[i] + (1.0f - ADAM_B1) * gi;
+    const float vi = ADAM_B2 * v[i] + (1.0f - ADAM_B2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    wi -= lr_t * mi / (sqrtf(vi) + ADAM_EPS);
+    w[i] = wi;
+    if (EMA) e[i] = d * e[i] + (1.0f - d) * wi;
+}
+
+// =====================================================================================================================
 // host
 // =====================================================================================================================
 // conv GEMM arithmetic: split bf16 (default; 6-pass forward, 3-pass backward) or the fp32 MFMA (AZR_TRAIN_GEMM=f32)
@@ -233,6 +346,14 @@ struct TrainCtx {
     double* red = nullptr;     // [2 * NG][256] reduced BN partials
     double* hsum = nullptr;    // [6] head BN sums
     float* lr = nullptr;   // device: this step's bias-corrected learning rate
+    // the step's options (azr_nn_train_set_options), copied from the handle when a training call is entered
+    azr_train_options opt = {};
+    bool opt_default = true;     // ... every one at its default: the step launches t_tick_lr and t_adam
+    bool last_default = true;    // the path the LAST step took (azr_nn_train_stats)
+    StatRow* row = nullptr;      // device: what the step's kernels leave for azr_nn_train_stats
+    double* sqpart = nullptr;    // device: [SQ_BLOCKS] partial sums of the gradient norm
+    float* e = nullptr;          // device: the EMA vector, created by the first step with ema_decay > 0; optimiser state like m and v
+    long ema_steps = 0;          // steps folded into it
     // the weight-gradient branch of the backward pass (t_wgrad_g5 + t_sum_slices of every layer) hangs off the gradient chain: nothing
     // but Adam waits for it.  At small batches (<= 128 records: a rank's share of a data-parallel minibatch) it runs on a second,
     // low-priority stream beside the chain's kernels, which leave most of the chip idle there: 4.22 -> 3.87 ms per step at 64 records.
@@ -267,6 +388,14 @@ inline float* layer_at(float* flat, int l) { return flat + OFF_BLOCK0 + (size_t)
 inline const float* layer_at(const float* flat, int l) { return flat + OFF_BLOCK0 + (size_t)(l - 1) * LAYER; }
 
 TrainCtx* ctx_of(azr_engine* h) { return static_cast<TrainCtx*>(h->train); }
+
+// a training call is entered: the handle's options, as they are now, are this call's
+void opt_enter(azr_engine* h, TrainCtx* c)
+{
+    const azr_train_options& o = h->train_opt;
+    c->opt = o;
+    c->opt_default = o.lr == LR && o.l2 == L2_C && o.lr_schedule == AZR_LR_CONSTANT && o.warmup_steps == 0 && o.clip_norm == 0.0f && o.ema_decay == 0.0f;
+}
 
 template <typename T>
 int dalloc(azr_engine* h, TrainCtx* c, T** p, size_t n)
@@ -323,9 +452,20 @@ int ctx_ensure(azr_engine* h, int BS)
 #endif
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(t_wgrad_g5<WG5_NC>), hipFuncAttributeMaxDynamicSharedMemorySize, Wg5<WG5_NC>::LDS_BLOCK));
     // a different batch size rebuilds the activation slabs but keeps the optimiser state
-    std::vector<float> keep_m, keep_v;
-    long keep_step = 0;
+    std::vector<float> keep_m, keep_v, keep_e;
+    long keep_step = 0, keep_ema_steps = 0;
+    StatRow keep_row = {};     // what azr_nn_train_stats reports is the last STEP's, whatever was rebuilt since: the row, the rate, the path
+    float keep_lr = 0.0f;
+    bool keep_last_default = true;
     if (c) {
+        keep_last_default = c->last_default;
+        if (c->e) {
+            keep_e.resize(c->count);
+            HIPCHK(h, hipMemcpy(keep_e.data(), c->e, c->count * 4, hipMemcpyDeviceToHost));
+            keep_ema_steps = c->ema_steps;
+        }
+        HIPCHK(h, hipMemcpy(&keep_row, c->row, sizeof keep_row, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&keep_lr, c->lr, sizeof keep_lr, hipMemcpyDeviceToHost));
         keep_m.resize(c->count); keep_v.resize(c->count);
         HIPCHK(h, hipMemcpy(keep_m.data(), c->m, c->count * 4, hipMemcpyDeviceToHost));
         HIPCHK(h, hipMemcpy(keep_v.data(), c->v, c->count * 4, hipMemcpyDeviceToHost));
@@ -394,6 +534,15 @@ int ctx_ensure(azr_engine* h, int BS)
     TRY(dalloc(h, c, &c->loss, (size_t)4));
     TRY(dalloc(h, c, &c->cur, (size_t)4)); TRY(dalloc(h, c, &c->lr, (size_t)1));
     TRY(dalloc(h, c, &c->red, (size_t)2 * NG * NF)); TRY(dalloc(h, c, &c->hsum, (size_t)8));
+    TRY(dalloc(h, c, &c->row, (size_t)1)); TRY(dalloc(h, c, &c->sqpart, (size_t)SQ_BLOCKS));
+    HIPCHK(h, hipMemcpy(c->row, &keep_row, sizeof keep_row, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(c->lr, &keep_lr, sizeof keep_lr, hipMemcpyHostToDevice));
+    c->last_default = keep_last_default;
+    if (!keep_e.empty()) {
+        TRY(dalloc(h, c, &c->e, c->count));
+        HIPCHK(h, hipMemcpy(c->e, keep_e.data(), c->count * 4, hipMemcpyHostToDevice));
+        c->ema_steps = keep_ema_steps;
+    }
     {
         const int init[4] = {0, (int)keep_step, 0, 0};
         HIPCHK(h, hipMemcpy(c->cur, init, sizeof init, hipMemcpyHostToDevice));
@@ -737,9 +886,31 @@ int train_step(azr_engine* h, TrainCtx* c, float* d_acc)
     // ---------------- data-parallel: the ranks' gradient vectors add up to the gradient of the whole minibatch (one RCCL
     //                  all-reduce of count floats: 94.7 MB at B = 20); every rank then takes the same Adam step
     if (dp) TRY(dp_allreduce(h, c, g, c->count, 0));
-    // ---------------- Adam
-    hipLaunchKernelGGL(t_tick_lr, dim3(1), dim3(1), 0, st, c->cur, c->lr);
-    hipLaunchKernelGGL(t_adam, grid1(c->count, 256), dim3(256), 0, st, w, g, c->m, c->v, c->kind, c->count, (const float*)c->lr);
+    // ---------------- Adam: with every option at its default, the reference's step; else [norm ->] schedule -> Adam on the clipped
+    //                  gradient (+ EMA), behind the all-reduce so that every rank computes the same norm
+    c->last_default = c->opt_default;
+    if (c->opt_default) {
+        hipLaunchKernelGGL(t_tick_lr, dim3(1), dim3(1), 0, st, c->cur, c->lr);
+        hipLaunchKernelGGL(t_adam, grid1(c->count, 256), dim3(256), 0, st, w, g, c->m, c->v, c->kind, c->count, (const float*)c->lr);
+    } else {
+        const azr_train_options& o = c->opt;
+        const float l2x2 = 2.0f * o.l2;
+        if (o.clip_norm > 0.0f) {
+            hipLaunchKernelGGL(t_grad_sqsum, dim3(SQ_BLOCKS), dim3(256), 0, st, (const float*)w, (const float*)g, (const uint8_t*)c->kind, c->count, l2x2, c->sqpart);
+            hipLaunchKernelGGL(t_grad_sqsum_final, dim3(1), dim3(256), 0, st, (const double*)c->sqpart, (double)o.clip_norm, c->row);
+        }
+        const Sched sc = {(double)o.lr, (double)o.lr_min / (double)o.lr, (double)o.decay_gamma, o.lr_schedule, o.warmup_steps, o.total_steps,
+                          o.decay_period, o.clip_norm > 0.0f ? 1 : 0};
+        hipLaunchKernelGGL(t_tick_lr_sched, dim3(1), dim3(1), 0, st, c->cur, c->lr, c->row, sc);
+        if (o.ema_decay > 0.0f) {
+            hipLaunchKernelGGL(t_adam_opt<true>, grid1(c->count, 256), dim3(256), 0, st, w, (const float*)g, c->m, c->v, c->e, (const uint8_t*)c->kind, c->count,
+                               (const float*)c->lr, (const StatRow*)c->row, l2x2, o.ema_decay);
+            c->ema_steps++;
+        } else {
+            hipLaunchKernelGGL(t_adam_opt<false>, grid1(c->count, 256), dim3(256), 0, st, w, (const float*)g, c->m, c->v, (float*)nullptr, (const uint8_t*)c->kind,
+                               c->count, (const float*)c->lr, (const StatRow*)c->row, l2x2, 0.0f);
+        }
+    }
     hipLaunchKernelGGL(t_tick_batch, dim3(1), dim3(1), 0, st, c->cur, BSg);
     HIPCHK(h, hipGetLastError());
     return AZR_OK;
@@ -751,6 +922,11 @@ int train_step(azr_engine* h, TrainCtx* c, float* d_acc)
 int run_step(azr_engine* h, TrainCtx* c)
 {
     c->step++;
+    if (c->opt.ema_decay > 0.0f && !c->e) {   // the EMA vector starts as the weights from before its first step
+        TRY(dalloc(h, c, &c->e, c->count));
+        HIPCHK(h, hipMemcpyAsync(c->e, h->net.d_flat, c->count * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        c->ema_steps = 0;
+    }
     hipLaunchKernelGGL(t_gather, dim3(c->BS), dim3(64), 0, h->stream, c->rec, c->perm, (const int*)c->cur, c->BS, c->in88, c->pit, c->zt);
     return train_step(h, c, c->loss + 2);
 }
@@ -834,6 +1010,7 @@ extern "C" int azr_nn_train_batch(azr_engine* h, const void* rec265_host, int n,
     TRY(ctx_ensure(h, n));
     TrainCtx* c = ctx_of(h);
     c->world = 1; c->rank = 0; c->ar = nullptr; c->ar_ctx = nullptr; c->native = false;   // (a data-parallel call that failed half-way must not linger)
+    opt_enter(h, c);
     TRY(upload_records(h, c, rec265_host, (size_t)n));
     std::vector<int> id(n);
     for (int i = 0; i < n; i++) id[i] = i;
@@ -888,6 +1065,7 @@ static int train_impl(azr_engine* h, const void* rec265_host, size_t n, int epoc
         TRY(ctx_ensure(h, local_bs));
         c = ctx_of(h);
         c->world = world; c->rank = rank; c->ar = ar; c->ar_ctx = ar_ctx; c->native = native;
+        opt_enter(h, c);
         TRY(upload_records(h, c, rec265_host, n));
     }
     int rc = AZR_OK;
@@ -1071,6 +1249,72 @@ extern "C" int azr_nn_train_reset(azr_engine* h)
 {
     if (!h) return AZR_E_BAD_HANDLE;
     azr::train_free(h);
+    return AZR_OK;
+}
+
+extern "C" void azr_default_train_options(azr_train_options* o)
+{
+    if (o) *o = TRAIN_OPT_DEFAULT;
+}
+
+extern "C" int azr_nn_train_set_options(azr_engine* h, const azr_train_options* o)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (!o) { h->err = "azr_nn_train_set_options: no options"; return AZR_E_INVALID_ARGUMENT; }
+    const char* why = nullptr;
+    for (float x : {o->lr, o->l2, o->decay_gamma, o->lr_min, o->clip_norm, o->ema_decay})
+        if (!std::isfinite(x)) why = "a value is not finite";
+    if (why) {}
+    else if (!(o->lr > 0.0f)) why = "lr must be > 0";
+    else if (o->l2 < 0.0f) why = "l2 must be >= 0";
+    else if (o->lr_schedule != AZR_LR_CONSTANT && o->lr_schedule != AZR_LR_COSINE && o->lr_schedule != AZR_LR_STEP) why = "unknown lr_schedule";
+    else if (o->warmup_steps < 0) why = "warmup_steps must be >= 0";
+    else if (o->lr_schedule == AZR_LR_COSINE && o->total_steps <= o->warmup_steps) why = "COSINE needs total_steps > warmup_steps";
+    else if (o->lr_schedule == AZR_LR_COSINE && (o->lr_min < 0.0f || o->lr_min > o->lr)) why = "COSINE needs lr_min in [0, lr]";
+    else if (o->lr_schedule == AZR_LR_STEP && o->decay_period < 1) why = "STEP needs decay_period >= 1";
+    else if (o->lr_schedule == AZR_LR_STEP && (o->decay_gamma <= 0.0f || o->decay_gamma > 1.0f)) why = "STEP needs decay_gamma in (0, 1]";
+    else if (o->clip_norm < 0.0f) why = "clip_norm must be 0 (off) or > 0";
+    else if (o->ema_decay < 0.0f || o->ema_decay >= 1.0f) why = "ema_decay must be 0 (off) or in (0, 1)";
+    if (why) { h->err = std::string("azr_nn_train_set_options: ") + why + "; the previous options stay in force"; return AZR_E_INVALID_ARGUMENT; }
+    h->train_opt = *o;
+    return AZR_OK;
+}
+
+extern "C" int azr_nn_train_get_options(azr_engine* h, azr_train_options* o)
+{
+    if (!h) return AZR_E_BAD_HANDLE;
+    if (!o) { h->err = "azr_nn_train_get_options: no destination"; return AZR_E_INVALID_ARGUMENT; }
+    *o = h->train_opt;
+    return AZR_OK;
+}
+
+extern "C" int azr_nn_train_stats(azr_engine* h, azr_train_stats* out)
+{
+    ENTER(h);
+    TrainCtx* c = ctx_of(h);
+    if (!c || c->step == 0) { h->err = "azr_nn_train_stats: no training step has run"; return AZR_E_STATE; }
+    if (!out) { h->err = "azr_nn_train_stats: no destination"; return AZR_E_INVALID_ARGUMENT; }
+    StatRow row;
+    float lr_t = 0.0f;
+    HIPCHK(h, hipMemcpy(&row, c->row, sizeof row, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&lr_t, c->lr, sizeof lr_t, hipMemcpyDeviceToHost));
+    out->step = c->step;
+    out->lr = c->last_default ? LR : row.lr;
+    out->lr_t = lr_t;
+    out->grad_norm = c->last_default ? NAN : row.norm;
+    out->clip_scale = c->last_default ? 1.0f : row.scale;
+    out->clipped_steps = row.clipped;
+    out->ema_steps = c->ema_steps;
+    return AZR_OK;
+}
+
+extern "C" int azr_nn_get_ema_weights(azr_engine* h, float* flat_host, size_t count)
+{
+    ENTER(h);
+    TrainCtx* c = ctx_of(h);
+    if (!c || !c->e) { h->err = "azr_nn_get_ema_weights: there is no EMA vector (no step has run with ema_decay > 0 since the optimiser state was created)"; return AZR_E_STATE; }
+    if (!flat_host || count != c->count) { h->err = "azr_nn_get_ema_weights: count must be azr_nn_param_count"; return AZR_E_INVALID_ARGUMENT; }
+    HIPCHK(h, hipMemcpy(flat_host, c->e, count * sizeof(float), hipMemcpyDeviceToHost));
     return AZR_OK;
 }
 

@@ -154,10 +154,26 @@ void Settings::init(int argc, char* argv[])
         {"cv-max-epochs", "[this build] cap on the epochs of one -m analysis fold (0 = no cap, the reference's loop)", std::to_string(CV_MAX_EPOCHS), false},
         {"help", "Display help", "0", true},
     };
+    // the optimiser step's options (azr_nn_train_set_options): a table of their own, next to the one above and not in it; parsed, listed
+    // and written to the settings file like its rows, range-checked behind them, then the rules that tie them to --lr-schedule
+    const std::vector<Opt> train_opts = {
+        real("lr", "[this build] optimiser step: base learning rate (above 0; the reference's graph has 1e-3)", "0.001", &Settings::LR, 0, 1e30, "is not a learning rate (a finite number above 0)", true),
+        real("l2", "[this build] optimiser step: L2 coefficient of the conv / dense kernels (at least 0; the reference's graph has 1e-3)", "0.001", &Settings::L2, 0, 1e30, "is not an L2 coefficient (a finite number, at least 0)"),
+        {"lr-schedule", "[this build] optimiser step: learning-rate schedule over Adam's step count: constant, cosine (from --lr at --lr-warmup down to --lr-min at --lr-steps) or step (times --lr-gamma every --lr-period steps)", LR_SCHEDULE, false},
+        whole("lr-warmup", "[this build] optimiser step: steps of linear warm-up to the scheduled rate (0 = none)", "0", &Settings::LR_WARMUP, 0, 2147483647.0, "is not a number of warm-up steps (a whole number, at least 0)"),
+        whole("lr-steps", "[this build] optimiser step: the step at which the cosine schedule reaches --lr-min (above --lr-warmup)", "0", &Settings::LR_STEPS, 0, 2147483647.0, "is not a step count (a whole number, at least 0)"),
+        real("lr-min", "[this build] optimiser step: floor of the cosine schedule (within [0, --lr])", "0", &Settings::LR_MIN, 0, 1e30, "is not a learning rate (a finite number, at least 0)"),
+        whole("lr-period", "[this build] optimiser step: steps between two decays of the step schedule (at least 1)", "1", &Settings::LR_PERIOD, 1, 2147483647.0, "is not a decay period (a whole number, at least 1)"),
+        real("lr-gamma", "[this build] optimiser step: factor of one decay of the step schedule (within (0, 1])", "1", &Settings::LR_GAMMA, 0, 1, "is not a decay factor (a number in (0, 1])", true),
+        real("clip-norm", "[this build] optimiser step: the gradient of the whole loss is scaled down to this global norm (tf.clip_by_global_norm; 0 = off)", "0", &Settings::CLIP_NORM, 0, 1e30, "is not a norm to clip to (a finite number above 0; 0 = off)"),
+        real("ema-decay", "[this build] optimiser step: decay d of an exponential moving average of the weights, e = d e + (1 - d) w after every step (within (0, 1); 0 = off)", "0", &Settings::EMA_DECAY, 0, 0.99999994, "is not an EMA decay (a number in (0, 1); 0 = off)"),
+        onoff("ema-play", "[this build] 1 = the averaged net of --ema-decay plays the compare games, is saved and generates the next games, while training goes on with the raw weights (0 = the raw net does)", "0", &Settings::EMA_PLAY),
+    };
     std::map<std::string, std::string> val;
     std::map<std::string, bool> given;
     auto find = [&](const std::string& n) -> const Opt* {
         for (auto& o : opts) if (n == o.name) return &o;
+        for (auto& o : train_opts) if (n == o.name) return &o;
         return nullptr;
     };
     for (int i = 1; i < argc; i++) {
@@ -189,7 +205,8 @@ void Settings::init(int argc, char* argv[])
     auto get = [&](const char* n) { return given.count(n) ? val[n] : find(n)->def; };
     if (given.count("help")) {
         printf("AlphaZero implementation for game Risk (MI355X-native hot path)\nUsage:\n  AlphaZero-Risk [OPTION...]\n\n");
-        for (auto& o : opts) printf("  %s%-22s %s (default: %s)\n", strlen(o.name) == 1 ? " -" : "--", o.name, o.desc, o.def.c_str());
+        for (const std::vector<Opt>* t : {(const std::vector<Opt>*)&opts, &train_opts})
+            for (auto& o : *t) printf("  %s%-22s %s (default: %s)\n", strlen(o.name) == 1 ? " -" : "--", o.name, o.desc, o.def.c_str());
         exit(0);
     }
     MODE = get("m");
@@ -332,6 +349,27 @@ void Settings::init(int argc, char* argv[])
         exit(2);
     }
     fill_through("");
+    for (auto& o : train_opts) fill(o);
+    LR_SCHEDULE = get("lr-schedule");
+    {   // what azr_nn_train_set_options would refuse, before an engine exists
+        const bool cosine = LR_SCHEDULE == "cosine", step = LR_SCHEDULE == "step";
+        if (!cosine && !step && LR_SCHEDULE != "constant") {
+            fprintf(stderr, "--lr-schedule: unknown schedule '%s' (constant|cosine|step)\n", LR_SCHEDULE.c_str());
+            exit(2);
+        }
+        if (cosine && LR_STEPS <= LR_WARMUP) {
+            fprintf(stderr, "--lr-steps: %d steps do not lie behind the warm-up's %d (--lr-schedule cosine needs --lr-steps above --lr-warmup)\n", LR_STEPS, LR_WARMUP);
+            exit(2);
+        }
+        if (cosine && LR_MIN > LR) {
+            fprintf(stderr, "--lr-min: %g is not a floor of the cosine schedule (a number in [0, --lr %g])\n", LR_MIN, LR);
+            exit(2);
+        }
+        if (EMA_PLAY == 1 && !(EMA_DECAY > 0.0f)) {
+            fprintf(stderr, "--ema-play: 1 needs --ema-decay above 0 (there is no averaged net to play)\n");
+            exit(2);
+        }
+    }
     CV_K = atoi(get("cvk").c_str());
     CV_MAX_EPOCHS = atoi(get("cv-max-epochs").c_str());
     DEVICE_MAP.clear();
@@ -347,7 +385,25 @@ void Settings::init(int argc, char* argv[])
     // `--lnt` and `--apbs` are parsed and never applied in the reference either
     mkdirs("log");
     std::ofstream out("log/settings.txt", std::ofstream::out);
-    for (auto& o : opts) out << o.name << "(" << o.desc << ")=" << (val.count(o.name) ? val[o.name] : o.def) << std::endl;
+    for (const std::vector<Opt>* t : {(const std::vector<Opt>*)&opts, &train_opts})
+        for (auto& o : *t) out << o.name << "(" << o.desc << ")=" << (val.count(o.name) ? val[o.name] : o.def) << std::endl;
+}
+
+azr_train_options Settings::trainOptions() const
+{
+    azr_train_options o;
+    azr_default_train_options(&o);
+    o.lr = LR; o.l2 = L2;
+    o.lr_schedule = LR_SCHEDULE == "cosine" ? AZR_LR_COSINE : LR_SCHEDULE == "step" ? AZR_LR_STEP : AZR_LR_CONSTANT;
+    o.warmup_steps = LR_WARMUP; o.total_steps = LR_STEPS; o.lr_min = LR_MIN;
+    o.decay_period = LR_PERIOD; o.decay_gamma = LR_GAMMA;
+    o.clip_norm = CLIP_NORM; o.ema_decay = EMA_DECAY;
+    return o;
+}
+
+bool Settings::trainOptionsDefault() const
+{
+    return LR == 1e-3f && L2 == 1e-3f && LR_SCHEDULE == "constant" && LR_WARMUP == 0 && CLIP_NORM == 0.0f && EMA_DECAY == 0.0f;
 }
 
 void Settings::toEngine(azr_settings& s, int device) const
@@ -487,6 +543,13 @@ Engine::Engine(const Settings& s, int device, int g) : games(g)
         h = nullptr;
         throw std::runtime_error("engine: " + msg);
     }
+    setTrainOptions(s);
+}
+// the optimiser step's options, once per engine: they stay on the handle
+void Engine::setTrainOptions(const Settings& s)
+{
+    const azr_train_options o = s.trainOptions();
+    check(azr_nn_train_set_options(h, &o), "train_set_options");
 }
 Engine::Engine(const Settings& s, int device, int g, int blocks, const std::string& dtype) : games(g)
 {
@@ -501,6 +564,7 @@ Engine::Engine(const Settings& s, int device, int g, int blocks, const std::stri
         h = nullptr;
         throw std::runtime_error("engine: " + msg);
     }
+    setTrainOptions(s);
 }
 Engine::~Engine() { if (h) azr_engine_destroy(h); }
 void Engine::check(int rc, const char* what) const
@@ -513,6 +577,7 @@ void Engine::check(int rc, const char* what) const
 void AlphaZeroNNId::loadCheckpoint(const std::string& path)
 {
     struct stat st;
+    rawWeights.clear();   // (the weights of a training phase are replaced: there is nothing to put back)
     if (stat(path.c_str(), &st) == 0) {
         engine->check(azr_nn_load(engine->h, path.c_str()), "loadCheckpoint");
         printf("Loaded checkpoint %s\n", path.c_str());
@@ -565,6 +630,7 @@ void AlphaZeroNNId::train(const std::vector<NNTrainData>& trainData, int epochs)
         memcpy(r + 93, trainData[i].out.policy.data(), 4 * AZR_MOVES);
     }
     printf("Started training\n");
+    trainRaw();
     std::vector<float> lp(std::max(epochs, 1)), lv(std::max(epochs, 1));
     auto t0 = std::chrono::steady_clock::now();
     engine->check(azr_nn_train(engine->h, buf.data(), trainData.size(), epochs, SETTINGS.BATCH_SIZE, &g_shuffle_state, lp.data(), lv.data()),
@@ -577,6 +643,37 @@ void AlphaZeroNNId::train(const std::vector<NNTrainData>& trainData, int epochs)
     if (SETTINGS.LOG_NN_TRAINING) logFile("log/azr-nn-training-log.txt") << std::endl;
     const size_t steps = (size_t)epochs * (trainData.size() / SETTINGS.BATCH_SIZE);
     printf("Trained %zu minibatch steps of %d in %.2f s (%.1f ms/step)\n", steps, SETTINGS.BATCH_SIZE, dt, steps ? 1e3 * dt / steps : 0.0);
+    if (steps) { logOptimiser(steps); playAveraged(); }
+}
+
+void AlphaZeroNNId::logOptimiser(size_t steps)
+{
+    if (SETTINGS.trainOptionsDefault()) return;
+    azr_train_stats st;
+    engine->check(azr_nn_train_stats(engine->h, &st), "train_stats");
+    char norm[32] = "n/a";
+    if (!std::isnan(st.grad_norm)) snprintf(norm, sizeof norm, "%.6g", st.grad_norm);
+    printf("Optimiser step: lr %.6g, grad norm %s, clipped %lld/%lld steps   [%zu steps in this phase]%s\n", st.lr, norm, (long long)st.clipped_steps,
+           (long long)st.step, steps, SETTINGS.EMA_PLAY ? "   [the averaged net plays]" : "");
+}
+
+// --ema-play 1, behind a training phase: keep the raw weights, hold the averaged ones (azr_nn_set_weights keeps the training context)
+void AlphaZeroNNId::playAveraged()
+{
+    if (!SETTINGS.EMA_PLAY) return;
+    const size_t n = azr_nn_param_count(SETTINGS.BLOCKS);
+    rawWeights.resize(n);
+    std::vector<float> ema(n);
+    engine->check(azr_nn_get_weights(engine->h, rawWeights.data(), n), "get_weights");
+    engine->check(azr_nn_get_ema_weights(engine->h, ema.data(), n), "get_ema_weights");
+    engine->check(azr_nn_set_weights(engine->h, ema.data(), n), "set_weights");
+}
+// ... and in front of the next one: training goes on with the raw weights
+void AlphaZeroNNId::trainRaw()
+{
+    if (rawWeights.empty()) return;
+    engine->check(azr_nn_set_weights(engine->h, rawWeights.data(), rawWeights.size()), "set_weights");
+    rawWeights.clear();
 }
 
 // ---- cross-validation (`-m analysis`) ---------------------------------------------------------------------------------
@@ -641,6 +738,7 @@ void AlphaZeroNNId::trainCrossValidation(const std::vector<NNTrainData>& trainDa
                 std::shuffle(validationSamples.begin(), validationSamples.end(), eng);
                 g_shuffle_state = engineState(eng);
                 printf("Training Loss Policy %f Value: %f\n", lp, lv);
+                if (trainingSamples.size() >= (size_t)SETTINGS.BATCH_SIZE) logOptimiser(trainingSamples.size() / SETTINGS.BATCH_SIZE);
                 saveCheckpoint(SETTINGS.DEFAULT_CHECKPOINT_DIR + "/cross-validation-" + std::to_string(vi) + "-" + std::to_string(e) + " .bin");
                 logFile("log/azr-nn-training-log.txt") << lp << "," << lv;
             }

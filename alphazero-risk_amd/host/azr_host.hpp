@@ -100,6 +100,18 @@ public:
     int ARENA_GUMBEL_TREE2 = 0;
     int CV_K = 10;                       // --cvk: folds of `-m analysis` (the reference hard-codes trainCrossValidation(data, 10))
     int CV_MAX_EPOCHS = 0;               // --cv-max-epochs: cap on the epochs of one fold (0 = none: the reference's unbounded loop)
+    // the optimiser step's options (azr_nn_train_set_options; a flag table of their own in Settings::init), set on every engine once
+    float LR = 1e-3f, L2 = 1e-3f;        // --lr, --l2: base learning rate and L2 coefficient (the reference's graph: 1e-3 both)
+    std::string LR_SCHEDULE = "constant";   // --lr-schedule: constant | cosine | step
+    int LR_WARMUP = 0, LR_STEPS = 0;     // --lr-warmup, --lr-steps: steps of linear warm-up; the step at which the cosine schedule reaches --lr-min
+    float LR_MIN = 0.0f;                 // --lr-min: floor of the cosine schedule
+    int LR_PERIOD = 1;                   // --lr-period, --lr-gamma: the step schedule multiplies the rate by gamma every so many steps
+    float LR_GAMMA = 1.0f;
+    float CLIP_NORM = 0.0f;              // --clip-norm: global-norm clipping of the gradient of the whole loss (0 = off)
+    float EMA_DECAY = 0.0f;              // --ema-decay: decay of the exponential moving average of the weights (0 = off)
+    int EMA_PLAY = 0;                    // --ema-play: 1 = the averaged net plays the compare games, is saved and generates; training goes on with the raw weights
+    azr_train_options trainOptions() const;
+    bool trainOptionsDefault() const;    // every option at its default: the reference's step, nothing to log
 
     int deviceOf(int gpu) const { return DEVICE_MAP.empty() ? gpu : DEVICE_MAP.at(gpu); }
     int arenaMirrorMode() const { return !MIRROR_GAMES ? AZR_MIRROR_OFF : CONCURRENT_PAIR_HALVES ? AZR_MIRROR_CONCURRENT : AZR_MIRROR_SEQUENTIAL; }
@@ -175,6 +187,7 @@ public:
     Engine(const Settings& s, int device, int games, int blocks, const std::string& dtype);   // a net shape other than s.BLOCKS / s.NET_DTYPE
     ~Engine();
     void check(int rc, const char* what) const;
+    void setTrainOptions(const Settings& s);
 };
 
 class AlphaZeroNNId {  // alphazero_gpu_cluster.h:14-47
@@ -192,6 +205,12 @@ public:
     // AlphaZeroNN::trainCrossValidation (alphazero_nn.cpp:412-575): k folds, each a fresh net trained epoch by epoch
     // (azr_nn_train, one epoch per call) and validated after every epoch (azr_nn_validate: inference-mode BN, no update)
     void trainCrossValidation(const std::vector<NNTrainData>& trainData, int k);
+    // --ema-play 1: behind a training phase the engine holds the averaged weights (they play, are saved and handed on) and these are
+    // the raw ones, put back in front of the next training phase; a checkpoint load replaces both
+    std::vector<float> rawWeights;
+    void logOptimiser(size_t steps);    // one line per training phase: the last rate, the gradient norm, the clipped steps
+    void playAveraged();
+    void trainRaw();
 };
 
 class AlphaZeroNNGroup {  // alphazero_gpu_cluster.h:76-95: the same net on every GPU

@@ -93,6 +93,77 @@ SELFPLAY_OPTIONS = (
 )
 SELFPLAY_FLAGS = {f.name[2:].replace("-", "_"): f for _, flags in SELFPLAY_OPTIONS for f in flags}   # by argparse's attribute name
 
+# The options of the optimiser step (azr_nn_train_set_options), a table of their own next to the self-play table: the field of
+# azr_train_options each flag sets.  --lr-schedule is a name (argparse's choices), --ema-play is not a field: it says which net plays.
+TRAIN_OPTIONS = (
+    ("lr", Flag("--lr", float, 1e-3, "[this build] optimiser step: base learning rate (above 0; the reference's 1e-3)")),
+    ("l2", Flag("--l2", float, 1e-3, "[this build] optimiser step: L2 coefficient of the conv / dense kernels (at least 0; the reference's 1e-3)")),
+    ("lr_schedule", Flag("--lr-schedule", str, "constant", "[this build] optimiser step: learning-rate schedule over Adam's step count: constant, cosine "
+                         "(from --lr at --lr-warmup down to --lr-min at --lr-steps) or step (times --lr-gamma every --lr-period steps)")),
+    ("warmup_steps", Flag("--lr-warmup", int, 0, "[this build] optimiser step: steps of linear warm-up to the scheduled rate (0 = none)")),
+    ("total_steps", Flag("--lr-steps", int, 0, "[this build] optimiser step: the step at which the cosine schedule reaches --lr-min (above --lr-warmup)")),
+    ("lr_min", Flag("--lr-min", float, 0.0, "[this build] optimiser step: floor of the cosine schedule (within [0, --lr])")),
+    ("decay_period", Flag("--lr-period", int, 1, "[this build] optimiser step: steps between two decays of the step schedule (at least 1)")),
+    ("decay_gamma", Flag("--lr-gamma", float, 1.0, "[this build] optimiser step: factor of one decay of the step schedule (within (0, 1])")),
+    ("clip_norm", Flag("--clip-norm", float, 0.0, "[this build] optimiser step: the gradient of the whole loss is scaled down to this global norm "
+                       "(tf.clip_by_global_norm; 0 = off)")),
+    ("ema_decay", Flag("--ema-decay", float, 0.0, "[this build] optimiser step: decay d of an exponential moving average of the weights, "
+                       "e = d e + (1 - d) w after every step (within (0, 1); 0 = off)")),
+)
+EMA_PLAY = Flag("--ema-play", int, 0, "[this build] 1 = the averaged net of --ema-decay plays the compare games, is saved and generates the next "
+                "games, while training goes on with the raw weights (0 = the raw net does)")
+
+
+def add_train_flags(ap):
+    for _, f in TRAIN_OPTIONS:
+        ap.add_argument(f.name, type=f.type, default=f.default, help=f.help, **(dict(choices=sorted(P.LR_SCHEDULES)) if f.type is str else {}))
+    ap.add_argument(EMA_PLAY.name, type=EMA_PLAY.type, default=EMA_PLAY.default, help=EMA_PLAY.help)
+
+
+def train_options_of(a):
+    """(the keyword arguments of Engine.train_set_options out of the parsed flags — a caller's namespace may lack them: the defaults —,
+    --ema-play)"""
+    kw = {field: getattr(a, f.name[2:].replace("-", "_"), f.default) for field, f in TRAIN_OPTIONS}
+    return kw, getattr(a, "ema_play", 0)
+
+
+def train_options_error(kw, ema_play=0):
+    """what azr_nn_train_set_options would refuse, as "--flag: value reason" (None: it takes them) — checked before an engine exists"""
+    name = {field: f.name for field, f in TRAIN_OPTIONS}
+    bad = lambda field, why: f"{name[field]}: {kw[field]} {why}"   # noqa: E731
+    for field in ("lr", "l2", "lr_min", "decay_gamma", "clip_norm", "ema_decay"):
+        if not np.isfinite(kw[field]):
+            return bad(field, "is not a finite number")
+    cosine, step = kw["lr_schedule"] == "cosine", kw["lr_schedule"] == "step"
+    if not kw["lr"] > 0:
+        return bad("lr", "is not a learning rate (a number above 0)")
+    if kw["l2"] < 0:
+        return bad("l2", "is not an L2 coefficient (a number of at least 0)")
+    if kw["warmup_steps"] < 0:
+        return bad("warmup_steps", "is not a number of warm-up steps (a whole number of at least 0)")
+    if cosine and kw["total_steps"] <= kw["warmup_steps"]:
+        return bad("total_steps", f"steps do not lie behind the warm-up's {kw['warmup_steps']} (--lr-schedule cosine needs --lr-steps above --lr-warmup)")
+    if cosine and not 0 <= kw["lr_min"] <= kw["lr"]:
+        return bad("lr_min", f"is not a floor of the cosine schedule (a number in [0, --lr {kw['lr']:g}])")
+    if step and kw["decay_period"] < 1:
+        return bad("decay_period", "is not a decay period (a whole number of at least 1)")
+    if step and not 0 < kw["decay_gamma"] <= 1:
+        return bad("decay_gamma", "is not a decay factor (a number in (0, 1])")
+    if kw["clip_norm"] < 0:
+        return bad("clip_norm", "is not a norm to clip to (a number above 0; 0 = off)")
+    if not 0 <= kw["ema_decay"] < 1:
+        return bad("ema_decay", "is not an EMA decay (a number in (0, 1); 0 = off)")
+    if ema_play not in (0, 1) or (ema_play == 1 and not kw["ema_decay"] > 0):
+        return f"{EMA_PLAY.name}: {ema_play} is neither 0 nor 1, or is 1 without --ema-decay above 0"
+    return None
+
+
+def optimiser_line(st, steps):
+    """the log line of a training phase: the last step's scheduled rate and gradient norm (computed only while clipping is on), and how
+    many of the optimiser state's steps were clipped"""
+    norm = "n/a" if np.isnan(st["grad_norm"]) else f"{st['grad_norm']:.6g}"
+    return f"Optimiser step: lr {st['lr']:.6g}, grad norm {norm}, clipped {st['clipped_steps']}/{st['step']} steps   [{steps} steps in this phase]"
+
 
 # The search of the arena games (compare and benchmark games; the generated games have SELFPLAY_OPTIONS): a Gumbel search with sequential
 # halving per side, deterministic.  m1 / tree1: player 1, the new net of the compare games and the AlphaZero side of the benchmark games;
@@ -270,6 +341,12 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         dist.barrier()
     for e in (new, gen):
         e.load(latest)
+    # the optimiser step's options: set once, they stay on the handle.  --ema-play 1: `new` holds the averaged net while it plays, is saved
+    # and handed to `gen`, and gets its raw weights back (raw) before it trains again; set_weights keeps the training context
+    train_kw, ema_play = train_options_of(a)
+    train_opts_on = train_kw != {field: f.default for field, f in TRAIN_OPTIONS}
+    new.train_set_options(**train_kw)
+    raw = None
     shuffle_state = a.seed % 2147483646 + 1   # raw minstd_rand0 state standing in for the reference's global RNG
     records = load_training_samples("data/training_samples.bin")   # trainStorage.loadTrainingSamples(DEFAULT_SAMPLES)
     old_game_index = 0
@@ -338,6 +415,10 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         # opt-in until a run on a multi-GPU node is on record.
         dp_flag = getattr(a, "dp", 0)
         dp = dist is not None and dp_flag == 1 and a.bs % world == 0 and a.bs // world >= 2
+        if raw is not None:
+            new.set_weights(raw)
+            raw = None
+        trained = False
         if dp:
             # data-parallel optimiser step: every rank takes 1/world of each minibatch (same shuffle stream everywhere);
             # batch statistics, losses and the gradient vector are all-reduced (RCCL over xGMI), every rank takes the
@@ -355,15 +436,23 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
                                                    batch_size=a.bs, rng_state=shuffle_state)
                 how = ("torch.distributed all_reduce on device buffers, backend " + dist.get_backend()) if cdev != "cpu" else "host copies (gloo rehearsal)"
             hist = [h for h in hist if not np.isnan(h[0])]
+            trained = bool(hist)
             log(f"Data-parallel optimiser step: {how}")
             if rank == 0:
                 nn_log.write(nn_training_line(hist)); nn_log.flush()
+            if trained and ema_play:   # every rank holds the same raw and averaged weights
+                raw = new.get_weights()
+                new.set_weights(new.get_ema_weights())
         else:
             if rank == 0:   # AlphaZeroNNGroup::train: the first GPU trains (alphazero_gpu_cluster.cpp:221-231)
                 hist, shuffle_state = new.train(records, a.e, batch_size=a.bs, rng_state=shuffle_state)
                 hist = [h for h in hist if not np.isnan(h[0])]
+                trained = bool(hist)
                 nn_log.write(nn_training_line(hist)); nn_log.flush()
-            if dist is not None:   # ... and the others receive its weights
+                if trained and ema_play:
+                    raw = new.get_weights()
+                    new.set_weights(new.get_ema_weights())
+            if dist is not None:   # ... and the others receive its weights (--ema-play 1: the averaged ones)
                 w = shard_mod.broadcast_flat(new.get_weights(), dist, src=0, device=cdev)
                 log(f"Weight broadcast from rank 0: backend {dist.get_backend()}, tensor on {cdev}")
                 if rank != 0:
@@ -371,6 +460,8 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         steps = a.e * (len(records) // a.bs)
         if hist:
             log(f"Loss Policy / Value: {hist[-1][0]:f} / {hist[-1][1]:f}   [{steps} steps, {1e3 * (time.time() - t0) / max(steps, 1):.1f} ms/step]")
+        if trained and train_opts_on:
+            log(optimiser_line(new.train_stats(), steps) + ("   [the averaged net plays]" if ema_play else ""))
         # ---- updateIfImprovement (alphazero_trainer.cpp:134-190)
         wd.arm("compare and benchmark games")
         improved = True
@@ -408,6 +499,7 @@ def learn(a, log=print, dist=None, rank=0, world=1, cdev="cpu"):
         else:
             log("Model did not improve\nModel reverted back old")
             new.load(latest)
+            raw = None
         wd.disarm()
         summary.append(dict(iteration=it, samples=len(records), losses=hist, arena=gr, improved=improved))
     # saveTrainingSamples (reference writer layout: 8-byte count + 265-byte records)
@@ -446,6 +538,7 @@ def main():
     ap.add_argument("--arena-gumbel-tree", type=int, default=0,
                     help="[this build] under --arena-gumbel-m, player 1's selection below the root: 1 = by the improved policy of each node (0 = PUCT there)")
     ap.add_argument("--arena-gumbel-tree2", type=int, default=None, help="[this build] the same for player 2 (default: --arena-gumbel-tree)")
+    add_train_flags(ap)   # the optimiser step's options: a table of their own (TRAIN_OPTIONS)
     ap.add_argument("--pair-halves", type=int, default=1,
                     help="mirrored arena pairs: 1 = both games of a pair at the same time on two slots (AZR_MIRROR_CONCURRENT), "
                          "0 = one after the other on one slot (the reference's thread-per-pair form)")
@@ -476,6 +569,8 @@ def main():
     if a.gumbel_tree == 1 and a.gumbel_m == 0:
         ap.error("--gumbel-tree: the selection below the root needs the Gumbel root search (--gumbel-m above 0)")
     check("resign_streak", "resign_q", "resign_holdout", "resign_seed")
+    if train_options_error(*train_options_of(a)):
+        ap.error(train_options_error(*train_options_of(a)))
     if a.arena_gumbel_m2 is None:
         a.arena_gumbel_m2 = a.arena_gumbel_m
     if a.arena_gumbel_tree2 is None:

@@ -168,6 +168,57 @@ int azr_nn_train_batch(azr_engine* h, const void* rec265_host, int n, float* los
 int azr_nn_train_grads(azr_engine* h, float* flat_host, size_t count);
 /* drop the optimiser state and the training buffers */
 int azr_nn_train_reset(azr_engine* h);
+/* Options of the optimiser step: learning-rate schedule, global-norm gradient clipping, an exponential moving average (EMA) of the
+ * weights.  The defaults are the reference's graph (build_graph.py: Adam at a constant 1e-3, L2 1e-3, nothing else), and with every
+ * option at its default the step launches the kernels it launched before the options existed.
+ * Lifetime: the options live on the handle — they survive azr_nn_train_reset, a rebuild of the training context and a failed health
+ * check — and are read once when azr_nn_train, azr_nn_train_dp or azr_nn_train_batch is entered; a running call never sees a setter.
+ * Schedule: evaluated on the device, in double, from Adam's step count t (1-based behind the increment; azr_nn_train_reset restarts it
+ * at 0), so azr_nn_train's queue of steps needs no host round trip:
+ *   warm(t) = W > 0 ? min(1, t / W) : 1                                         (W = warmup_steps)
+ *   CONSTANT: f = 1
+ *   COSINE:   p = clamp((t - W) / (N - W), 0, 1), f = r + (1 - r) * 0.5 * (1 + cos(pi * p)), r = lr_min / lr     (N = total_steps)
+ *   STEP:     f = decay_gamma ^ floor((t - 1) / decay_period)
+ *   lr_eff = lr * warm * f,   lr_t = (float)(lr_eff * sqrt(1 - b2^t) / (1 - b1^t))    (the bias-corrected rate Adam multiplies by)
+ * Clipping (tf.clip_by_global_norm on the gradient of the whole loss): g^ = g + 2 * l2 * w on the conv / dense kernels, g^ = g on BN
+ * gamma / beta and biases, the BN moving statistics take no part; norm = sqrt(sum g^2), s = clip_norm / max(norm, clip_norm), Adam
+ * sees s * g^.  The sum is in double, atomic-free and in a fixed order: two runs give the same bits, and under azr_nn_train_dp it
+ * runs behind the gradient all-reduce, so every rank computes the same bits.  azr_nn_train_grads keeps returning the raw g.
+ * EMA: the first step taken with ema_decay = d > 0 creates the vector as a copy of the weights from before that step; every step
+ * then sets e = d * e + (1 - d) * w_new on the trained slots and e = w_new on the BN moving statistics (averages already).  The
+ * vector is optimiser state: it lives through a rebuild of the training context as Adam's moments do, and azr_nn_train_reset and a
+ * failed health check drop it.  azr_nn_get_ema_weights returns it as an AZRW vector that azr_nn_set_weights accepts on any handle.
+ * azr_nn_train_set_options: AZR_E_INVALID_ARGUMENT, with a reason in azr_last_error and the previous options still in place, for a
+ * value that is not finite, lr <= 0, l2 < 0, an unknown schedule, warmup_steps < 0, COSINE with total_steps <= warmup_steps or lr_min
+ * outside [0, lr], STEP with decay_period < 1 or decay_gamma outside (0, 1], clip_norm < 0, ema_decay outside [0, 1). */
+enum { AZR_LR_CONSTANT = 0, AZR_LR_COSINE = 1, AZR_LR_STEP = 2 };
+typedef struct azr_train_options {
+    float   lr;            /* base learning rate, default 1e-3f (build_graph.py) */
+    float   l2;            /* L2 coefficient of the conv / dense kernels, default 1e-3f */
+    int32_t lr_schedule;   /* AZR_LR_*, default CONSTANT */
+    int32_t warmup_steps;  /* W >= 0, default 0 */
+    int32_t total_steps;   /* COSINE: N > W, the step at which lr_min is reached */
+    int32_t decay_period;  /* STEP: every so many steps ... (>= 1, default 1) */
+    float   decay_gamma;   /* ... the rate is multiplied by gamma, in (0, 1], default 1 */
+    float   lr_min;        /* COSINE floor, in [0, lr] */
+    float   clip_norm;     /* global-norm clipping, 0 = off, else > 0 */
+    float   ema_decay;     /* d in (0, 1), 0 = off */
+} azr_train_options;
+typedef struct azr_train_stats {   /* of the LAST step taken on the handle */
+    int64_t step;          /* Adam step count t */
+    float   lr, lr_t;      /* scheduled rate, and the bias-corrected rate Adam used */
+    float   grad_norm;     /* NaN where it was not computed (clipping off) */
+    float   clip_scale;    /* 1 where nothing was clipped */
+    int64_t clipped_steps; /* steps with clip_scale < 1 since the optimiser state was created */
+    int64_t ema_steps;     /* steps folded into the EMA vector */
+} azr_train_stats;
+void azr_default_train_options(azr_train_options* o);
+int azr_nn_train_set_options(azr_engine* h, const azr_train_options* o);
+int azr_nn_train_get_options(azr_engine* h, azr_train_options* o);
+/* AZR_E_STATE before the first step (and behind azr_nn_train_reset or a failed health check) */
+int azr_nn_train_stats(azr_engine* h, azr_train_stats* out);
+/* AZR_E_STATE while there is no EMA vector; count = azr_nn_param_count */
+int azr_nn_get_ema_weights(azr_engine* h, float* flat_host, size_t count);
 
 /* ---- search: AlphaZeroMCTS / StateSimulationsStorage (alphazero_mcts.h:55-95) ---------------------------- */
 int azr_mcts_clear(azr_engine* h);   /* clearNodes (alphazero_mcts.cpp:223-227), all games */

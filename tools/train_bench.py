@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the native optimiser step (azr_nn_train) at the reference's training shape: BATCH_SIZE 512, B residual blocks.
-    python tools/train_bench.py [--blocks 20] [--bs 512] [--batches 8] [--epochs 2]
-Prints ms per minibatch step and the achieved fp32 FLOP rate (3 x forward FLOPs of the dense-padded GEMMs)."""
+    python tools/train_bench.py [--blocks 20] [--bs 512] [--batches 8] [--epochs 2] [--clip-norm 1] [--ema-decay 0.999]
+Prints ms per minibatch step and the achieved fp32 FLOP rate (3 x forward FLOPs of the dense-padded GEMMs).  With --clip-norm or
+--ema-decay (azr_nn_train_set_options) it then times the step with the options off and on, alternating in the same run."""
 import argparse
 import importlib
 import os
@@ -31,6 +32,9 @@ def main():
     ap.add_argument("--native", action="store_true",
                     help="with --dp-world: the engine's own RCCL communicator (one rank, AZR_DP_LOOPBACK=1) instead of the callback: the all-reduces "
                          "are in-stream ncclAllReduce calls, as on a real multi-GPU run")
+    ap.add_argument("--clip-norm", type=float, default=0.0, help="global-norm gradient clipping of the timed step (0 = off)")
+    ap.add_argument("--ema-decay", type=float, default=0.0, help="EMA of the weights in the timed step (0 = off)")
+    ap.add_argument("--rounds", type=int, default=5, help="with --clip-norm / --ema-decay: rounds of (options off, options on), timed alternately")
     a = ap.parse_args()
     if a.native:
         os.environ["AZR_DP_LOOPBACK"] = "1"
@@ -78,6 +82,25 @@ def main():
         return
     print(f"blocks={a.blocks} bs={a.bs}: {1e3 * dt / steps:.2f} ms/step, {flop * steps / dt / 1e12:.1f} TFLOP/s fp32 (dense-padded GEMM work), "
           f"losses {hist}")
+    if a.clip_norm > 0 or a.ema_decay > 0:
+        # the same engine, the same records: default options (t_tick_lr + t_adam) against the options given (norm, schedule kernel,
+        # t_adam_opt), one after the other, `rounds` times
+        on = dict(clip_norm=a.clip_norm, ema_decay=a.ema_decay)
+        eng.train_set_options(**on)
+        run(rec[:a.bs], 1)   # the EMA vector is created by the first step that has it
+        ms = {"off": [], "on": []}
+        for _ in range(a.rounds):
+            for name, kw in (("off", {}), ("on", on)):
+                eng.train_set_options(**kw)
+                t0 = time.time()
+                run(rec, a.epochs)
+                ms[name].append(1e3 * (time.time() - t0) / steps)
+        st = eng.train_stats()
+        for name in ("off", "on"):
+            print(f"options {name}: ms/step per round {' '.join('%.3f' % x for x in ms[name])}, median {np.median(ms[name]):.3f}")
+        print(f"options on = clip_norm {a.clip_norm:g}, ema_decay {a.ema_decay:g}: {np.median(ms['on']) - np.median(ms['off']):+.3f} ms/step "
+              f"(medians of {a.rounds}); last step: grad norm {st['grad_norm']:.4g}, clip scale {st['clip_scale']:.4g}, "
+              f"{st['clipped_steps']} of {st['step']} steps clipped")
     if a.torch:
         print(f"PyTorch-ROCm autograd (MIOpen fp32), same graph and batch: {1e3 * torch_time(a, eng, rec):.2f} ms/step")
 
