@@ -27,10 +27,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <rccl/rccl.h>   // types and enumerators only: the library is bound at run time (rccl_api below)
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <random>
 #include <sstream>
@@ -306,43 +308,78 @@ AZR_HOOK_FLAG g_conv_q = true;       // t_conv_q for batches of up to 128 record
 // (AZR_TRAIN_FUSE_APPLY=0: separate kernels; same bits)
 AZR_HOOK_FLAG g_fuse_apply = true;
 
-// The kernel choice of the step, derived once per training context (ctx_ensure: the hooks are read and the batch size is known there);
-// train_step, forward_tower and azr_nn_validate read it.
+
+// The kernel choice of the step, derived once per set of slabs (ctx_ensure: the hooks are read and the batch size is known there);
+// everything below ctx_ensure reads the plan and no switch.
 struct Plan {
     bool sb = false;      // split-bf16 conv GEMMs (the stem, K = 144, and row counts that are no multiple of the k-tile stay on the fp32 MFMA)
     bool f16 = false;     // forward conv: fp16 pairs, 3 passes
     bool fap = false;     // layer l's normalise step is computed in the staging path of the forward conv of layer l + 1
     bool convq = false;   // small batches (a rank's share of a data-parallel minibatch): t_conv_q, one board x 64 channels per block
+    bool wg5 = true;      // weight gradient: t_wgrad_g5 (the hook's other choice: t_wgrad_rs)
+    bool fuse = false;    // split path: batch statistics in the forward conv's epilogue, BN-backward stage 1 in the backward-data conv's
+    bool bap = false;     // ... and t_bn_bwd_apply computed in the backward-data conv's staging path: the product's backward pass
 };
 
-struct TrainCtx {
-    int BS = 0, blocks = 0, M = 0, L = 0, R = 0, nz = 0, kchunk = 0;
+// ---- Two lifetimes.  Slabs: everything sized by the batch (BS / M / R / nz / wg_*), with those numbers and the plan; freed and rebuilt
+// when a call comes with another batch size (a validation pass behind a training step, data-parallel shares of another size).
+// TrainState: the optimiser state and everything sized by the net's depth alone; one per handle, created by the first training or
+// validation call, freed by azr_nn_train_reset, a failed health check and engine destroy.  A rebuild of the slabs never touches it.
+struct Slabs {
+    int BS = 0, M = 0, R = 0, nz = 0, kchunk = 0;
     Plan plan;
     int wg_slices = 0;                       // weight gradient: slices (split-K units of whole boards)
     int wg_bps = 0;                          // ... boards per slice
     int wg_parts = 0;                        // ... split-K partials that reach memory (t_wgrad_g5: one per four slices, summed in the block)
-    size_t count = 0;
-    long step = 0;
-    float *g = nullptr, *m = nullptr, *v = nullptr;
-    uint8_t* kind = nullptr;
-    float *X0 = nullptr, *col0 = nullptr, *wpad = nullptr, *gpad = nullptr;
+    float *X0 = nullptr, *col0 = nullptr;
     float *Y = nullptr, *A = nullptr;        // [L][M][256]
     float *G = nullptr, *DS = nullptr, *DT = nullptr, *dY = nullptr;
-    float *mean = nullptr, *istd = nullptr;  // [L][256]
-    float* sums = nullptr;                   // [2][256]
     double* part = nullptr;                  // [R][2*NG][256]
     float* wpart = nullptr;                  // split-K partials [nz][KC][256]
     uint16_t *ap[3] = {nullptr, nullptr, nullptr}, *dyp[2] = {nullptr, nullptr};          // bf16 parts of activations / gradients
+    uint16_t* dyp2[2] = {nullptr, nullptr};  // the dY parts of odd layers (a second set: the chain runs ahead of the weight-gradient branch)
     uint16_t* af[2] = {nullptr, nullptr};    // fp16 pair (hi, lo) of the newest post-activation: the next forward conv's operand
-    uint16_t *wpf[3] = {nullptr, nullptr, nullptr}, *wpb[2] = {nullptr, nullptr};        // packed kernels: forward / backward-data view
-    float *pv0 = nullptr, *dpv = nullptr, *hstat = nullptr, *fpi = nullptr, *fv = nullptr, *h1 = nullptr, *vout = nullptr,
-          *prob = nullptr, *lossb = nullptr, *hpart = nullptr, *cpart = nullptr, *loss = nullptr;
-    int* cur = nullptr;    // device: {minibatch offset in perm, Adam step count, this rank's offset inside the minibatch}
-    // data-parallel step (azr_nn_train_dp): this rank's shard of every minibatch; sums that span the batch are all-reduced
+    float *pv0 = nullptr, *dpv = nullptr, *fpi = nullptr, *fv = nullptr, *h1 = nullptr, *vout = nullptr, *prob = nullptr, *lossb = nullptr,
+          *hpart = nullptr, *cpart = nullptr;
+    uint8_t* in88 = nullptr;
+    float *pit = nullptr, *zt = nullptr;
+    std::vector<void*> allocs;
+
+    ~Slabs() { for (void* p : allocs) hipFree(p); }   // (held by a unique_ptr, never copied)
+    // views of layer l: pre-BN conv output, post-activation and its bf16 parts (the third part only until the next forward conv has read it)
+    size_t act() const { return (size_t)M * NF; }
+    float* Yl(int l) const { return Y + act() * l; }
+    float* Al(int l) const { return A + act() * l; }
+    Parts Ap(int l) const { return Parts{{ap[0] + act() * l, ap[1] + act() * l, ap[2]}}; }
+};
+
+// data-parallel step (azr_nn_train_dp): this rank's shard of every minibatch; sums that span the batch are all-reduced.  A call sets
+// the link and resets it by assignment (a data-parallel call that failed half-way must not linger).
+struct DpLink {
     int world = 1, rank = 0;
     azr_allreduce_fn ar = nullptr;
     void* ar_ctx = nullptr;
     bool native = false;       // the sums go through the handle's own RCCL communicator, in stream order (azr_dp_init)
+    // the data-parallel code path (a callback was supplied, or the handle has a communicator), also with one rank
+    bool dp() const { return ar != nullptr || native; }
+};
+
+// the device cursor `cur` of t_gather, the tick kernels and t_pack_w (the kernels index it as an int*)
+enum { CUR_OFFSET = 0, CUR_STEP = 1, CUR_RANK = 2, CUR_RANGE = 3, CUR_N = 4 };   // minibatch offset in perm, Adam step count, this rank's offset inside the minibatch, range flag
+
+struct TrainState {
+    int blocks = 0, L = 0;
+    size_t count = 0;
+    long step = 0;
+    float *g = nullptr, *m = nullptr, *v = nullptr;   // g: cleared once, here — the slots the backward pass never writes stay 0
+    uint8_t* kind = nullptr;
+    float *wpad = nullptr, *gpad = nullptr;
+    float *mean = nullptr, *istd = nullptr;  // [L][256]
+    float* sums = nullptr;                   // [2][256]
+    uint16_t *wpf[3] = {nullptr, nullptr, nullptr}, *wpb[2] = {nullptr, nullptr};        // packed kernels: forward / backward-data view
+    float *hstat = nullptr, *loss = nullptr;
+    int* cur = nullptr;        // device: [CUR_N]
+    DpLink link;
     double* red = nullptr;     // [2 * NG][256] reduced BN partials
     double* hsum = nullptr;    // [6] head BN sums
     float* lr = nullptr;   // device: this step's bias-corrected learning rate
@@ -360,26 +397,23 @@ struct TrainCtx {
     hipStream_t side = nullptr;
     hipEvent_t ev_conv[2] = {nullptr, nullptr};   // main -> side: the backward-data conv of a layer has left its dY parts (by layer parity)
     hipEvent_t ev_wg[2] = {nullptr, nullptr};     // side -> main: that layer's weight gradient has read them
-    uint16_t* dyp2[2] = {nullptr, nullptr};       // the dY parts of odd layers (a second set: the chain runs ahead of the branch)
+    // grow-only (grow): the call's records and their order, and the validation pass's buffer (ValHdr)
     uint8_t* rec = nullptr;
-    size_t rec_cap = 0;
     int* perm = nullptr;
-    size_t perm_cap = 0;
-    uint8_t* in88 = nullptr;
-    float *pit = nullptr, *zt = nullptr;
-    // validation pass (azr_nn_validate): {loss sums[2], range flag, pad, gather offsets cur[4]} | batch means [nb][2] | per-record terms [nb * BS][2]
     float* vbuf = nullptr;
-    size_t vbuf_cap = 0;
+    size_t rec_cap = 0, perm_cap = 0, vbuf_cap = 0;
     std::vector<void*> allocs;
+    std::unique_ptr<Slabs> slabs;   // null until the first call, and behind a rebuild that failed: the next call rebuilds
 
-    // the data-parallel code path (a callback was supplied, or the handle has a communicator), also with one rank
-    bool dp() const { return ar != nullptr || native; }
-    // views of layer l: pre-BN conv output, post-activation and its bf16 parts (the third part only until the next forward conv has read
-    // it), packed kernels of conv layer l >= 1 in the forward / backward-data view
-    size_t act() const { return (size_t)M * NF; }
-    float* Yl(int l) const { return Y + act() * l; }
-    float* Al(int l) const { return A + act() * l; }
-    Parts Ap(int l) const { return Parts{{ap[0] + act() * l, ap[1] + act() * l, ap[2]}}; }
+    ~TrainState()
+    {
+        slabs.reset();
+        for (int q = 0; q < 2; q++) { if (ev_conv[q]) hipEventDestroy(ev_conv[q]); if (ev_wg[q]) hipEventDestroy(ev_wg[q]); }
+        if (side) hipStreamDestroy(side);
+        for (void* p : allocs) hipFree(p);
+        for (void* p : {(void*)rec, (void*)perm, (void*)vbuf}) if (p) hipFree(p);
+    }
+    // packed kernels of conv layer l >= 1 in the forward / backward-data view
     Parts Wpf(int l) const { const size_t o = (size_t)(l - 1) * KC * NF; return Parts{{wpf[0] + o, wpf[1] + o, wpf[2] + o}}; }
     Parts Wpb(int l) const { const size_t o = (size_t)(l - 1) * KC * NF; return Parts{{wpb[0] + o, wpb[1] + o, nullptr}}; }
 };
@@ -387,34 +421,34 @@ struct TrainCtx {
 inline float* layer_at(float* flat, int l) { return flat + OFF_BLOCK0 + (size_t)(l - 1) * LAYER; }
 inline const float* layer_at(const float* flat, int l) { return flat + OFF_BLOCK0 + (size_t)(l - 1) * LAYER; }
 
-TrainCtx* ctx_of(azr_engine* h) { return static_cast<TrainCtx*>(h->train); }
+TrainState* ctx_of(azr_engine* h) { return static_cast<TrainState*>(h->train); }
 
 // a training call is entered: the handle's options, as they are now, are this call's
-void opt_enter(azr_engine* h, TrainCtx* c)
+void opt_enter(azr_engine* h, TrainState* c)
 {
     const azr_train_options& o = h->train_opt;
     c->opt = o;
     c->opt_default = o.lr == LR && o.l2 == L2_C && o.lr_schedule == AZR_LR_CONSTANT && o.warmup_steps == 0 && o.clip_norm == 0.0f && o.ema_decay == 0.0f;
 }
 
+// one hipMalloc per buffer, remembered by its owner (a TrainState's or a Slabs' allocs)
 template <typename T>
-int dalloc(azr_engine* h, TrainCtx* c, T** p, size_t n)
+int dalloc(azr_engine* h, std::vector<void*>& owner, T** p, size_t n)
 {
     HIPCHK(h, hipMalloc((void**)p, n * sizeof(T)));
-    c->allocs.push_back(*p);
+    owner.push_back(*p);
     return AZR_OK;
 }
 
-void ctx_free(TrainCtx* c)
+// grow-only buffers (rec, perm, vbuf): at least `need` elements behind the call; a failed allocation leaves none and capacity 0
+int grow(azr_engine* h, void** p, size_t* cap, size_t need, size_t elem_size)
 {
-    if (!c) return;
-    for (int q = 0; q < 2; q++) { if (c->ev_conv[q]) hipEventDestroy(c->ev_conv[q]); if (c->ev_wg[q]) hipEventDestroy(c->ev_wg[q]); }
-    if (c->side) hipStreamDestroy(c->side);
-    for (void* p : c->allocs) hipFree(p);
-    if (c->rec) hipFree(c->rec);
-    if (c->perm) hipFree(c->perm);
-    if (c->vbuf) hipFree(c->vbuf);
-    delete c;
+    if (need <= *cap) return AZR_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    HIPCHK(h, hipMalloc(p, need * elem_size));
+    *cap = need;
+    return AZR_OK;
 }
 
 #define TRY(x)                 \
@@ -423,100 +457,35 @@ void ctx_free(TrainCtx* c)
         if (rc__) return rc__; \
     } while (0)
 
-// the weight gradient of one tower conv: 64 one-wave blocks (16 ci tiles x 4 co quarters) per slice of whole boards -> c->wpart[slice]
-static void launch_wgrad(TrainCtx* c, hipStream_t st, const Parts& apP, const Parts& dyP, int M)
+// the weight gradient of one tower conv: 64 one-wave blocks (16 ci tiles x 4 co quarters) per slice of whole boards -> s.wpart[slice]
+static void launch_wgrad(const Slabs& s, hipStream_t st, const Parts& apP, const Parts& dyP)
 {
 #ifdef AZR_TEST_HOOKS
-    if (!g_wgrad_g5) {
-        hipLaunchKernelGGL(t_wgrad_rs, dim3(64 * c->wg_slices), dim3(64), Wg::LDS_BYTES, st, apP, dyP, c->wpart, M, c->wg_slices, c->wg_bps * NPOS);
+    if (!s.plan.wg5) {
+        hipLaunchKernelGGL(t_wgrad_rs, dim3(64 * s.wg_slices), dim3(64), Wg::LDS_BYTES, st, apP, dyP, s.wpart, s.M, s.wg_slices, s.wg_bps * NPOS);
         return;
     }
 #endif
-    hipLaunchKernelGGL(t_wgrad_g5<WG5_NC>, dim3(Wg5<WG5_NC>::BLOCKS_PER_SLICE * c->wg_parts), dim3(256), Wg5<WG5_NC>::LDS_BLOCK, st, apP, dyP, c->wpart, M / NPOS,
-                       c->wg_slices, c->wg_bps);
+    hipLaunchKernelGGL(t_wgrad_g5<WG5_NC>, dim3(Wg5<WG5_NC>::BLOCKS_PER_SLICE * s.wg_parts), dim3(256), Wg5<WG5_NC>::LDS_BLOCK, st, apP, dyP, s.wpart, s.M / NPOS,
+                       s.wg_slices, s.wg_bps);
 }
 
-int ctx_ensure(azr_engine* h, int BS)
+// the handle's TrainState, created on the first call: installed only when it is complete (a failure on the way frees what was built)
+int state_ensure(azr_engine* h)
 {
-    TrainCtx* c = ctx_of(h);
-    if (c && c->BS == BS) return AZR_OK;
-    // tuning switch, read when a training context is (re)built — never in the step path
-#ifdef AZR_TEST_HOOKS
-    g_gemm_bf16x3 = !(hook_env("AZR_TRAIN_GEMM") && strcmp(hook_env("AZR_TRAIN_GEMM"), "f32") == 0);
-    g_fuse_bwd = hook_env_int("AZR_TRAIN_FUSE", 1) != 0;
-    g_fwd_f16 = !(hook_env("AZR_TRAIN_FWD") && strcmp(hook_env("AZR_TRAIN_FWD"), "bf16") == 0);
-    g_fuse_apply = hook_env_int("AZR_TRAIN_FUSE_APPLY", 1) != 0;
-    g_conv_q = hook_env_int("AZR_TRAIN_CONVQ", 1) != 0;
-    g_wgrad_g5 = !(hook_env("AZR_TRAIN_WGRAD") && strcmp(hook_env("AZR_TRAIN_WGRAD"), "rs") == 0);
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(t_wgrad_rs), hipFuncAttributeMaxDynamicSharedMemorySize, Wg::LDS_BYTES));
-#endif
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(t_wgrad_g5<WG5_NC>), hipFuncAttributeMaxDynamicSharedMemorySize, Wg5<WG5_NC>::LDS_BLOCK));
-    // a different batch size rebuilds the activation slabs but keeps the optimiser state
-    std::vector<float> keep_m, keep_v, keep_e;
-    long keep_step = 0, keep_ema_steps = 0;
-    StatRow keep_row = {};     // what azr_nn_train_stats reports is the last STEP's, whatever was rebuilt since: the row, the rate, the path
-    float keep_lr = 0.0f;
-    bool keep_last_default = true;
-    if (c) {
-        keep_last_default = c->last_default;
-        if (c->e) {
-            keep_e.resize(c->count);
-            HIPCHK(h, hipMemcpy(keep_e.data(), c->e, c->count * 4, hipMemcpyDeviceToHost));
-            keep_ema_steps = c->ema_steps;
-        }
-        HIPCHK(h, hipMemcpy(&keep_row, c->row, sizeof keep_row, hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(&keep_lr, c->lr, sizeof keep_lr, hipMemcpyDeviceToHost));
-        keep_m.resize(c->count); keep_v.resize(c->count);
-        HIPCHK(h, hipMemcpy(keep_m.data(), c->m, c->count * 4, hipMemcpyDeviceToHost));
-        HIPCHK(h, hipMemcpy(keep_v.data(), c->v, c->count * 4, hipMemcpyDeviceToHost));
-        keep_step = c->step;
-        ctx_free(c);
-        h->train = nullptr;
-    }
-    c = new TrainCtx();
-    h->train = c;
+    if (h->train) return AZR_OK;
+    std::unique_ptr<TrainState> c(new TrainState());
     const int B = h->net.blocks;
-    c->BS = BS; c->blocks = B; c->M = BS * NPOS; c->L = 2 * B + 1;
-    c->R = (c->M + RB - 1) / RB;
+    c->blocks = B; c->L = 2 * B + 1;
     c->count = net_param_count(B);
-    // split-K of the weight-gradient GEMM (36 output tiles of 128 x 128): as many slices as keep <= 2 blocks per CU
-    c->nz = std::max(1, std::min(512 / ((KC / GT) * (NF / GT)), (c->M + 1023) / 1024));
-    c->kchunk = (((c->M + c->nz - 1) / c->nz) + K3 - 1) / K3 * K3;
-    c->step = keep_step;
-    c->plan.sb = g_gemm_bf16x3 && c->M % K3 == 0;
-    c->plan.f16 = c->plan.sb && g_fwd_f16;
-    c->plan.fap = c->plan.f16 && g_fuse_bwd && g_fuse_apply;
-    c->plan.convq = c->plan.fap && g_conv_q && BS <= 128;
-    const size_t M = c->M, act = M * NF;
-    TRY(dalloc(h, c, &c->g, c->count)); TRY(dalloc(h, c, &c->m, c->count)); TRY(dalloc(h, c, &c->v, c->count));
-    TRY(dalloc(h, c, &c->kind, c->count));
-    TRY(dalloc(h, c, &c->X0, M * SIN)); TRY(dalloc(h, c, &c->col0, M * KS));
-    TRY(dalloc(h, c, &c->wpad, (size_t)KS * NF)); TRY(dalloc(h, c, &c->gpad, (size_t)KS * NF));
-    TRY(dalloc(h, c, &c->Y, act * c->L)); TRY(dalloc(h, c, &c->A, act * c->L));
-    TRY(dalloc(h, c, &c->G, act)); TRY(dalloc(h, c, &c->DS, act)); TRY(dalloc(h, c, &c->DT, act)); TRY(dalloc(h, c, &c->dY, act));
-    TRY(dalloc(h, c, &c->mean, (size_t)c->L * NF)); TRY(dalloc(h, c, &c->istd, (size_t)c->L * NF));
-    TRY(dalloc(h, c, &c->sums, (size_t)2 * NF));
-    TRY(dalloc(h, c, &c->part, (size_t)c->R * 2 * NG * NF));
-    {
-        // t_wgrad_g5: whole groups of 5 boards, as many slices as make the chip's 1024 SIMDs one block each
-        using W = Wg5<WG5_NC>;
-        const int want = 1024 / W::BLOCKS_PER_SLICE;
-        int bps = std::max(W::GB, ((BS + want - 1) / want + W::GB - 1) / W::GB * W::GB);
-#ifdef AZR_TEST_HOOKS
-        // t_wgrad_rs: slices of 16 j boards (16 boards = 672 rows = 21 k-steps), about 256 blocks = 16 ci tiles x slices
-        // (small batches — a rank's share of a data-parallel minibatch: 8-board slices, so that 64 records are 512 one-wave blocks)
-        if (!g_wgrad_g5) bps = (BS <= 128 && BS % 8 == 0) ? 8 : 16 * std::max(1, BS / 256);
-#endif
-        c->wg_slices = (BS + bps - 1) / bps;
-        c->wg_bps = bps;
-        c->wg_parts = g_wgrad_g5 ? (c->wg_slices + 3) / 4 : c->wg_slices;
-    }
-    TRY(dalloc(h, c, &c->wpart, (size_t)std::max(c->nz, c->wg_slices) * KC * NF));
-    // bf16 parts of the post-activations: the two leading parts are kept PER LAYER (the weight-gradient GEMM of the backward
-    // pass wants exactly them: no second split), the third one only until the next forward conv has read it
-    for (int q = 0; q < 3; q++) { TRY(dalloc(h, c, &c->ap[q], q < 2 ? act * c->L : act)); TRY(dalloc(h, c, &c->wpf[q], (size_t)2 * B * KC * NF)); }
-    for (int q = 0; q < 2; q++) TRY(dalloc(h, c, &c->wpb[q], (size_t)2 * B * KC * NF));
-    for (int q = 0; q < 2; q++) { TRY(dalloc(h, c, &c->dyp[q], act)); TRY(dalloc(h, c, &c->dyp2[q], act)); }
+    auto alloc = [&](auto** p, size_t n) { return dalloc(h, c->allocs, p, n); };
+    TRY(alloc(&c->g, c->count)); TRY(alloc(&c->m, c->count)); TRY(alloc(&c->v, c->count));
+    TRY(alloc(&c->kind, c->count));
+    TRY(alloc(&c->wpad, (size_t)KS * NF)); TRY(alloc(&c->gpad, (size_t)KS * NF));
+    TRY(alloc(&c->mean, (size_t)c->L * NF)); TRY(alloc(&c->istd, (size_t)c->L * NF));
+    TRY(alloc(&c->sums, (size_t)2 * NF));
+    for (int q = 0; q < 3; q++) TRY(alloc(&c->wpf[q], (size_t)2 * B * KC * NF));
+    for (int q = 0; q < 2; q++) TRY(alloc(&c->wpb[q], (size_t)2 * B * KC * NF));
     {
         int lo = 0, hi = 0;
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));   // (lo = the numerically greatest = least urgent)
@@ -526,37 +495,14 @@ int ctx_ensure(azr_engine* h, int BS)
             HIPCHK(h, hipEventCreateWithFlags(&c->ev_wg[q], hipEventDisableTiming));
         }
     }
-    for (int q = 0; q < 2; q++) TRY(dalloc(h, c, &c->af[q], act));
-    TRY(dalloc(h, c, &c->pv0, M * 4)); TRY(dalloc(h, c, &c->dpv, M * 4)); TRY(dalloc(h, c, &c->hstat, (size_t)8));
-    TRY(dalloc(h, c, &c->fpi, (size_t)BS * 84)); TRY(dalloc(h, c, &c->fv, (size_t)BS * 42)); TRY(dalloc(h, c, &c->h1, (size_t)BS * 256));
-    TRY(dalloc(h, c, &c->vout, (size_t)BS)); TRY(dalloc(h, c, &c->prob, (size_t)BS * 43)); TRY(dalloc(h, c, &c->lossb, (size_t)BS * 2));
-    TRY(dalloc(h, c, &c->hpart, (size_t)BS * HP_FLOATS)); TRY(dalloc(h, c, &c->cpart, (size_t)c->R * 3 * NF));
-    TRY(dalloc(h, c, &c->loss, (size_t)4));
-    TRY(dalloc(h, c, &c->cur, (size_t)4)); TRY(dalloc(h, c, &c->lr, (size_t)1));
-    TRY(dalloc(h, c, &c->red, (size_t)2 * NG * NF)); TRY(dalloc(h, c, &c->hsum, (size_t)8));
-    TRY(dalloc(h, c, &c->row, (size_t)1)); TRY(dalloc(h, c, &c->sqpart, (size_t)SQ_BLOCKS));
-    HIPCHK(h, hipMemcpy(c->row, &keep_row, sizeof keep_row, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(c->lr, &keep_lr, sizeof keep_lr, hipMemcpyHostToDevice));
-    c->last_default = keep_last_default;
-    if (!keep_e.empty()) {
-        TRY(dalloc(h, c, &c->e, c->count));
-        HIPCHK(h, hipMemcpy(c->e, keep_e.data(), c->count * 4, hipMemcpyHostToDevice));
-        c->ema_steps = keep_ema_steps;
-    }
-    {
-        const int init[4] = {0, (int)keep_step, 0, 0};
-        HIPCHK(h, hipMemcpy(c->cur, init, sizeof init, hipMemcpyHostToDevice));
-    }
-    TRY(dalloc(h, c, &c->in88, (size_t)BS * 88)); TRY(dalloc(h, c, &c->pit, (size_t)BS * 43)); TRY(dalloc(h, c, &c->zt, (size_t)BS));
-    HIPCHK(h, hipMemset(c->dpv, 0, M * 4 * sizeof(float)));
-    HIPCHK(h, hipMemset(c->g, 0, c->count * 4));
-    if (keep_m.empty()) {
-        HIPCHK(h, hipMemset(c->m, 0, c->count * 4));
-        HIPCHK(h, hipMemset(c->v, 0, c->count * 4));
-    } else {
-        HIPCHK(h, hipMemcpy(c->m, keep_m.data(), c->count * 4, hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(c->v, keep_v.data(), c->count * 4, hipMemcpyHostToDevice));
-    }
+    TRY(alloc(&c->hstat, (size_t)8)); TRY(alloc(&c->loss, (size_t)4));
+    TRY(alloc(&c->cur, (size_t)CUR_N)); TRY(alloc(&c->lr, (size_t)1));
+    TRY(alloc(&c->red, (size_t)2 * NG * NF)); TRY(alloc(&c->hsum, (size_t)8));
+    TRY(alloc(&c->row, (size_t)1)); TRY(alloc(&c->sqpart, (size_t)SQ_BLOCKS));
+    HIPCHK(h, hipMemset(c->row, 0, sizeof(StatRow)));
+    HIPCHK(h, hipMemset(c->lr, 0, sizeof(float)));
+    HIPCHK(h, hipMemset(c->cur, 0, CUR_N * sizeof(int)));
+    for (float* z : {c->g, c->m, c->v}) HIPCHK(h, hipMemset(z, 0, c->count * 4));
     // parameter kinds: 1 = kernel (L2-regularised), 2 = BN gamma/beta and dense biases, 0 = BN moving statistics
     std::vector<uint8_t> kind(c->count, 0);
     auto fill = [&](size_t off, size_t n, uint8_t k) { std::fill(kind.begin() + off, kind.begin() + off + n, k); };
@@ -575,6 +521,85 @@ int ctx_ensure(azr_engine* h, int BS)
     fill(hh + H_V1_W, 10752, 1); fill(hh + H_V1_B, 256, 2);
     fill(hh + H_V2_W, 256, 1); fill(hh + H_V2_B, 1, 2);
     HIPCHK(h, hipMemcpy(c->kind, kind.data(), c->count, hipMemcpyHostToDevice));
+    h->train = c.release();
+    return AZR_OK;
+}
+
+// The state, and slabs for batches of BS records.  Another batch size frees the old slabs first (peak memory does not rise), builds the
+// new ones into a local owner and installs them only when every allocation has succeeded: behind a failure the state has no slabs, and
+// the next call builds them.  Nothing can see a batch size without its buffers.
+int ctx_ensure(azr_engine* h, int BS)
+{
+    TRY(state_ensure(h));
+    TrainState* c = ctx_of(h);
+    if (c->slabs && c->slabs->BS == BS) return AZR_OK;
+    // tuning switches, read when the slabs are (re)built — never in the step path
+#ifdef AZR_TEST_HOOKS
+    g_gemm_bf16x3 = !(hook_env("AZR_TRAIN_GEMM") && strcmp(hook_env("AZR_TRAIN_GEMM"), "f32") == 0);
+    g_fuse_bwd = hook_env_int("AZR_TRAIN_FUSE", 1) != 0;
+    g_fwd_f16 = !(hook_env("AZR_TRAIN_FWD") && strcmp(hook_env("AZR_TRAIN_FWD"), "bf16") == 0);
+    g_fuse_apply = hook_env_int("AZR_TRAIN_FUSE_APPLY", 1) != 0;
+    g_conv_q = hook_env_int("AZR_TRAIN_CONVQ", 1) != 0;
+    g_wgrad_g5 = !(hook_env("AZR_TRAIN_WGRAD") && strcmp(hook_env("AZR_TRAIN_WGRAD"), "rs") == 0);
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(t_wgrad_rs), hipFuncAttributeMaxDynamicSharedMemorySize, Wg::LDS_BYTES));
+#endif
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(t_wgrad_g5<WG5_NC>), hipFuncAttributeMaxDynamicSharedMemorySize, Wg5<WG5_NC>::LDS_BLOCK));
+    c->slabs.reset();
+    std::unique_ptr<Slabs> s(new Slabs());
+    s->BS = BS; s->M = BS * NPOS;
+    s->R = (s->M + RB - 1) / RB;
+    // split-K of the weight-gradient GEMM (36 output tiles of 128 x 128): as many slices as keep <= 2 blocks per CU
+    s->nz = std::max(1, std::min(512 / ((KC / GT) * (NF / GT)), (s->M + 1023) / 1024));
+    s->kchunk = (((s->M + s->nz - 1) / s->nz) + K3 - 1) / K3 * K3;
+    Plan& p = s->plan;
+    p.sb = g_gemm_bf16x3 && s->M % K3 == 0;
+    p.f16 = p.sb && g_fwd_f16;
+    p.fap = p.f16 && g_fuse_bwd && g_fuse_apply;
+    p.convq = p.fap && g_conv_q && BS <= 128;
+    p.wg5 = g_wgrad_g5;
+    p.fuse = p.sb && g_fuse_bwd;
+    p.bap = p.fuse && g_fuse_apply;
+    {
+        // t_wgrad_g5: whole groups of 5 boards, as many slices as make the chip's 1024 SIMDs one block each
+        using W = Wg5<WG5_NC>;
+        const int want = 1024 / W::BLOCKS_PER_SLICE;
+        int bps = std::max(W::GB, ((BS + want - 1) / want + W::GB - 1) / W::GB * W::GB);
+#ifdef AZR_TEST_HOOKS
+        // t_wgrad_rs: slices of 16 j boards (16 boards = 672 rows = 21 k-steps), about 256 blocks = 16 ci tiles x slices
+        // (small batches — a rank's share of a data-parallel minibatch: 8-board slices, so that 64 records are 512 one-wave blocks)
+        if (!p.wg5) bps = (BS <= 128 && BS % 8 == 0) ? 8 : 16 * std::max(1, BS / 256);
+#endif
+        s->wg_slices = (BS + bps - 1) / bps;
+        s->wg_bps = bps;
+        s->wg_parts = p.wg5 ? (s->wg_slices + 3) / 4 : s->wg_slices;
+    }
+    // (test hook AZR_TRAIN_FAIL_ALLOC=k, k >= 1 — libazr_hip_test.so only: the k-th allocation below fails before it reaches hipMalloc)
+    const int fail = hook_env_int("AZR_TRAIN_FAIL_ALLOC", 0);
+    auto alloc = [&](auto** p, size_t n) {
+        if (fail > 0 && (size_t)fail == s->allocs.size() + 1) {
+            h->err = "azr_nn_train: slab allocation " + std::to_string(fail) + " failed (injected by AZR_TRAIN_FAIL_ALLOC, no hipMalloc was called)";
+            return (int)AZR_E_HIP;
+        }
+        return dalloc(h, s->allocs, p, n);
+    };
+    const size_t M = s->M, act = M * NF, L = c->L;
+    TRY(alloc(&s->X0, M * SIN)); TRY(alloc(&s->col0, M * KS));
+    TRY(alloc(&s->Y, act * L)); TRY(alloc(&s->A, act * L));
+    TRY(alloc(&s->G, act)); TRY(alloc(&s->DS, act)); TRY(alloc(&s->DT, act)); TRY(alloc(&s->dY, act));
+    TRY(alloc(&s->part, (size_t)s->R * 2 * NG * NF));
+    TRY(alloc(&s->wpart, (size_t)std::max(s->nz, s->wg_slices) * KC * NF));
+    // bf16 parts of the post-activations: the two leading parts are kept PER LAYER (the weight-gradient GEMM of the backward
+    // pass wants exactly them: no second split), the third one only until the next forward conv has read it
+    for (int q = 0; q < 3; q++) TRY(alloc(&s->ap[q], q < 2 ? act * L : act));
+    for (int q = 0; q < 2; q++) { TRY(alloc(&s->dyp[q], act)); TRY(alloc(&s->dyp2[q], act)); }
+    for (int q = 0; q < 2; q++) TRY(alloc(&s->af[q], act));
+    TRY(alloc(&s->pv0, M * 4)); TRY(alloc(&s->dpv, M * 4));
+    TRY(alloc(&s->fpi, (size_t)BS * 84)); TRY(alloc(&s->fv, (size_t)BS * 42)); TRY(alloc(&s->h1, (size_t)BS * 256));
+    TRY(alloc(&s->vout, (size_t)BS)); TRY(alloc(&s->prob, (size_t)BS * 43)); TRY(alloc(&s->lossb, (size_t)BS * 2));
+    TRY(alloc(&s->hpart, (size_t)BS * HP_FLOATS)); TRY(alloc(&s->cpart, (size_t)s->R * 3 * NF));
+    TRY(alloc(&s->in88, (size_t)BS * 88)); TRY(alloc(&s->pit, (size_t)BS * 43)); TRY(alloc(&s->zt, (size_t)BS));
+    HIPCHK(h, hipMemset(s->dpv, 0, M * 4 * sizeof(float)));
+    c->slabs = std::move(s);
     return AZR_OK;
 }
 
@@ -629,37 +654,37 @@ RcclApi* rccl_api()   // bound once, whichever host thread asks first (the host 
 // the engine's own stream — stream-ordered, the host never waits (86 of them per step at B = 20: with a host hand-over each they
 // cost more than the step's kernels).  Otherwise through the caller's callback (a torch.distributed rehearsal over gloo, or any other
 // transport): the engine's stream is drained first, the callback returns when the result is in place.
-int dp_allreduce(azr_engine* h, TrainCtx* c, void* dev, size_t count, int dtype)
+int dp_allreduce(azr_engine* h, const DpLink& k, void* dev, size_t count, int dtype)
 {
-    if (c->native) {
+    if (k.native) {
         RcclApi* R = rccl_api();
         const ncclResult_t rc = R->AllReduce(dev, dev, count, dtype ? ncclDouble : ncclFloat, ncclSum, static_cast<ncclComm_t>(h->dp_comm), h->stream);
         if (rc != ncclSuccess) { h->err = std::string("ncclAllReduce: ") + R->GetErrorString(rc); return AZR_E_HIP; }
         return AZR_OK;
     }
-    if (!c->ar) return AZR_OK;
+    if (!k.ar) return AZR_OK;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int rc = c->ar(c->ar_ctx, dev, count, dtype);
+    const int rc = k.ar(k.ar_ctx, dev, count, dtype);
     if (rc) { h->err = "azr_nn_train_dp: the all-reduce callback failed with code " + std::to_string(rc); return AZR_E_STATE; }
     return AZR_OK;
 }
 
 // sums over the batch in a data-parallel step: [R local block partials of K rows -> one slab] -> all-reduce over the ranks; the finalize
 // kernel then reads the slab as one block of partials
-int reduce_parts(azr_engine* h, TrainCtx* c, int R, int K)
+int reduce_parts(azr_engine* h, TrainState* c, int R, int K)
 {
-    hipLaunchKernelGGL(t_parts_sum, dim3(K), dim3(256), 0, h->stream, c->part, R, K, c->red);
-    return dp_allreduce(h, c, c->red, (size_t)K * NF, 1);
+    hipLaunchKernelGGL(t_parts_sum, dim3(K), dim3(256), 0, h->stream, c->slabs->part, R, K, c->red);
+    return dp_allreduce(h, c->link, c->red, (size_t)K * NF, 1);
 }
 
 // One tower conv of the split path: t_conv_q at small batches, else t_conv_rs (two parts), with the grid that goes with it.  Returns the
 // number of blocks, i.e. of partials a statistics epilogue (FUSE != 0) leaves in bf.part.
 template <int AMODE, int FUSE, bool F16, int PRO>
-int launch_conv(const TrainCtx* c, hipStream_t st, const Parts& A, const Parts& W, float* out, const BwdFuse& bf, float oscale, const ProFuse& pf)
+int launch_conv(const Slabs& s, hipStream_t st, const Parts& A, const Parts& W, float* out, const BwdFuse& bf, float oscale, const ProFuse& pf)
 {
-    const int BS = c->BS;
-    if (c->plan.convq) {
+    const int BS = s.BS;
+    if (s.plan.convq) {
         hipLaunchKernelGGL((t_conv_q<AMODE, FUSE, F16, PRO>), dim3(4 * BS), dim3(256), 0, st, A, W, out, BS, bf, oscale, pf);
         return BS;
     }
@@ -667,232 +692,255 @@ int launch_conv(const TrainCtx* c, hipStream_t st, const Parts& A, const Parts& 
     return (BS + 1) / 2;
 }
 
-// The tower's forward pass on the minibatch already gathered into c->in88: planes -> stem -> conv layers 1 .. L - 1, leaving every
+// The tower's forward pass on the minibatch already gathered into s.in88: planes -> stem -> conv layers 1 .. L - 1, leaving every
 // layer's conv output (Yl) and post-activation (Al, with its bf16 parts) behind.
 //   training:  batch statistics — taken in the conv's epilogue (FUSE = 2) or by t_bn_stats, all-reduced in a data-parallel step,
 //              t_bn_finalize writes mean / 1/std and updates the moving averages; the stem kernel is padded every step (Adam moved it);
 //   otherwise (the validation pass): c->mean / istd hold the MOVING statistics and c->wpad the padded stem kernel (azr_nn_validate,
-//              once per call): no statistics kernels, no statistics epilogue (FUSE = 0), nothing but the context's scratch is written.
-int forward_tower(azr_engine* h, TrainCtx* c, bool training)
+//              once per call): no statistics kernels, no statistics epilogue (FUSE = 0), nothing but scratch is written.
+int forward_tower(azr_engine* h, TrainState* c, bool training)
 {
     hipStream_t st = h->stream;
-    const Plan& p = c->plan;
-    const int M = c->M, R = c->R;
-    const bool dp = c->dp();
+    const Slabs& s = *c->slabs;
+    const Plan& p = s.plan;
+    const int M = s.M, R = s.R, L = c->L, world = c->link.world;
+    const bool dp = c->link.dp();
     float* w = h->net.d_flat;
-    const unsigned g4 = (unsigned)((c->act() / 4 + 255) / 256);
+    const unsigned g4 = (unsigned)((s.act() / 4 + 255) / 256);
     uint16_t* const nil16 = nullptr;
-    hipLaunchKernelGGL(t_planes, grid1((size_t)M * SIN, 256), dim3(256), 0, st, c->in88, M, c->X0);
+    hipLaunchKernelGGL(t_planes, grid1((size_t)M * SIN, 256), dim3(256), 0, st, s.in88, M, s.X0);
     if (training) hipLaunchKernelGGL(t_stem_pad, grid1((size_t)KS * NF, 256), dim3(256), 0, st, w, c->wpad);
-    hipLaunchKernelGGL((t_im2col<SIN>), grid1((size_t)M * 9, 4), dim3(256), 0, st, c->X0, c->col0, M);
-    gemm<false, false, 64>(st, c->col0, KS, c->wpad, NF, c->Yl(0), NF, M, NF, KS);
+    hipLaunchKernelGGL((t_im2col<SIN>), grid1((size_t)M * 9, 4), dim3(256), 0, st, s.X0, s.col0, M);
+    gemm<false, false, 64>(st, s.col0, KS, c->wpad, NF, s.Yl(0), NF, M, NF, KS);
     if (training) {
-        hipLaunchKernelGGL((t_bn_stats<true>), dim3(R), dim3(1024), 0, st, c->Yl(0), M, c->part);
+        hipLaunchKernelGGL((t_bn_stats<true>), dim3(R), dim3(1024), 0, st, s.Yl(0), M, s.part);
         if (dp) TRY(reduce_parts(h, c, R, 2 * NG));
-        hipLaunchKernelGGL((t_bn_finalize<true>), dim3(NG), dim3(1024), 0, st, dp ? c->red : c->part, dp ? 1 : R,
-                           (double)c->BS * c->world * 6 * NF, c->mean, c->istd, w + OFF_STEM_BN);
+        hipLaunchKernelGGL((t_bn_finalize<true>), dim3(NG), dim3(1024), 0, st, dp ? c->red : s.part, dp ? 1 : R,
+                           (double)s.BS * world * 6 * NF, c->mean, c->istd, w + OFF_STEM_BN);
     }
     // (each layer's normalise kernel also writes the bf16 parts of its output and the fp16 pair: the next conv's A operand)
-    hipLaunchKernelGGL((t_bn_apply<true>), dim3(g4), dim3(256), 0, st, c->Yl(0), c->mean, c->istd, w + OFF_STEM_BN, (const float*)nullptr, c->Al(0), M,
-                       p.sb ? c->ap[0] : nil16, c->ap[1], p.f16 ? nil16 : c->ap[2], p.f16 ? c->af[0] : nil16, c->af[1]);
-    const Parts none{{nullptr, nullptr, nullptr}}, af{{c->af[0], c->af[1], nullptr}};
-    const BwdFuse bf{nullptr, nullptr, nullptr, nullptr, nullptr, training ? c->part : nullptr};
-    for (int l = 1; l < c->L; l++) {
+    hipLaunchKernelGGL((t_bn_apply<true>), dim3(g4), dim3(256), 0, st, s.Yl(0), c->mean, c->istd, w + OFF_STEM_BN, (const float*)nullptr, s.Al(0), M,
+                       p.sb ? s.ap[0] : nil16, s.ap[1], p.f16 ? nil16 : s.ap[2], p.f16 ? s.af[0] : nil16, s.af[1]);
+    const Parts none{{nullptr, nullptr, nullptr}}, af{{s.af[0], s.af[1], nullptr}};
+    const BwdFuse bf{nullptr, nullptr, nullptr, nullptr, nullptr, training ? s.part : nullptr};
+    for (int l = 1; l < L; l++) {
         float* bn = layer_at(w, l) + (size_t)9 * NF * NF;
-        const float* S = (l % 2 == 0) ? c->Al(l - 2) : nullptr;  // second conv of a block adds the block input
+        const float* S = (l % 2 == 0) ? s.Al(l - 2) : nullptr;  // second conv of a block adds the block input
         int parts = 0;   // block partials of the output's statistics that the conv's epilogue left (training)
-        if (!p.sb) gemm<false, false, 64, 1, 0>(st, c->Al(l - 1), KC, layer_at(w, l), NF, c->Yl(l), NF, M, NF, KC);
+        if (!p.sb) gemm<false, false, 64, 1, 0>(st, s.Al(l - 1), KC, layer_at(w, l), NF, s.Yl(l), NF, M, NF, KC);
         else if (p.fap && l >= 2) {
             // Fused mode (fp16 forward + epilogue statistics + staging-path normalise): layer l - 1's normalise step is not a kernel of
             // its own — this conv computes A_m = relu(BN(Y_m) (+ S)), m = l - 1, while it stages its operand and writes A_m and its bf16
             // parts out; only the stem (row-wise BN) and the last layer (the heads read it) keep t_bn_apply.
             const int m = l - 1;
-            const ProFuse pf{c->Yl(m), (m % 2 == 0) ? (const float*)c->Al(m - 2) : (const float*)nullptr, nullptr, c->mean + m * NF, c->istd + m * NF,
-                             layer_at(w, m) + (size_t)9 * NF * NF, nullptr, 0.0f, c->Al(m), const_cast<uint16_t*>(c->Ap(m).p[0]),
-                             const_cast<uint16_t*>(c->Ap(m).p[1])};
-            if (training) parts = launch_conv<1, 2, true, 1>(c, st, none, c->Wpf(l), c->Yl(l), bf, 1.0f / FWD_WSCALE, pf);
-            else launch_conv<1, 0, true, 1>(c, st, none, c->Wpf(l), c->Yl(l), bf, 1.0f / FWD_WSCALE, pf);
+            const ProFuse pf{s.Yl(m), (m % 2 == 0) ? (const float*)s.Al(m - 2) : (const float*)nullptr, nullptr, c->mean + m * NF, c->istd + m * NF,
+                             layer_at(w, m) + (size_t)9 * NF * NF, nullptr, 0.0f, s.Al(m), const_cast<uint16_t*>(s.Ap(m).p[0]),
+                             const_cast<uint16_t*>(s.Ap(m).p[1])};
+            if (training) parts = launch_conv<1, 2, true, 1>(s, st, none, c->Wpf(l), s.Yl(l), bf, 1.0f / FWD_WSCALE, pf);
+            else launch_conv<1, 0, true, 1>(s, st, none, c->Wpf(l), s.Yl(l), bf, 1.0f / FWD_WSCALE, pf);
         } else if (p.f16) {   // operand = the fp16 pair the previous normalise kernel wrote (layer 1: the stem's)
-            if (training && g_fuse_bwd) parts = launch_conv<1, 2, true, 0>(c, st, af, c->Wpf(l), c->Yl(l), bf, 1.0f / FWD_WSCALE, ProFuse{});
-            else launch_conv<1, 0, true, 0>(c, st, af, c->Wpf(l), c->Yl(l), bf, 1.0f / FWD_WSCALE, ProFuse{});   // (training: AZR_TRAIN_FUSE=0)
+            if (training && p.fuse) parts = launch_conv<1, 2, true, 0>(s, st, af, c->Wpf(l), s.Yl(l), bf, 1.0f / FWD_WSCALE, ProFuse{});
+            else launch_conv<1, 0, true, 0>(s, st, af, c->Wpf(l), s.Yl(l), bf, 1.0f / FWD_WSCALE, ProFuse{});   // (training: AZR_TRAIN_FUSE=0)
         }
 #ifdef AZR_TEST_HOOKS   // AZR_TRAIN_FWD=bf16, the older formulation of the same conv: three bf16 parts, 6 passes (libazr_hip_test.so only)
-        else hipLaunchKernelGGL((t_conv_rs<1, 3>), dim3((c->BS + 1) / 2), dim3(256), 0, st, c->Ap(l - 1), c->Wpf(l), c->Yl(l), c->BS, BwdFuse{}, 1.0f, ProFuse{});
+        else hipLaunchKernelGGL((t_conv_rs<1, 3>), dim3((s.BS + 1) / 2), dim3(256), 0, st, s.Ap(l - 1), c->Wpf(l), s.Yl(l), s.BS, BwdFuse{}, 1.0f, ProFuse{});
 #endif
         if (training) {
             const int Rf = parts ? parts : R;
-            if (!parts) hipLaunchKernelGGL((t_bn_stats<false>), dim3(R), dim3(1024), 0, st, c->Yl(l), M, c->part);
+            if (!parts) hipLaunchKernelGGL((t_bn_stats<false>), dim3(R), dim3(1024), 0, st, s.Yl(l), M, s.part);
             if (dp) TRY(reduce_parts(h, c, Rf, 2));
-            hipLaunchKernelGGL((t_bn_finalize<false>), dim3(8), dim3(1024), 0, st, dp ? c->red : c->part, dp ? 1 : Rf, (double)M * c->world,
+            hipLaunchKernelGGL((t_bn_finalize<false>), dim3(8), dim3(1024), 0, st, dp ? c->red : s.part, dp ? 1 : Rf, (double)M * world,
                                c->mean + l * NF, c->istd + l * NF, bn);
         }
-        if (p.fap && l + 1 < c->L) continue;   // the next conv normalises this layer's output itself
-        hipLaunchKernelGGL((t_bn_apply<false>), dim3(g4), dim3(256), 0, st, c->Yl(l), c->mean + l * NF, c->istd + l * NF, bn, S, c->Al(l), M,
-                           (p.sb && l + 1 < c->L) ? const_cast<uint16_t*>(c->Ap(l).p[0]) : nil16, const_cast<uint16_t*>(c->Ap(l).p[1]),
-                           p.f16 ? nil16 : c->ap[2], (p.f16 && l + 1 < c->L) ? c->af[0] : nil16, c->af[1]);
+        if (p.fap && l + 1 < L) continue;   // the next conv normalises this layer's output itself
+        hipLaunchKernelGGL((t_bn_apply<false>), dim3(g4), dim3(256), 0, st, s.Yl(l), c->mean + l * NF, c->istd + l * NF, bn, S, s.Al(l), M,
+                           (p.sb && l + 1 < L) ? const_cast<uint16_t*>(s.Ap(l).p[0]) : nil16, const_cast<uint16_t*>(s.Ap(l).p[1]),
+                           p.f16 ? nil16 : s.ap[2], (p.f16 && l + 1 < L) ? s.af[0] : nil16, s.af[1]);
     }
     return AZR_OK;
 }
 
-// one optimiser step on the minibatch already gathered into c->in88 / pit / zt
-int train_step(azr_engine* h, TrainCtx* c, float* d_acc)
-{
-    hipStream_t st = h->stream;
-    const int M = c->M, B = c->blocks, R = c->R, BS = c->BS;
-    // data-parallel: BS / M are this rank's shard, BSg / Mg the whole minibatch every statistic and mean refers to
-    const int W = c->world, BSg = BS * W, Mg = M * W;
-    const bool dp = c->dp();
-    const float gscale = 1.0f / (float)W;
-    float* w = h->net.d_flat;
-    float* g = c->g;
-    const size_t act = c->act(), wn = (size_t)KC * NF;
-    const size_t hh = OFF_BLOCK0 + (size_t)2 * B * LAYER;
-    float* hp = w + hh;
-    float* gh = g + hh;
-    const unsigned g4 = (unsigned)((act / 4 + 255) / 256);
-    const bool sb = c->plan.sb, convq = c->plan.convq;
+// what the backward loop carries from layer l to layer l - 1
+struct LayerCarry {
+    int fused_parts = 0;            // t_conv_rs<2, 2, 1>, the backward-data conv of layer l, has left stage 1 of layer l - 1's batch-norm backward
+                                    // behind: its block partials are already in s.part, this many blocks of them
+    float* pending_sum = nullptr;   // the slice sum of the layer above is launched together with this layer's BN-backward stage 2 (t_sum_slices_fin)
+    int side_used = 0;              // the layer parities whose weight gradient ran on the side stream
+};
+
+// One optimiser step on the minibatch already gathered into s.in88 / pit / zt: what every stage reads, and the stages in the order
+// run() calls them.  (Data-parallel: BS / M are this rank's shard, BSg / Mg the whole minibatch every statistic and mean refers to.)
+struct Step {
+    azr_engine* const h;
+    TrainState* const c;
+    const Slabs& s = *c->slabs;
+    const Plan& p = s.plan;
+    const hipStream_t st = h->stream;
+    const int M = s.M, R = s.R, BS = s.BS, BSg = BS * c->link.world, Mg = M * c->link.world;
+    const bool dp = c->link.dp();
+    const float gscale = 1.0f / (float)c->link.world, invM = 1.0f / (float)Mg;
+    float* const w = h->net.d_flat;
+    float* const g = c->g;
+    const size_t wn = (size_t)KC * NF, hh = OFF_BLOCK0 + (size_t)2 * c->blocks * LAYER;
+    float* const hp = w + hh;   // the heads' part of w
+    float* const gh = g + hh;   // ... and of g
+    const unsigned g4 = (unsigned)((s.act() / 4 + 255) / 256);
     uint16_t* const nil16 = nullptr;
-    if (sb) {
-        const dim3 pg((unsigned)((wn / 8 + 255) / 256), 2 * B);
-        hipLaunchKernelGGL((t_pack_w<3>), pg, dim3(256), 0, st, w, 0, c->wpf[0], c->wpf[1], c->wpf[2], c->plan.f16 ? FWD_WSCALE : 0.0f, c->cur + 3);
-        hipLaunchKernelGGL((t_pack_w<2>), pg, dim3(256), 0, st, w, 1, c->wpb[0], c->wpb[1], (uint16_t*)nullptr);
+
+    int heads_forward(float* d_acc) const
+    {
+        const float* H = s.Al(c->L - 1);
+        hipLaunchKernelGGL(t_head_conv, grid1((size_t)M, 4), dim3(256), 0, st, H, hp, s.pv0, M);
+        hipLaunchKernelGGL(t_head_bn_sums, dim3(1), dim3(1024), 0, st, s.pv0, M, c->hsum);
+        if (dp) TRY(dp_allreduce(h, c->link, c->hsum, 6, 1));
+        hipLaunchKernelGGL(t_head_bn_stats, dim3(1), dim3(64), 0, st, (const double*)c->hsum, (double)Mg, hp, c->hstat);
+        hipLaunchKernelGGL(t_head_fwd, dim3(BS), dim3(256), 0, st, s.pv0, hp, c->hstat, s.pit, s.zt, s.fpi, s.fv, s.h1, s.vout, s.prob, s.lossb);
+        hipLaunchKernelGGL(t_loss, dim3(1), dim3(1), 0, st, s.lossb, BS, BSg, c->loss);
+        if (dp) TRY(dp_allreduce(h, c->link, c->loss, 2, 0));
+        hipLaunchKernelGGL(t_loss_acc, dim3(1), dim3(1), 0, st, (const float*)c->loss, d_acc);
+        return AZR_OK;
     }
 
-    // ---------------- forward, training mode
-    TRY(forward_tower(h, c, true));
-    const float* H = c->Al(c->L - 1);
-    hipLaunchKernelGGL(t_head_conv, grid1((size_t)M, 4), dim3(256), 0, st, H, hp, c->pv0, M);
-    hipLaunchKernelGGL(t_head_bn_sums, dim3(1), dim3(1024), 0, st, c->pv0, M, c->hsum);
-    if (dp) TRY(dp_allreduce(h, c, c->hsum, 6, 1));
-    hipLaunchKernelGGL(t_head_bn_stats, dim3(1), dim3(64), 0, st, (const double*)c->hsum, (double)Mg, hp, c->hstat);
-    hipLaunchKernelGGL(t_head_fwd, dim3(BS), dim3(256), 0, st, c->pv0, hp, c->hstat, c->pit, c->zt, c->fpi, c->fv, c->h1, c->vout, c->prob, c->lossb);
-    hipLaunchKernelGGL(t_loss, dim3(1), dim3(1), 0, st, c->lossb, BS, BSg, c->loss);
-    if (dp) TRY(dp_allreduce(h, c, c->loss, 2, 0));
-    hipLaunchKernelGGL(t_loss_acc, dim3(1), dim3(1), 0, st, (const float*)c->loss, d_acc);
+    int heads_backward() const
+    {
+        const float* H = s.Al(c->L - 1);
+        hipLaunchKernelGGL(t_head_bwd, dim3(BS), dim3(256), 0, st, hp, s.pit, s.zt, s.fpi, s.fv, s.h1, s.vout, s.prob, BSg, s.dpv, s.hpart);
+        hipLaunchKernelGGL(t_head_reduce, grid1(HP_FLOATS, 256), dim3(256), 0, st, s.hpart, BS, gh);
+        hipLaunchKernelGGL(t_head_bn_bwd_sums, dim3(1), dim3(1024), 0, st, s.pv0, c->hstat, M, (const float*)s.dpv, c->hsum);
+        if (dp) TRY(dp_allreduce(h, c->link, c->hsum, 6, 1));
+        hipLaunchKernelGGL(t_head_bn_bwd, dim3((M + 1023) / 1024), dim3(1024), 0, st, s.pv0, hp, c->hstat, M, (const double*)c->hsum, (float)Mg, gscale, s.dpv, gh);
+        hipLaunchKernelGGL(t_head_conv_bwd, dim3(R), dim3(256), 0, st, H, s.dpv, hp, M, s.G, s.cpart);
+        hipLaunchKernelGGL(t_head_conv_bwd_finalize, dim3(1), dim3(256), 0, st, s.cpart, R, gh);
+        return AZR_OK;
+    }
 
-    // ---------------- backward
-    hipLaunchKernelGGL(t_head_bwd, dim3(BS), dim3(256), 0, st, hp, c->pit, c->zt, c->fpi, c->fv, c->h1, c->vout, c->prob, BSg, c->dpv, c->hpart);
-    hipLaunchKernelGGL(t_head_reduce, grid1(HP_FLOATS, 256), dim3(256), 0, st, c->hpart, BS, gh);
-    hipLaunchKernelGGL(t_head_bn_bwd_sums, dim3(1), dim3(1024), 0, st, c->pv0, c->hstat, M, (const float*)c->dpv, c->hsum);
-    if (dp) TRY(dp_allreduce(h, c, c->hsum, 6, 1));
-    hipLaunchKernelGGL(t_head_bn_bwd, dim3((M + 1023) / 1024), dim3(1024), 0, st, c->pv0, hp, c->hstat, M, (const double*)c->hsum, (float)Mg, gscale, c->dpv, gh);
-    hipLaunchKernelGGL(t_head_conv_bwd, dim3(R), dim3(256), 0, st, H, c->dpv, hp, M, c->G, c->cpart);
-    hipLaunchKernelGGL(t_head_conv_bwd_finalize, dim3(1), dim3(256), 0, st, c->cpart, R, gh);
-    const float invM = 1.0f / (float)Mg;
-    // (t_conv_rs<2, 2, 1>, the backward-data conv of layer l, leaves stage 1 of layer l - 1's batch-norm backward behind: its
-    //  block partials are then already in c->part, `fused_parts` blocks of them)
-    int fused_parts = 0, side_used = 0;
-    const bool fuse = sb && g_fuse_bwd;
-    float* pending_sum = nullptr;   // the slice sum of the layer above is launched together with this layer's BN-backward stage 2 (t_sum_slices_fin)
-    for (int l = c->L - 1; l >= 1; l--) {
-        // gradient w.r.t. this layer's post-activation output: G for the second conv of a block, DT for the first
-        const bool second = (l % 2 == 0);
-        const float* dOut = second ? c->G : c->DT;
-        float* bn = layer_at(w, l) + wn;
+    // gradient w.r.t. layer l's post-activation output: G for the second conv of a block, DT for the first; the conv's input gradient
+    // goes to the other one
+    static bool second(int l) { return l % 2 == 0; }
+    const float* dOut(int l) const { return second(l) ? s.G : s.DT; }
+    float* dIn(int l) const { return second(l) ? s.DT : s.G; }
+
+    // both forms of a layer's backward pass begin with the sums of its batch-norm backward: stage 1 (unless the conv of the layer above
+    // left it), the ranks' sum, stage 2 — with the slice sum that is still pending, in one launch where that is possible
+    int layer_bn_sums(int l, LayerCarry& k) const
+    {
         float* gbn = layer_at(g, l) + wn;
-        const int Rl = fused_parts ? fused_parts : R;
-        if (!fused_parts)
-            hipLaunchKernelGGL((t_bn_bwd_stats<false>), dim3(R), dim3(1024), 0, st, dOut, c->Al(l), c->Yl(l), c->mean + l * NF, c->istd + l * NF, M, c->part);
+        const int Rl = k.fused_parts ? k.fused_parts : R;
+        if (!k.fused_parts)
+            hipLaunchKernelGGL((t_bn_bwd_stats<false>), dim3(R), dim3(1024), 0, st, dOut(l), s.Al(l), s.Yl(l), c->mean + l * NF, c->istd + l * NF, M, s.part);
         if (dp) TRY(reduce_parts(h, c, Rl, 2));
-        if (pending_sum && !dp && fused_parts) {
-            hipLaunchKernelGGL(t_sum_slices_fin, dim3(8 + (unsigned)((wn + 1023) / 1024)), dim3(1024), 0, st, c->wpart, c->wg_parts, wn, pending_sum, c->part,
+        if (k.pending_sum && !dp && k.fused_parts) {
+            hipLaunchKernelGGL(t_sum_slices_fin, dim3(8 + (unsigned)((wn + 1023) / 1024)), dim3(1024), 0, st, s.wpart, s.wg_parts, wn, k.pending_sum, s.part,
                                Rl, gbn, c->sums, gscale);
-            pending_sum = nullptr;
         } else {
-            if (pending_sum) { hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, st, c->wpart, c->wg_parts, wn, pending_sum); pending_sum = nullptr; }
-            hipLaunchKernelGGL((t_bn_bwd_finalize<false>), dim3(8), dim3(1024), 0, st, dp ? c->red : c->part, dp ? 1 : Rl, gbn, c->sums, gscale);
+            if (k.pending_sum) hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, st, s.wpart, s.wg_parts, wn, k.pending_sum);
+            hipLaunchKernelGGL((t_bn_bwd_finalize<false>), dim3(8), dim3(1024), 0, st, dp ? c->red : s.part, dp ? 1 : Rl, gbn, c->sums, gscale);
         }
-        float* dIn = second ? c->DT : c->G;
-        const Parts apP{{c->Ap(l - 1).p[0], c->Ap(l - 1).p[1], nullptr}};
-        if (fuse && g_fuse_apply) {
-            // dY is computed in the backward-data conv's staging path (t_bn_bwd_apply's arithmetic; its two bf16 parts and, where the
-            // layer closes a block, dz = the shortcut gradient DS are written out on the way), so that conv runs FIRST and the
-            // weight-gradient GEMM reads the parts it left behind — on the side stream (TrainCtx::side), from the set of its layer parity
-            const bool beside = convq && !c->native;   // (in-stream RCCL collectives and cross-stream edges do not mix: 16 ms per step measured)
-            const int q = beside ? (l & 1) : 0;
-            uint16_t* const* dq = q ? c->dyp2 : c->dyp;
-            const Parts dyP{{dq[0], dq[1], nullptr}};
-            if (beside && l + 2 <= c->L - 1) HIPCHK(h, hipStreamWaitEvent(st, c->ev_wg[q], 0));   // layer l + 2's weight gradient has read this set
-            const ProFuse pf{dOut, c->Al(l), c->Yl(l), c->mean + l * NF, c->istd + l * NF, bn, c->sums, invM, second ? c->DS : (float*)nullptr, dq[0], dq[1]};
-            const Parts none{{nullptr, nullptr, nullptr}};
-            fused_parts = 0;
-            if (l >= 2) {
-                const BwdFuse bf{second ? (const float*)nullptr : (const float*)c->DS, c->Al(l - 1), c->Yl(l - 1), c->mean + (l - 1) * NF, c->istd + (l - 1) * NF, c->part};
-                fused_parts = launch_conv<2, 1, false, 2>(c, st, none, c->Wpb(l), dIn, bf, 1.0f, pf);
-            } else {
-                launch_conv<2, 0, false, 2>(c, st, none, c->Wpb(l), dIn, BwdFuse{}, 1.0f, pf);
-                if (!second) hipLaunchKernelGGL(t_add, dim3(g4), dim3(256), 0, st, dIn, c->DS, act / 4);
-            }
-            if (!beside) {  // large batches: the chain's kernels and the weight gradient each fill the register files on their own (368 and 280
-                            // VGPRs: no SIMD holds a wave of both) and nothing overlaps: one stream.  (Measured at batch 512: the branch on the
-                            // side stream 11.16 ms per step, only its slice sums there 11.28, one stream 11.1 — a cross-stream edge costs the
-                            // chain a barrier packet per layer, about what hiding the 10-us slice sum saves.)
-                launch_wgrad(c, st, apP, dyP, M);
-                pending_sum = layer_at(g, l);   // summed by the next layer's launch (t_sum_slices_fin), or behind the loop
-                continue;
-            }
-            // small batches (a rank's share of a data-parallel minibatch): the chain's kernels leave most of the chip idle, the branch runs beside them
-            HIPCHK(h, hipEventRecord(c->ev_conv[q], st));
-            HIPCHK(h, hipStreamWaitEvent(c->side, c->ev_conv[q], 0));
-            launch_wgrad(c, c->side, apP, dyP, M);
-            hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, c->side, c->wpart, c->wg_parts, wn, layer_at(g, l));
-            HIPCHK(h, hipEventRecord(c->ev_wg[q], c->side));
-            side_used |= 1 << q;
-            continue;
+        k.pending_sum = nullptr;
+        return AZR_OK;
+    }
+
+    // The product's form (plan.bap).  dY is computed in the backward-data conv's staging path (t_bn_bwd_apply's arithmetic; its two bf16
+    // parts and, where the layer closes a block, dz = the shortcut gradient DS are written out on the way), so that conv runs FIRST and
+    // the weight-gradient GEMM reads the parts it left behind — on the side stream (TrainState::side), from the set of its layer parity
+    int layer_bwd_fused(int l, LayerCarry& k) const
+    {
+        const int L = c->L;
+        const Parts apP{{s.Ap(l - 1).p[0], s.Ap(l - 1).p[1], nullptr}};
+        const bool beside = p.convq && !c->link.native;   // (in-stream RCCL collectives and cross-stream edges do not mix: 16 ms per step measured)
+        const int q = beside ? (l & 1) : 0;
+        uint16_t* const* dq = q ? s.dyp2 : s.dyp;
+        const Parts dyP{{dq[0], dq[1], nullptr}};
+        if (beside && l + 2 <= L - 1) HIPCHK(h, hipStreamWaitEvent(st, c->ev_wg[q], 0));   // layer l + 2's weight gradient has read this set
+        const ProFuse pf{dOut(l), s.Al(l), s.Yl(l), c->mean + l * NF, c->istd + l * NF, layer_at(w, l) + wn, c->sums, invM, second(l) ? s.DS : (float*)nullptr,
+                         dq[0], dq[1]};
+        const Parts none{{nullptr, nullptr, nullptr}};
+        k.fused_parts = 0;
+        if (l >= 2) {
+            const BwdFuse bf{second(l) ? (const float*)nullptr : (const float*)s.DS, s.Al(l - 1), s.Yl(l - 1), c->mean + (l - 1) * NF, c->istd + (l - 1) * NF, s.part};
+            k.fused_parts = launch_conv<2, 1, false, 2>(s, st, none, c->Wpb(l), dIn(l), bf, 1.0f, pf);
+        } else {
+            launch_conv<2, 0, false, 2>(s, st, none, c->Wpb(l), dIn(l), BwdFuse{}, 1.0f, pf);
+            if (!second(l)) hipLaunchKernelGGL(t_add, dim3(g4), dim3(256), 0, st, dIn(l), s.DS, s.act() / 4);
         }
-        const Parts dyP{{c->dyp[0], c->dyp[1], nullptr}};
+        if (!beside) {  // large batches: the chain's kernels and the weight gradient each fill the register files on their own (368 and 280
+                        // VGPRs: no SIMD holds a wave of both) and nothing overlaps: one stream.  (Measured at batch 512: the branch on the
+                        // side stream 11.16 ms per step, only its slice sums there 11.28, one stream 11.1 — a cross-stream edge costs the
+                        // chain a barrier packet per layer, about what hiding the 10-us slice sum saves.)
+            launch_wgrad(s, st, apP, dyP);
+            k.pending_sum = layer_at(g, l);   // summed by the next layer's launch (t_sum_slices_fin), or behind the loop
+            return AZR_OK;
+        }
+        // small batches (a rank's share of a data-parallel minibatch): the chain's kernels leave most of the chip idle, the branch runs beside them
+        HIPCHK(h, hipEventRecord(c->ev_conv[q], st));
+        HIPCHK(h, hipStreamWaitEvent(c->side, c->ev_conv[q], 0));
+        launch_wgrad(s, c->side, apP, dyP);
+        hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, c->side, s.wpart, s.wg_parts, wn, layer_at(g, l));
+        HIPCHK(h, hipEventRecord(c->ev_wg[q], c->side));
+        k.side_used |= 1 << q;
+        return AZR_OK;
+    }
+
+    // The unfused form: normalise kernel, weight gradient, backward-data conv.  In the product library it is reached only by batches whose
+    // row count is no multiple of the 32-deep k-tile: the fp32-MFMA GEMMs.  The split-bf16 kernels WITHOUT the staging-path fusions are
+    // older formulations, compiled into libazr_hip_test.so only.
+    int layer_bwd_unfused(int l, LayerCarry& k) const
+    {
+        const bool sb = p.sb;
+        const Parts apP{{s.Ap(l - 1).p[0], s.Ap(l - 1).p[1], nullptr}}, dyP{{s.dyp[0], s.dyp[1], nullptr}};
         // (the split-bf16 kernels read the two parts of dY; its fp32 image is only written for the fp32-MFMA GEMMs)
-        hipLaunchKernelGGL((t_bn_bwd_apply<false>), dim3(g4), dim3(256), 0, st, dOut, c->Al(l), c->Yl(l), c->mean + l * NF, c->istd + l * NF, bn, c->sums,
-                           invM, sb ? (float*)nullptr : c->dY, second ? c->DS : (float*)nullptr, M, sb ? c->dyp[0] : nil16, c->dyp[1]);
+        hipLaunchKernelGGL((t_bn_bwd_apply<false>), dim3(g4), dim3(256), 0, st, dOut(l), s.Al(l), s.Yl(l), c->mean + l * NF, c->istd + l * NF, layer_at(w, l) + wn,
+                           c->sums, invM, sb ? (float*)nullptr : s.dY, second(l) ? s.DS : (float*)nullptr, M, sb ? s.dyp[0] : nil16, s.dyp[1]);
         // dW = col(input)^T x dY  (implicit im2col, split-K over the M rows)
-        // (In the product library this point is reached only by batches whose row count is no multiple of the 32-deep k-tile: the fp32-MFMA
-        //  GEMMs.  The split-bf16 kernels WITHOUT the staging-path fusions are older formulations, compiled into libazr_hip_test.so only.)
 #ifdef AZR_TEST_HOOKS
         if (sb) {
-            launch_wgrad(c, st, apP, dyP, M);
+            launch_wgrad(s, st, apP, dyP);
         } else
 #endif
-        gemm<true, false, 128, 1, 0>(st, c->Al(l - 1), KC, c->dY, NF, c->wpart, NF, KC, NF, M, c->nz, c->kchunk, wn);
-        hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, st, c->wpart, sb ? c->wg_parts : c->nz, wn, layer_at(g, l));
+        gemm<true, false, 128, 1, 0>(st, s.Al(l - 1), KC, s.dY, NF, s.wpart, NF, KC, NF, M, s.nz, s.kchunk, wn);
+        hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, st, s.wpart, sb ? s.wg_parts : s.nz, wn, layer_at(g, l));
         // d(input) = transposed conv of dY with W: the same implicit GEMM with negated taps and W read as [tap][co] x [ci]
-        fused_parts = 0;
+        k.fused_parts = 0;
 #ifdef AZR_TEST_HOOKS
-        if (fuse && l >= 2) {   // + the shortcut gradient (first conv of a block), + stage 1 of layer l - 1's BN backward
-            fused_parts = (BS + 1) / 2;
-            hipLaunchKernelGGL((t_conv_rs<2, 2, 1>), dim3(fused_parts), dim3(256), 0, st, dyP, c->Wpb(l), dIn, BS,
-                               BwdFuse{second ? (const float*)nullptr : (const float*)c->DS, c->Al(l - 1), c->Yl(l - 1), c->mean + (l - 1) * NF,
-                                       c->istd + (l - 1) * NF, c->part}, 1.0f, ProFuse{});
-            continue;
+        if (p.fuse && l >= 2) {   // + the shortcut gradient (first conv of a block), + stage 1 of layer l - 1's BN backward
+            k.fused_parts = (BS + 1) / 2;
+            hipLaunchKernelGGL((t_conv_rs<2, 2, 1>), dim3(k.fused_parts), dim3(256), 0, st, dyP, c->Wpb(l), dIn(l), BS,
+                               BwdFuse{second(l) ? (const float*)nullptr : (const float*)s.DS, s.Al(l - 1), s.Yl(l - 1), c->mean + (l - 1) * NF,
+                                       c->istd + (l - 1) * NF, s.part}, 1.0f, ProFuse{});
+            return AZR_OK;
         }
-        if (sb) hipLaunchKernelGGL((t_conv_rs<2, 2>), dim3((BS + 1) / 2), dim3(256), 0, st, dyP, c->Wpb(l), dIn, BS, BwdFuse{}, 1.0f, ProFuse{});
+        if (sb) hipLaunchKernelGGL((t_conv_rs<2, 2>), dim3((BS + 1) / 2), dim3(256), 0, st, dyP, c->Wpb(l), dIn(l), BS, BwdFuse{}, 1.0f, ProFuse{});
         else
 #endif
-        gemm<false, true, 64, 2, 3>(st, c->dY, KC, layer_at(w, l), NF, dIn, NF, M, NF, KC);
-        if (!second) hipLaunchKernelGGL(t_add, dim3(g4), dim3(256), 0, st, dIn, c->DS, act / 4);  // + shortcut gradient
+        gemm<false, true, 64, 2, 3>(st, s.dY, KC, layer_at(w, l), NF, dIn(l), NF, M, NF, KC);
+        if (!second(l)) hipLaunchKernelGGL(t_add, dim3(g4), dim3(256), 0, st, dIn(l), s.DS, s.act() / 4);  // + shortcut gradient
+        return AZR_OK;
     }
-    if (pending_sum) hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, st, c->wpart, c->wg_parts, wn, pending_sum);
-    // the weight-gradient branch joins: the stem below reuses its split-K buffer, and the gradient vector is complete behind it
-    for (int q = 0; q < 2; q++) if ((side_used >> q) & 1) HIPCHK(h, hipStreamWaitEvent(st, c->ev_wg[q], 0));
-    {   // stem: parameters only
-        hipLaunchKernelGGL((t_bn_bwd_stats<true>), dim3(R), dim3(1024), 0, st, c->G, c->Al(0), c->Yl(0), c->mean, c->istd, M, c->part);
+
+    // stem: parameters only
+    int stem_backward() const
+    {
+        hipLaunchKernelGGL((t_bn_bwd_stats<true>), dim3(R), dim3(1024), 0, st, s.G, s.Al(0), s.Yl(0), c->mean, c->istd, M, s.part);
         if (dp) TRY(reduce_parts(h, c, R, 2 * NG));
-        hipLaunchKernelGGL((t_bn_bwd_finalize<true>), dim3(NG), dim3(1024), 0, st, dp ? c->red : c->part, dp ? 1 : R, g + OFF_STEM_BN, c->sums, gscale);
-        hipLaunchKernelGGL((t_bn_bwd_apply<true>), dim3(g4), dim3(256), 0, st, c->G, c->Al(0), c->Yl(0), c->mean, c->istd, w + OFF_STEM_BN, c->sums,
-                           1.0f / ((float)BSg * 6 * NF), c->dY, (float*)nullptr, M, nil16, nil16);
-        gemm<true, false>(st, c->col0, KS, c->dY, NF, c->wpart, NF, KS, NF, M, c->nz, c->kchunk, (size_t)KS * NF);
-        hipLaunchKernelGGL(t_sum_slices, grid1((size_t)KS * NF, 256), dim3(256), 0, st, c->wpart, c->nz, (size_t)KS * NF, c->gpad);
+        hipLaunchKernelGGL((t_bn_bwd_finalize<true>), dim3(NG), dim3(1024), 0, st, dp ? c->red : s.part, dp ? 1 : R, g + OFF_STEM_BN, c->sums, gscale);
+        hipLaunchKernelGGL((t_bn_bwd_apply<true>), dim3(g4), dim3(256), 0, st, s.G, s.Al(0), s.Yl(0), c->mean, c->istd, w + OFF_STEM_BN, c->sums,
+                           1.0f / ((float)BSg * 6 * NF), s.dY, (float*)nullptr, M, nil16, nil16);
+        gemm<true, false>(st, s.col0, KS, s.dY, NF, s.wpart, NF, KS, NF, M, s.nz, s.kchunk, (size_t)KS * NF);
+        hipLaunchKernelGGL(t_sum_slices, grid1((size_t)KS * NF, 256), dim3(256), 0, st, s.wpart, s.nz, (size_t)KS * NF, c->gpad);
         hipLaunchKernelGGL(t_stem_unpad, grid1((size_t)9 * 13 * NF, 256), dim3(256), 0, st, c->gpad, g);
+        return AZR_OK;
     }
-    // ---------------- data-parallel: the ranks' gradient vectors add up to the gradient of the whole minibatch (one RCCL
-    //                  all-reduce of count floats: 94.7 MB at B = 20); every rank then takes the same Adam step
-    if (dp) TRY(dp_allreduce(h, c, g, c->count, 0));
-    // ---------------- Adam: with every option at its default, the reference's step; else [norm ->] schedule -> Adam on the clipped
-    //                  gradient (+ EMA), behind the all-reduce so that every rank computes the same norm
-    c->last_default = c->opt_default;
-    if (c->opt_default) {
-        hipLaunchKernelGGL(t_tick_lr, dim3(1), dim3(1), 0, st, c->cur, c->lr);
-        hipLaunchKernelGGL(t_adam, grid1(c->count, 256), dim3(256), 0, st, w, g, c->m, c->v, c->kind, c->count, (const float*)c->lr);
-    } else {
+
+    // Adam: with every option at its default, the reference's step; else [norm ->] schedule -> Adam on the clipped gradient (+ EMA),
+    // behind the all-reduce so that every rank computes the same norm
+    int update() const
+    {
+        c->last_default = c->opt_default;
+        if (c->opt_default) {
+            hipLaunchKernelGGL(t_tick_lr, dim3(1), dim3(1), 0, st, c->cur, c->lr);
+            hipLaunchKernelGGL(t_adam, grid1(c->count, 256), dim3(256), 0, st, w, g, c->m, c->v, c->kind, c->count, (const float*)c->lr);
+            return AZR_OK;
+        }
         const azr_train_options& o = c->opt;
         const float l2x2 = 2.0f * o.l2;
         if (o.clip_norm > 0.0f) {
@@ -910,46 +958,74 @@ int train_step(azr_engine* h, TrainCtx* c, float* d_acc)
             hipLaunchKernelGGL(t_adam_opt<false>, grid1(c->count, 256), dim3(256), 0, st, w, (const float*)g, c->m, c->v, (float*)nullptr, (const uint8_t*)c->kind,
                                c->count, (const float*)c->lr, (const StatRow*)c->row, l2x2, 0.0f);
         }
+        return AZR_OK;
     }
-    hipLaunchKernelGGL(t_tick_batch, dim3(1), dim3(1), 0, st, c->cur, BSg);
-    HIPCHK(h, hipGetLastError());
-    return AZR_OK;
-}
+
+    int run(float* d_acc) const
+    {
+        if (p.sb) {
+            const dim3 pg((unsigned)((wn / 8 + 255) / 256), 2 * c->blocks);
+            hipLaunchKernelGGL((t_pack_w<3>), pg, dim3(256), 0, st, w, 0, c->wpf[0], c->wpf[1], c->wpf[2], p.f16 ? FWD_WSCALE : 0.0f, c->cur + CUR_RANGE);
+            hipLaunchKernelGGL((t_pack_w<2>), pg, dim3(256), 0, st, w, 1, c->wpb[0], c->wpb[1], (uint16_t*)nullptr);
+        }
+        TRY(forward_tower(h, c, true));
+        TRY(heads_forward(d_acc));
+        TRY(heads_backward());
+        LayerCarry k;
+        for (int l = c->L - 1; l >= 1; l--) {
+            TRY(layer_bn_sums(l, k));
+            TRY(p.bap ? layer_bwd_fused(l, k) : layer_bwd_unfused(l, k));
+        }
+        if (k.pending_sum) hipLaunchKernelGGL(t_sum_slices, grid1(wn, 256), dim3(256), 0, st, s.wpart, s.wg_parts, wn, k.pending_sum);
+        // the weight-gradient branch joins: the stem below reuses its split-K buffer, and the gradient vector is complete behind it
+        for (int q = 0; q < 2; q++) if ((k.side_used >> q) & 1) HIPCHK(h, hipStreamWaitEvent(st, c->ev_wg[q], 0));
+        TRY(stem_backward());
+        // data-parallel: the ranks' gradient vectors add up to the gradient of the whole minibatch (one RCCL all-reduce of count floats:
+        // 94.7 MB at B = 20); every rank then takes the same Adam step
+        if (dp) TRY(dp_allreduce(h, c->link, g, c->count, 0));
+        TRY(update());
+        hipLaunchKernelGGL(t_tick_batch, dim3(1), dim3(1), 0, st, c->cur, BSg);
+        HIPCHK(h, hipGetLastError());
+        return AZR_OK;
+    }
+};
 
 // One minibatch step = gather + forward + backward + Adam.  Everything that changes from step to step (minibatch offset, Adam step
 // count, learning rate) lives in device memory; the launches are plain stream launches (replaying the step as a captured hipGraph
 // measured the same: the ~3 us between consecutive kernels is device-side, not host launch cost).
-int run_step(azr_engine* h, TrainCtx* c)
+int run_step(azr_engine* h, TrainState* c)
 {
+    const Slabs& s = *c->slabs;
     c->step++;
     if (c->opt.ema_decay > 0.0f && !c->e) {   // the EMA vector starts as the weights from before its first step
-        TRY(dalloc(h, c, &c->e, c->count));
+        TRY(dalloc(h, c->allocs, &c->e, c->count));
         HIPCHK(h, hipMemcpyAsync(c->e, h->net.d_flat, c->count * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         c->ema_steps = 0;
     }
-    hipLaunchKernelGGL(t_gather, dim3(c->BS), dim3(64), 0, h->stream, c->rec, c->perm, (const int*)c->cur, c->BS, c->in88, c->pit, c->zt);
-    return train_step(h, c, c->loss + 2);
+    hipLaunchKernelGGL(t_gather, dim3(s.BS), dim3(64), 0, h->stream, c->rec, c->perm, (const int*)c->cur, s.BS, s.in88, s.pit, s.zt);
+    return Step{h, c}.run(c->loss + 2);
 }
 
-// The validation pass (inference mode) on the minibatch already gathered into c->in88 / pit / zt: the forward kernels of the step at the
+// The validation pass (inference mode) on the minibatch already gathered into s.in88 / pit / zt: the forward kernels of the step at the
 // step's precision (forward_tower with c->mean / istd / hstat holding the MOVING statistics: t_bn_moving, once per call), then the
-// fused heads (t_head_eval) write the per-record losses to lossb.  Reads the weights, writes only the training context's scratch slabs.
-int eval_step(azr_engine* h, TrainCtx* c, float* lossb)
+// fused heads (t_head_eval) write the per-record losses to lossb.  Reads the weights, writes only scratch.
+int eval_step(azr_engine* h, TrainState* c, float* lossb)
 {
+    const Slabs& s = *c->slabs;
     TRY(forward_tower(h, c, false));
     const float* hp = h->net.d_flat + OFF_BLOCK0 + (size_t)2 * c->blocks * LAYER;
-    hipLaunchKernelGGL(t_head_eval, dim3(c->BS), dim3(256), 0, h->stream, (const float*)c->Al(c->L - 1), hp, (const float*)c->hstat, (const float*)c->pit,
-                       (const float*)c->zt, lossb);
+    hipLaunchKernelGGL(t_head_eval, dim3(s.BS), dim3(256), 0, h->stream, (const float*)s.Al(c->L - 1), hp, (const float*)c->hstat, (const float*)s.pit,
+                       (const float*)s.zt, lossb);
     return AZR_OK;
 }
 
 // Behind an epoch (or a single step): did a conv weight leave the range of the fp16-pair forward conv (t_pack_w's flag: |w| >= 64, or
 // not a number), or did the losses stop being numbers?  Then the device copy of the weights and the optimiser state are poisoned: the
 // call fails loudly, the weights the handle had before the call (its host AZRW copy) are put back and the optimiser state is dropped.
-int step_health(azr_engine* h, TrainCtx* c, float loss_pi, float loss_v)
+int step_health(azr_engine* h, TrainState* c, float loss_pi, float loss_v)
 {
     int flag = 0;
-    HIPCHK(h, hipMemcpyAsync(&flag, c->cur + 3, sizeof flag, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&flag, c->cur + CUR_RANGE, sizeof flag, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!flag && std::isfinite(loss_pi) && std::isfinite(loss_v)) return AZR_OK;
     HIPCHK(h, hipMemcpyAsync(h->net.d_flat, h->flat.data(), h->flat.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -970,30 +1046,41 @@ int finish(azr_engine* h)
     return net_upload(h);
 }
 
-int upload_records(azr_engine* h, TrainCtx* c, const void* rec, size_t n)
+int upload_records(azr_engine* h, TrainState* c, const void* rec, size_t n)
 {
-    if (n > c->rec_cap) {
-        if (c->rec) hipFree(c->rec);
-        c->rec = nullptr; c->rec_cap = 0;
-        HIPCHK(h, hipMalloc((void**)&c->rec, n * 265));
-        c->rec_cap = n;
-    }
-    if (n > c->perm_cap) {
-        if (c->perm) hipFree(c->perm);
-        c->perm = nullptr; c->perm_cap = 0;
-        HIPCHK(h, hipMalloc((void**)&c->perm, n * sizeof(int)));
-        c->perm_cap = n;
-    }
+    TRY(grow(h, (void**)&c->rec, &c->rec_cap, n, 265));
+    TRY(grow(h, (void**)&c->perm, &c->perm_cap, n, sizeof(int)));
     HIPCHK(h, hipMemcpyAsync(c->rec, rec, n * 265, hipMemcpyHostToDevice, h->stream));
     return AZR_OK;
 }
+
+// the call's cursor: the first minibatch, the state's step count, this rank's offset inside a minibatch, a cleared range flag
+int upload_cursor(azr_engine* h, TrainState* c, int rank_offset)
+{
+    int cur[CUR_N] = {};
+    cur[CUR_STEP] = (int)c->step;
+    cur[CUR_RANK] = rank_offset;
+    HIPCHK(h, hipMemcpyAsync(c->cur, cur, sizeof cur, hipMemcpyHostToDevice, h->stream));
+    return AZR_OK;
+}
+
+// The validation pass's buffer vbuf, in floats: this header | batch means [nb][2] | per-record terms [nb * BS][2]
+struct ValHdr {
+    float sum[2];   // t_val_sum: the batch means' sums (policy, value)
+    int range;      // t_pack_w's range flag
+    int pad;
+    int cur[CUR_N];   // t_gather's view of cur: {offset in perm, -, 0, -}
+};
+static_assert(sizeof(ValHdr) == 32 && offsetof(ValHdr, cur) == 16, "the validation buffer's header");
+constexpr size_t val_mean(size_t k) { return sizeof(ValHdr) / sizeof(float) + 2 * k; }             // batch k's two means
+constexpr size_t val_rec(size_t nb, size_t i) { return val_mean(nb) + 2 * i; }                     // record i's two terms
 
 }  // namespace
 
 namespace azr {
 void train_free(azr_engine* h)
 {
-    ctx_free(ctx_of(h));
+    delete ctx_of(h);
     h->train = nullptr;
 }
 }  // namespace azr
@@ -1008,18 +1095,15 @@ extern "C" int azr_nn_train_batch(azr_engine* h, const void* rec265_host, int n,
     if (!h->weights_set) { h->err = "azr_nn_train_batch: no weights"; return AZR_E_STATE; }
     if (!rec265_host || n < 2) { h->err = "azr_nn_train_batch: need a minibatch of at least 2 records"; return AZR_E_INVALID_ARGUMENT; }
     TRY(ctx_ensure(h, n));
-    TrainCtx* c = ctx_of(h);
-    c->world = 1; c->rank = 0; c->ar = nullptr; c->ar_ctx = nullptr; c->native = false;   // (a data-parallel call that failed half-way must not linger)
+    TrainState* c = ctx_of(h);
+    c->link = DpLink{};
     opt_enter(h, c);
     TRY(upload_records(h, c, rec265_host, (size_t)n));
     std::vector<int> id(n);
     for (int i = 0; i < n; i++) id[i] = i;
     HIPCHK(h, hipMemcpyAsync(c->perm, id.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    {
-        const int cur4[4] = {0, (int)c->step, 0, 0};
-        HIPCHK(h, hipMemcpyAsync(c->cur, cur4, sizeof cur4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    TRY(upload_cursor(h, c, 0));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemsetAsync(c->loss + 2, 0, 2 * sizeof(float), h->stream));
     TRY(run_step(h, c));
     float l[2];
@@ -1060,11 +1144,11 @@ static int train_impl(azr_engine* h, const void* rec265_host, size_t n, int epoc
     }
     std::vector<int> order(n);
     for (size_t i = 0; i < n; i++) order[i] = (int)i;
-    TrainCtx* c = nullptr;
+    TrainState* c = nullptr;
     if (batches > 0 && epochs > 0) {
         TRY(ctx_ensure(h, local_bs));
         c = ctx_of(h);
-        c->world = world; c->rank = rank; c->ar = ar; c->ar_ctx = ar_ctx; c->native = native;
+        c->link = DpLink{world, rank, ar, ar_ctx, native};
         opt_enter(h, c);
         TRY(upload_records(h, c, rec265_host, n));
     }
@@ -1073,23 +1157,22 @@ static int train_impl(azr_engine* h, const void* rec265_host, size_t n, int epoc
         std::shuffle(order.begin(), order.end(), eng);  // alphazero_nn.cpp:372 (same libstdc++ algorithm, same engine)
         float l[2] = {NAN, NAN};
         if (batches > 0) {
-            const int cur4[4] = {0, (int)c->step, rank * local_bs, 0};   // minibatch offset, Adam step count, this rank's slice, range flag
             HIPCHK(h, hipMemcpyAsync(c->perm, order.data(), n * sizeof(int), hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipMemsetAsync(c->loss + 2, 0, 2 * sizeof(float), h->stream));
-            HIPCHK(h, hipMemcpyAsync(c->cur, cur4, sizeof cur4, hipMemcpyHostToDevice, h->stream));
+            TRY(upload_cursor(h, c, rank * local_bs));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             for (size_t b = 0; b < batches && rc == AZR_OK; b++) rc = run_step(h, c);
             if (rc) break;
             HIPCHK(h, hipMemcpyAsync(l, c->loss + 2, sizeof l, hipMemcpyDeviceToHost, h->stream));
             rc = step_health(h, c, l[0], l[1]);   // (synchronises the stream)
-            if (rc) { c = nullptr; break; }       // (the training context is gone with the poisoned optimiser state)
+            if (rc) { c = nullptr; break; }       // (the state is gone with the poisoned optimiser state)
             l[0] /= (float)batches;
             l[1] /= (float)batches;
         }
         if (loss_pi_host) loss_pi_host[e] = l[0];
         if (loss_v_host) loss_v_host[e] = l[1];
     }
-    if (c) { c->world = 1; c->rank = 0; c->ar = nullptr; c->ar_ctx = nullptr; c->native = false; }
+    if (c) c->link = DpLink{};
     if (rc) return rc;
     if (shuffle_rng_state) {
         // minstd_rand0 has no state accessor; operator<< prints the state as decimal text
@@ -1116,7 +1199,7 @@ extern "C" int azr_nn_train_dp(azr_engine* h, const void* rec265_host, size_t n,
 }
 
 // The validation phase of AlphaZeroNN::trainCrossValidation (alphazero_nn.cpp:512-548): every batch of the call is queued back to back
-// (gather with the device-side offset vbuf cur, eval_step), then the batch means and their sum; one read-back at the end.  The handle's
+// (gather with the device-side offset ValHdr::cur, eval_step), then the batch means and their sum; one read-back at the end.  The handle's
 // state — weights, moving statistics, Adam moments, step count, inference images — is only read.
 extern "C" int azr_nn_validate(azr_engine* h, const void* rec265_host, size_t n, int batch_size, float* loss_pi_out, float* loss_v_out,
                                float* rec_loss_pi_host, float* rec_loss_v_host)
@@ -1132,58 +1215,52 @@ extern "C" int azr_nn_validate(azr_engine* h, const void* rec265_host, size_t n,
     }
     if (nb * (size_t)batch_size > (size_t)INT32_MAX) { h->err = "azr_nn_validate: too many records for one call"; return AZR_E_INVALID_ARGUMENT; }
     TRY(ctx_ensure(h, batch_size));
-    TrainCtx* c = ctx_of(h);
+    TrainState* c = ctx_of(h);
+    const Slabs& s = *c->slabs;
     hipStream_t st = h->stream;
     const int BS = batch_size, B = c->blocks;
     const size_t nrec = nb * (size_t)BS;
-    constexpr size_t HDR = 8;   // sums[2], range flag, pad, cur[4]
-    const size_t need = HDR + 2 * nb + 2 * nrec;
-    if (need > c->vbuf_cap) {
-        if (c->vbuf) hipFree(c->vbuf);
-        c->vbuf = nullptr; c->vbuf_cap = 0;
-        HIPCHK(h, hipMalloc((void**)&c->vbuf, need * sizeof(float)));
-        c->vbuf_cap = need;
-    }
-    float* means = c->vbuf + HDR;
-    float* lossb = means + 2 * nb;
-    int* flag = reinterpret_cast<int*>(c->vbuf + 2);
-    int* vcur = reinterpret_cast<int*>(c->vbuf + 4);   // {offset in perm, -, 0, -}: t_gather's view of cur
+    const size_t need = val_rec(nb, nrec);
+    TRY(grow(h, (void**)&c->vbuf, &c->vbuf_cap, need, sizeof(float)));
+    ValHdr* hdr = reinterpret_cast<ValHdr*>(c->vbuf);   // (a device address: only its members' addresses are taken here)
+    float* means = c->vbuf + val_mean(0);
+    float* lossb = c->vbuf + val_rec(nb, 0);
     TRY(upload_records(h, c, rec265_host, nrec));
     std::vector<int> id(nrec);
     for (size_t i = 0; i < nrec; i++) id[i] = (int)i;
     HIPCHK(h, hipMemcpyAsync(c->perm, id.data(), nrec * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemsetAsync(c->vbuf, 0, HDR * sizeof(float), st));
+    HIPCHK(h, hipMemsetAsync(hdr, 0, sizeof(ValHdr), st));
     // once per call: the moving statistics into the statistics slots, the padded stem kernel, the packed forward kernels
     const float* w = h->net.d_flat;
     hipLaunchKernelGGL(t_bn_moving, dim3(c->L + 1), dim3(256), 0, st, w, c->L, c->mean, c->istd, c->hstat);
     hipLaunchKernelGGL(t_stem_pad, grid1((size_t)KS * NF, 256), dim3(256), 0, st, w, c->wpad);
-    if (c->plan.sb) {
+    if (s.plan.sb) {
         const dim3 pg((unsigned)((WPACK / 8 + 255) / 256), 2 * B);
-        hipLaunchKernelGGL((t_pack_w<3>), pg, dim3(256), 0, st, w, 0, c->wpf[0], c->wpf[1], c->wpf[2], c->plan.f16 ? FWD_WSCALE : 0.0f, flag);
+        hipLaunchKernelGGL((t_pack_w<3>), pg, dim3(256), 0, st, w, 0, c->wpf[0], c->wpf[1], c->wpf[2], s.plan.f16 ? FWD_WSCALE : 0.0f, &hdr->range);
     }
     for (size_t k = 0; k < nb; k++) {
-        hipLaunchKernelGGL(t_gather, dim3(BS), dim3(64), 0, st, c->rec, c->perm, (const int*)vcur, BS, c->in88, c->pit, c->zt);
-        hipLaunchKernelGGL(t_tick_batch, dim3(1), dim3(1), 0, st, vcur, BS);
+        hipLaunchKernelGGL(t_gather, dim3(BS), dim3(64), 0, st, c->rec, c->perm, (const int*)hdr->cur, BS, s.in88, s.pit, s.zt);
+        hipLaunchKernelGGL(t_tick_batch, dim3(1), dim3(1), 0, st, hdr->cur, BS);
         TRY(eval_step(h, c, lossb + k * 2 * BS));
     }
     hipLaunchKernelGGL(t_val_means, dim3((unsigned)nb), dim3(256), 0, st, (const float*)lossb, BS, means);
-    hipLaunchKernelGGL(t_val_sum, dim3(1), dim3(1), 0, st, (const float*)means, (int)nb, c->vbuf);
+    hipLaunchKernelGGL(t_val_sum, dim3(1), dim3(1), 0, st, (const float*)means, (int)nb, hdr->sum);
     HIPCHK(h, hipGetLastError());
     const bool per_record = rec_loss_pi_host || rec_loss_v_host;
-    std::vector<float> out(per_record ? need : HDR);
+    std::vector<float> out(per_record ? need : val_mean(0));
     HIPCHK(h, hipMemcpyAsync(out.data(), c->vbuf, out.size() * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    int range = 0;
-    memcpy(&range, &out[2], sizeof range);
-    if (range) {
+    ValHdr got;
+    memcpy(&got, out.data(), sizeof got);
+    if (got.range) {
         h->err = "azr_nn_validate: a conv weight is outside the range of the fp16-pair forward conv (|w| must stay below 64) or is not a number";
         return AZR_E_INVALID_ARGUMENT;
     }
-    if (loss_pi_out) *loss_pi_out = out[0] / (float)nb;
-    if (loss_v_out) *loss_v_out = out[1] / (float)nb;
+    if (loss_pi_out) *loss_pi_out = got.sum[0] / (float)nb;
+    if (loss_v_out) *loss_v_out = got.sum[1] / (float)nb;
     for (size_t i = 0; per_record && i < nrec; i++) {
-        if (rec_loss_pi_host) rec_loss_pi_host[i] = out[HDR + 2 * nb + 2 * i];
-        if (rec_loss_v_host) rec_loss_v_host[i] = out[HDR + 2 * nb + 2 * i + 1];
+        if (rec_loss_pi_host) rec_loss_pi_host[i] = out[val_rec(nb, i)];
+        if (rec_loss_v_host) rec_loss_v_host[i] = out[val_rec(nb, i) + 1];
     }
     return AZR_OK;
 }
@@ -1238,7 +1315,7 @@ extern "C" int azr_dp_init(azr_engine* h, int rank, int world, const void* id128
 extern "C" int azr_nn_train_grads(azr_engine* h, float* flat_host, size_t count)
 {
     ENTER(h);
-    TrainCtx* c = ctx_of(h);
+    TrainState* c = ctx_of(h);
     if (!c) { h->err = "azr_nn_train_grads: no training step has run"; return AZR_E_STATE; }
     if (!flat_host || count != c->count) return AZR_E_INVALID_ARGUMENT;
     HIPCHK(h, hipMemcpy(flat_host, c->g, count * sizeof(float), hipMemcpyDeviceToHost));
@@ -1291,7 +1368,7 @@ extern "C" int azr_nn_train_get_options(azr_engine* h, azr_train_options* o)
 extern "C" int azr_nn_train_stats(azr_engine* h, azr_train_stats* out)
 {
     ENTER(h);
-    TrainCtx* c = ctx_of(h);
+    TrainState* c = ctx_of(h);
     if (!c || c->step == 0) { h->err = "azr_nn_train_stats: no training step has run"; return AZR_E_STATE; }
     if (!out) { h->err = "azr_nn_train_stats: no destination"; return AZR_E_INVALID_ARGUMENT; }
     StatRow row;
@@ -1311,7 +1388,7 @@ extern "C" int azr_nn_train_stats(azr_engine* h, azr_train_stats* out)
 extern "C" int azr_nn_get_ema_weights(azr_engine* h, float* flat_host, size_t count)
 {
     ENTER(h);
-    TrainCtx* c = ctx_of(h);
+    TrainState* c = ctx_of(h);
     if (!c || !c->e) { h->err = "azr_nn_get_ema_weights: there is no EMA vector (no step has run with ema_decay > 0 since the optimiser state was created)"; return AZR_E_STATE; }
     if (!flat_host || count != c->count) { h->err = "azr_nn_get_ema_weights: count must be azr_nn_param_count"; return AZR_E_INVALID_ARGUMENT; }
     HIPCHK(h, hipMemcpy(flat_host, c->e, count * sizeof(float), hipMemcpyDeviceToHost));

@@ -164,7 +164,8 @@ int azr_dp_init(azr_engine* h, int rank, int world, const void* id128);
 int azr_dp_shutdown(azr_engine* h);
 /* one `session->Run(..., {optimize})` (alphazero_nn.cpp:389-391) on exactly n records in the given order */
 int azr_nn_train_batch(azr_engine* h, const void* rec265_host, int n, float* loss_pi, float* loss_v);
-/* diagnostics: gradient vector of the last step in AZRW layout (moving-statistics slots unused) */
+/* diagnostics: gradient vector of the last step in AZRW layout (moving-statistics slots unused): the last STEP's, whatever was
+ * rebuilt since */
 int azr_nn_train_grads(azr_engine* h, float* flat_host, size_t count);
 /* drop the optimiser state and the training buffers */
 int azr_nn_train_reset(azr_engine* h);
