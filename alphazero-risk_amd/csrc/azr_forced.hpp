@@ -17,7 +17,7 @@ constexpr float FORCED_K_MAX = 8.0f;   // azr_*_set_forced_playouts reject a lar
 
 __device__ __forceinline__ float forced_nf(float k, float noiseP, uint32_t sumN)
 {
-    return __fsqrt_rn(__fmul_rn(__fmul_rn(k, noiseP), (float)sumN));
+    return sqrtf(__fmul_rn(__fmul_rn(k, noiseP), (float)sumN));
 }
 
 // a legal move that has been tried and is still short of its forced count (a NaN nf — negative noiseP — forces nothing)
@@ -41,7 +41,7 @@ __device__ __forceinline__ uint32_t prune_counts(uint32_t N, float Q, float nois
     const uint32_t l = lane_id();
     const bool ok = l < (uint32_t)MOVES && ((valid >> l) & 1ULL);
     if (valid == 0) return N;
-    const float v = __fmul_rn(__fmul_rn(noiseP, hp), __fsqrt_rn(__fadd_rn(1.0f, (float)sumN)));
+    const float v = __fmul_rn(__fmul_rn(noiseP, hp), sqrtf(__fadd_rn(1.0f, (float)sumN)));
     const uint32_t top = wave_max_u32(ok ? N : 0u);
     const uint32_t cstar = (uint32_t)ctz64(ballot64(ok && N == top));   // the most visited legal move, lowest index on ties
     const float ustar = rdlf(__fadd_rn(Q, __fdiv_rn(v, __fadd_rn(1.0f, (float)N))), cstar);

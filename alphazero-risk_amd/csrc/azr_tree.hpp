@@ -385,7 +385,9 @@ __device__ __forceinline__ uint32_t tree_select(const Tree& t, uint32_t idx, con
     const uint32_t N = W & N_MASK, act = W >> 24;
     if (l == 0) t.touch[idx] = stamp;  // visited = true
     const float noiseP = (NOISE && root_level) ? __fadd_rn(__fmul_rn(S.c1, P), __fmul_rn(eps, eta)) : __fadd_rn(__fmul_rn(S.c1, P), S.c2);
-    const float v = __fmul_rn(__fmul_rn(noiseP, S.hp), __fsqrt_rn(__fadd_rn(1.0f, (float)sumN)));
+    // sqrtf, not __fsqrt_rn: that intrinsic is the hardware's approximate root here (1 ulp), sqrtf the correctly rounded one of the
+    // reference.  The ulp decides which of two siblings with Q = 1 and Q = 1 - 2^-24 on equal priors is searched first.
+    const float v = __fmul_rn(__fmul_rn(noiseP, S.hp), sqrtf(__fadd_rn(1.0f, (float)sumN)));
     const float nn = __fadd_rn(1.0f, (float)N);
     float u = __fadd_rn(Q, __fdiv_rn(v, nn));
     const bool ok = l < MOVES && ((valid >> l) & 1ULL);

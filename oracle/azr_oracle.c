@@ -1188,16 +1188,52 @@ void orc_net_forward_mt(const orc_net* net, const uint8_t* in88, int n, float* p
 void orc_net_eval(void* ctx, const uint8_t* in88, float* pi43, float* v) { net_forward_one((const orc_net*)ctx, in88, pi43, v); }
 
 /* stub nets for tree-only parity tests */
+static void hash_priors(uint64_t* s, float* pi)
+{
+    float sum = 0.0f;
+    for (int i = 0; i < 43; i++) { pi[i] = 0.5f + (float)((splitmix64(s) >> 40) * (1.0 / 16777216.0)); sum += pi[i]; }
+    for (int i = 0; i < 43; i++) pi[i] /= sum;
+}
+static float hash_value(uint64_t* s) { return (float)((splitmix64(s) >> 40) * (1.0 / 16777216.0)) * 2.0f - 1.0f; }
 void orc_hash_eval(void* ctx, const uint8_t* in88, float* pi, float* v)
 {
     (void)ctx;
     uint64_t h = 0xcbf29ce484222325ULL;
     for (int i = 0; i < 88; i++) { h ^= in88[i]; h *= 0x100000001b3ULL; }
     uint64_t s = h;
-    float sum = 0.0f;
-    for (int i = 0; i < 43; i++) { pi[i] = 0.5f + (float)((splitmix64(&s) >> 40) * (1.0 / 16777216.0)); sum += pi[i]; }
-    for (int i = 0; i < 43; i++) pi[i] /= sum;
-    *v = (float)((splitmix64(&s) >> 40) * (1.0 / 16777216.0)) * 2.0f - 1.0f;
+    hash_priors(&s, pi);
+    *v = hash_value(&s);
+}
+/* what a trained net puts out, per position hash: one-hot and two-peak priors, exact zeros, fp32 denormals, an all-zero row, with
+ * saturated values.  Modes 4 and value 5 are orc_hash_eval's formulas on the stream that follows r.  No negative prior and no NaN:
+ * those are not net outputs. */
+void orc_sharp_eval(void* ctx, const uint8_t* in88, float* pi, float* v)
+{
+    (void)ctx;
+    uint64_t h = 0xcbf29ce484222325ULL;
+    for (int i = 0; i < 88; i++) { h ^= in88[i]; h *= 0x100000001b3ULL; }
+    uint64_t s = h;
+    uint64_t r = splitmix64(&s);
+    int mode = (int)(r % 8), a = (int)((r >> 8) % 43), b = (int)((r >> 16) % 43), vm = (int)((r >> 24) % 6);
+    for (int i = 0; i < 43; i++) pi[i] = 0.0f;
+    switch (mode) {
+    case 0: pi[a] = 1.0f; break;
+    case 1: pi[a] = pi[b] = 0.5f; break;
+    case 2: for (int i = 0; i < 43; i++) pi[i] = ldexpf(1.0f, -4 * ((7 * i + a) % 43)); break;         /* normal, denormal, zero */
+    case 3: for (int i = 0; i < 43; i++) pi[i] = ldexpf(1.0f + (float)((5 * i + b) % 8) / 8.0f, -140 - i % 8); break; /* denormal */
+    case 4: hash_priors(&s, pi); break;
+    case 5: for (int i = 0; i < 43; i++) pi[i] = 1.0f / 43.0f; break;
+    case 6: break;
+    default: for (int i = 0; i < 43; i++) pi[i] = ldexpf(1.0f, -((11 * i + b) % 43)); break;
+    }
+    switch (vm) {
+    case 0: *v = 1.0f; break;
+    case 1: *v = -1.0f; break;
+    case 2: *v = 0.0f; break;
+    case 3: *v = 0.99999994f; break;
+    case 4: *v = -0.99999994f; break;
+    default: *v = hash_value(&s); break;
+    }
 }
 void orc_uniform_eval(void* ctx, const uint8_t* in88, float* pi, float* v)
 {

@@ -224,6 +224,10 @@ int orc_bench_selfplay(const orc_settings* cfg, const orc_net* net, uint32_t bas
 void orc_hash_eval(void* ctx, const uint8_t* in88, float* pi43, float* v);
 /* uniform stub: every prior identical (forces the unordered_map tie-break path), v = 0 */
 void orc_uniform_eval(void* ctx, const uint8_t* in88, float* pi43, float* v);
+/* sharp stub: per position hash one of eight prior shapes (one-hot, two peaks of 0.5, powers of two down through the denormals to
+ * exact zero, denormals only, orc_hash_eval's, uniform, all zero, 2^-k for k < 43) and one of six values (+1, -1, 0, the fp32
+ * neighbours of +-1, orc_hash_eval's): the outputs of a trained net, which the near-uniform stubs above never give */
+void orc_sharp_eval(void* ctx, const uint8_t* in88, float* pi43, float* v);
 /* orc_net adaptor: ctx = orc_net* */
 void orc_net_eval(void* ctx, const uint8_t* in88, float* pi43, float* v);
 

@@ -222,6 +222,52 @@ def make_net_flat(blocks, seed=20260002, perturb_bn=False):
     return flat
 
 
+_boards = {}
+
+
+def distinct_boards(n):
+    """n evenly spaced distinct encode.npz boards [n, 88] (read-only, shared)"""
+    if n not in _boards:
+        g = np.unique(np.load(os.path.join(GOLDEN, "encode.npz"))["in88"], axis=0)
+        x = g[np.linspace(0, len(g) - 1, n).astype(int)].copy()
+        assert len(np.unique(x, axis=0)) == n
+        x.setflags(write=False)
+        _boards[n] = x
+    return _boards[n]
+
+
+def orc_forward(blocks, flat, x, threads=8):
+    """the oracle's fp32 CPU net on the boards x: (pi [n, 43], v [n])"""
+    net = OrcNet(blocks, flat.ctypes.data_as(f32p))
+    pi, v = np.zeros((len(x), 43), np.float32), np.zeros(len(x), np.float32)
+    xx = np.ascontiguousarray(x)
+    oracle().orc_net_forward_mt(C.byref(net), ptr(xx), len(xx), ptr(pi), ptr(v), threads)
+    return pi, v
+
+
+_sharp = {}
+
+
+def make_sharp_net_flat(blocks, seed, kp=8, kv=10):
+    """make_net_flat(perturb_bn=True) with the heads of a trained net: the value head centred (v2_b less the median of atanh(v) over
+    512 distinct boards, in float64) and scaled by 2^kv, the policy logits scaled by 2^kp.  Its softmax gives exact zeros, fp32
+    denormals and an exact 1, often on an illegal move; its tanh saturates to +-1.  Only head parameters change (powers of two but
+    for the one bias), so the MFMA towers take the vector as they take the base net's."""
+    key = (blocks, seed, kp, kv)
+    if key not in _sharp:
+        flat = make_net_flat(blocks, seed, perturb_bn=True)
+        off = {name: (o, n) for name, o, n in _layout(blocks)[0]}
+        _, v = orc_forward(blocks, flat, distinct_boards(512))
+        o, n = off["v2_b"]
+        flat[o] = np.float32(np.float64(flat[o]) - np.median(np.arctanh(v.astype(np.float64))))
+        for name, k in (("pd_w", kp), ("pd_b", kp), ("v2_w", kv), ("v2_b", kv)):
+            o, n = off[name]
+            flat[o:o + n] = np.ldexp(flat[o:o + n], k)
+        flat.setflags(write=False)
+        _sharp[key] = flat
+    return _sharp[key].copy()
+
+
 def _layout(blocks):
     F = 256
     off = 0
@@ -411,24 +457,32 @@ def lowest_unvisited(valid, n):
 _tree_runs = {}
 
 
-def orc_tree_run(sims, threads, limit=0, unvisited=False, stride=1):
-    """TREE_DECISIONS decisions per golden root in the oracle (orc_hash_eval, sampling on odd steps) with a node limit (0 = none),
-    recorded per decision: N, Q, P, policy, the picked move, the move played, the next state and the RNG.  `unvisited`: the move
+def stub_fn(name):
+    """an oracle stub net by name, callable from Python"""
+    f = getattr(oracle(), name)
+    f.argtypes = [C.c_void_p, u8p, f32p, C.c_void_p]
+    return f
+
+
+def orc_tree_run(sims, threads, limit=0, unvisited=False, stride=1, stub="orc_hash_eval"):
+    """TREE_DECISIONS decisions per golden root in the oracle (stub net `stub`, sampling on odd steps) with a node limit (0 = none),
+    recorded per decision: the legal moves, N, Q, P, policy, the picked move, the move played, the next state and the RNG.  `unvisited`: the move
     played is the lowest legal one with N == 0 where there is one (its outcome is a root the search never expanded).  Computed once
     per setting and shared; callers must not write into it."""
-    key = (sims, threads, limit, unvisited, stride)
+    key = (sims, threads, limit, unvisited, stride, stub)
     if key in _tree_runs:
         return _tree_runs[key]
     L = oracle()
     states, seeds = tree_roots(stride)
     G = len(states)
     cfg = default_settings(mcts_simulations=sims, mcts_threads=threads)
-    evalfn = C.cast(L.orc_hash_eval, C.c_void_p)
+    evalfn = C.cast(getattr(L, stub), C.c_void_p)
     D = TREE_DECISIONS
-    run = dict(sims=sims, threads=threads, limit=limit, unvisited=unvisited, stride=stride, G=G,
+    run = dict(sims=sims, threads=threads, limit=limit, unvisited=unvisited, stride=stride, stub=stub, G=G,
                alive=np.zeros((D, G), bool), n=np.zeros((D, G, 43), np.uint32), q=np.zeros((D, G, 43), np.float32),
                p=np.zeros((D, G, 43), np.float32), pi=np.zeros((D, G, 43), np.float32), picked=np.full((D, G), 255, np.uint8),
                played=np.full((D, G), 255, np.uint8), after=np.zeros((D, G, 160), np.uint8), rng=np.zeros((D, G), np.uint32),
+               valid=np.zeros((D, G), np.uint64),
                peak=0, dropped=0, evictions=0, sims_per_search=set())
     for g in range(G):
         s, r = OrcState(), OrcRng()
@@ -439,6 +493,7 @@ def orc_tree_run(sims, threads, limit=0, unvisited=False, stride=1):
         for step in range(D):
             if L.orc_game_status(C.byref(s), C.byref(cfg)) == -1:
                 run["alive"][step, g] = True
+                run["valid"][step, g] = L.orc_valid_moves(C.byref(s), C.byref(cfg))
                 before = L.orc_mcts_sim_count(m)
                 assert L.orc_mcts_simulate(m, C.byref(s), C.byref(r), evalfn, None) == 0
                 run["sims_per_search"].add(L.orc_mcts_sim_count(m) - before)
@@ -460,6 +515,25 @@ def orc_tree_run(sims, threads, limit=0, unvisited=False, stride=1):
         L.orc_mcts_destroy(m)
     _tree_runs[key] = run
     return run
+
+
+FLT_MIN = np.float32(1.17549435e-38)
+
+
+def sharp_census(n, q, p):
+    """of searched roots given as rows of N, Q and normalised P [roots, 43]: (roots, those whose legal priors are all zero, those
+    with a denormal prior, those with a visited move of |Q| == 1).  Illegal entries of P are 0 after the normalisation."""
+    return (len(p), int((p == 0).all(1).sum()), int(((p > 0) & (p < FLT_MIN)).any(1).sum()),
+            int(((n > 0) & (np.abs(q) == 1)).any(1).sum()))
+
+
+def assert_sharp_regime(census):
+    """the regime guard: at least 10 % of the roots with an all-zero legal prior, at least 10 roots with a denormal prior and at
+    least 50 % with a visited |Q| == 1 (a stub that drifts back to near-uniform priors and unsaturated values fails here)"""
+    roots, zero, den, sat = census
+    print("sharp regime: %d roots, all legal priors zero %d (%.1f %%), a denormal prior %d, a visited |Q| == 1 %d (%.1f %%)"
+          % (roots, zero, 100.0 * zero / roots, den, sat, 100.0 * sat / roots))
+    assert zero >= 0.10 * roots and den >= 10 and sat >= 0.50 * roots, census
 
 
 def engine_stub_search(eng, stub, max_passes):
@@ -486,11 +560,9 @@ def host_stub_search(eng, orc, stub):
 
 
 def engine_matches_tree_run(eng, run):
-    """plays the recorded decisions on the engine (host-stepped, orc_hash_eval) and compares N, Q, P, the policy, the picked move, the
-    next state and the RNG with the oracle's, bit for bit, per decision and game"""
-    L = oracle()
-    stub = L.orc_hash_eval
-    stub.argtypes = [C.c_void_p, u8p, f32p, C.c_void_p]
+    """plays the recorded decisions on the engine (host-stepped, the run's stub net) and compares N, Q, P, the policy, the picked move,
+    the next state and the RNG with the oracle's, bit for bit, per decision and game"""
+    stub = stub_fn(run["stub"])
     states, seeds = tree_roots(run["stride"])
     G = run["G"]
     assert eng.G == G and eng.T == run["threads"]

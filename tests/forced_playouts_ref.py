@@ -1,7 +1,7 @@
 """Forced playouts and policy target pruning at the root, restated from include/azr.h in np.float32 (TEST INFRASTRUCTURE).
 
 Every operation is one fp32 operation on np.float32 operands, in the order the header writes them, so each is rounded on its own as
-the device's __fmul_rn / __fadd_rn / __fsqrt_rn / __fdiv_rn are.  puct_pick is tree_select's root-level selection with a root vector
+the device's __fmul_rn / __fadd_rn / sqrtf / __fdiv_rn are.  puct_pick is tree_select's root-level selection with a root vector
 (the restatement tests/test_gpu_root_noise.py checks against the device); forced_pick is the same selection run over the forced moves
 alone where there are any; prune_counts is the header's loop; root_policy is calculateMoveProbability(1.0f)."""
 import numpy as np

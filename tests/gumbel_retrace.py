@@ -18,7 +18,7 @@ def retrace(run, m, tree):
     key = ("retrace", run._replace(surprise=None, value_mix=None), m, tree)
     if key in _cache:
         return _cache[key]
-    eng = SR.engine(run.threads, run.sims)
+    eng = SR.engine(run.threads, run.sims, net=run.net)
     eng.set_gumbel(m, CV, CS)
     eng.set_gumbel_tree(tree)
     states, rngs = SR.late_positions()

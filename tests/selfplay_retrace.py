@@ -3,7 +3,8 @@ self-play and retraced decision by decision through the host-stepped entry point
 must hold every retraced game's records, bit for bit and side by side.  A Run names the games and the options in force; selfplay and
 retrace take it; the option under test turns the retrace's arrays into the stream it expects with its own restatement (surprise_ref,
 value_mix_ref) and hands it to assert_streams.  What a Run gave is computed once per process (cached); callers must not write into it.
-Engines of one block, NET_F32, the weights of make_net_flat(1, seed=11, perturb_bn=True)."""
+Engines of one block, NET_F32; the weights are the Run's: make_net_flat(1, seed=11, perturb_bn=True), or the sharp net of that seed
+(azr_testlib.make_sharp_net_flat: priors of exactly 0 and 1, often on illegal moves, and values of exactly +-1)."""
 import os
 from typing import NamedTuple, Optional, Tuple
 
@@ -30,6 +31,7 @@ class Run(NamedTuple):
     forced: Optional[Tuple[float, bool]] = None           # (k, prune)
     surprise: Optional[Tuple[float, float, int]] = None   # (share, max_weight, seed)
     value_mix: Optional[float] = None                     # q_share
+    net: str = "base"                                     # the weights: a key of NETS
 
 
 class Game(NamedTuple):
@@ -52,10 +54,13 @@ def late_positions(slots=G):
     return states, np.arange(600, 600 + slots, dtype=np.uint32)
 
 
-def engine(threads, sims, slots=G, **settings):
+NETS = {"base": lambda: T.make_net_flat(1, seed=11, perturb_bn=True), "sharp": lambda: T.make_sharp_net_flat(1, seed=11)}
+
+
+def engine(threads, sims, slots=G, net="base", **settings):
     P = pkg()
     eng = P.Engine(slots, blocks=1, sims=sims, dtype=P.NET_F32, threads=threads, **settings)
-    eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
+    eng.set_weights(NETS[net]())
     return eng
 
 
@@ -87,7 +92,7 @@ def place(eng, run):
 
 def selfplay(run, configure=None):
     """a new engine with the run's options set, then configure(eng) for what the test itself does to the setters, started"""
-    eng = engine(run.threads, run.sims)
+    eng = engine(run.threads, run.sims, net=run.net)
     if run.dirichlet:
         eng.selfplay_set_dirichlet(*run.dirichlet)
     if run.forced:
@@ -114,7 +119,7 @@ def retrace(run):
     with Dirichlet noise, forced playouts or a cap in force the vector of azr_debug_root_noise (or the constant: a fast decision, and
     every decision without Dirichlet noise), the factor and the budget of that kind (with none of them no setter is called); one search;
     the pruned policy into the record where the run prunes, the unpruned pick as the move.  ([Game], totals)"""
-    eng = engine(run.threads, run.sims)
+    eng = engine(run.threads, run.sims, net=run.net)
     states, rngs = late_positions()
     dnv, thr = f32(eng.settings.dir_noise_value), eng.settings.temperature_threshold
     k, prune = run.forced or (0.0, False)

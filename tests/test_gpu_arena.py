@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import azr_testlib as T
-from gpu_common import half_slot as _half_slot, pkg, run_arena
+from gpu_common import concurrent_two_net_arena, half_slot as _half_slot, pkg, run_arena
 
 pytestmark = pytest.mark.gpu
 FM = T.data_field_mask()
@@ -199,47 +199,7 @@ def test_concurrent_pair_halves_script_and_random_bit_exact(orc, kinds):
 def test_concurrent_pair_halves_two_net_arena_bit_exact_with_samples(orc, threads, b_first):
     """the learn loop's new-vs-old comparison in the concurrent form: results, final states, rounds and every (s, pi, z) record of
     both AlphaZero players against the oracle's slots, the two DEVICE nets called back per evaluation"""
-    P = pkg()
-    G, per_slot, S, B, base = 6, 2, 12, 1, 6100
-    a = P.Engine(G, blocks=B, sims=S, dtype=P.NET_BF16, threads=threads, max_game_rounds=40)
-    b = P.Engine(G, blocks=B, sims=S, dtype=P.NET_BF16, threads=threads, max_game_rounds=40)
-    a.set_weights(T.make_net_flat(B, seed=31, perturb_bn=True))
-    b.set_weights(T.make_net_flat(B, seed=32, perturb_bn=True))
-    a.arena_set_opponent(b)
-    a.arena_collect_samples(True)
-    k = (P.PLAYER_ALPHAZERO_B, P.PLAYER_ALPHAZERO) if b_first else (P.PLAYER_ALPHAZERO, P.PLAYER_ALPHAZERO_B)
-    res, (n, st, rd, fin) = run_arena(a, k[0], k[1], 10 ** 6, per_slot, P.MIRROR_CONCURRENT, base)
-    assert (n == per_slot).all() and a.counters()["errors"] == 0 and a.counters()["nodes_dropped"] == 0
-    recs = a.drain()
-
-    def make_eval(eng):
-        @T.EVAL_FN
-        def f(ctx, in88, pi, v):
-            x = np.ctypeslib.as_array(in88, shape=(88,)).copy()[None]
-            p, vv = eng.predict(x)
-            C.memmove(pi, p.ctypes.data, 43 * 4)
-            v[0] = float(vv[0])
-        return f
-
-    ea, eb = make_eval(a), make_eval(b)
-    cfg = T.default_settings(mcts_simulations=S, mcts_threads=threads, max_game_rounds=40)
-    tot = np.zeros(6, np.int64)
-    blob = recs.tobytes()
-    nrec = 0
-    for g in range(G):
-        half, q0, stride = _half_slot(g, G, base)
-        r6, ost, ord_, ofin, orec = T.orc_play_half_games(k[0], k[1], per_slot, half, q0, stride, cfg, ea, eb)
-        assert (st[g, :per_slot] == ost).all(), (g, st[g], ost)
-        assert (rd[g, :per_slot] == ord_).all(), g
-        assert (fin[g, :per_slot][:, FM] == ofin[:, FM]).all(), g
-        tot += np.array(r6)
-        for gi, game in enumerate(orec):
-            assert len(game) > 0 and game.tobytes() in blob, (g, gi)
-            nrec += len(game)
-    assert nrec == len(recs)
-    assert [res["count"], res["draw"], res["win"][0], res["win_and_started"][0], res["win"][1], res["win_and_started"][1]] == list(tot)
-    a.arena_set_opponent(None)
-    a.close(); b.close()
+    concurrent_two_net_arena(orc, threads, b_first, T.make_net_flat(1, seed=31, perturb_bn=True), T.make_net_flat(1, seed=32, perturb_bn=True))
 
 
 # ---- passes queued without a read-back (azr_arena_run, up to 256 leaf slots on the 16-bit towers) ---------------------------------

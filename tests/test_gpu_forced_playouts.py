@@ -24,7 +24,17 @@ def _bitwise(a, b):
 
 # ---- 1. the root rule, bit for bit -----------------------------------------------------------------------------------------------
 def test_root_rule_bit_for_bit(orc):
-    eng = setup_engine(32)
+    root_rule(orc, False)
+
+
+def test_sharp_root_rule_bit_for_bit(orc):
+    """the same on the sharp net of that seed: priors of exactly 0 (the threshold sqrt(k * noiseP * sumN) rests on the noise term alone),
+    denormal priors and values of +-1.  How often the forced pick differs from PUCT's is printed, not required."""
+    root_rule(orc, True)
+
+
+def root_rule(orc, sharp):
+    eng = setup_engine(32, sharp)
     valid = eng.valid_moves()
     r = np.random.default_rng(5).random((G, 43))
     eta = (r / r.sum(1, keepdims=True)).astype(f32)
@@ -45,7 +55,12 @@ def test_root_rule_bit_for_bit(orc):
     last = stepped(eng, eta, 32, check)
     assert (last[0].sum(1) == 32).all()
     print("passes where the forced pick is not PUCT's, per game:", differs)
-    assert (differs > 0).sum() >= G // 2, differs
+    assert sharp or (differs > 0).sum() >= G // 2, differs
+    if sharp:
+        prior = last[2]
+        zero = sum(int((prior[g][T.bits(valid[g])] == 0).any()) for g in range(G))
+        print("sharp roots: zero legal prior rows %d, rows with a zero prior on a legal move %d" % ((prior == 0).all(1).sum(), zero))
+        assert zero > 0   # the condition of the case: the threshold is taken at P == 0
     eng.close()
 
 

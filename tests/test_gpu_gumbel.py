@@ -13,7 +13,7 @@ import gumbel_ref as G
 import selfplay_retrace as SR
 import surprise_ref as S
 import value_mix_ref as V
-from gpu_common import pi_of, pkg
+from gpu_common import host_net, pi_of, pkg
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -24,10 +24,10 @@ ALL = (1 << 43) - 1
 
 
 # ---- 1. the debug kernels, bit for bit ---------------------------------------------------------------------------------------------
-def _engine(threads=1, sims=16):
+def _engine(threads=1, sims=16, sharp=False):
     P = pkg()
     eng = P.Engine(SLOTS, blocks=1, sims=sims, dtype=P.NET_F32, threads=threads)
-    eng.set_weights(T.make_net_flat(1, seed=23, perturb_bn=True))
+    eng.set_weights(host_net(sharp))
     return eng
 
 
@@ -120,28 +120,38 @@ def _stepped_search(eng, g, m, n):
     N0 = eng.root_stats()[0].copy()                                                # zeros for a root that is not in the tree
     claims = np.zeros(eng.G, np.int64)
     x, need, act = eng.mcts_leaves()
-    prev = eng.root_stats()
+    prev, roots = eng.root_stats(), eng.get_states()
+    in_tree = eng.node_stats(roots)[5]                                             # (a sharp net's prior row may be all zero: P.any() does not tell)
     while act:
         eng.mcts_apply(*eng.predict(x))
         x, need, act = eng.mcts_leaves()
         cur = eng.root_stats()
         for gi in range(eng.G):
             inflight, want = np.zeros(43, np.uint32), np.zeros(43, np.int64)
-            if prev[2][gi].any() and claims[gi] < n:                                # the root was in the tree: the launch before selected
+            if in_tree[gi] and claims[gi] < n:                                      # the root was in the tree: the launch before selected
                 for th in range(Tn):
                     mv, _ = G.select(prev[0][gi], N0[gi], inflight, prev[1][gi], prev[2][gi], g[gi], vhat[gi], int(valid[gi]),
                                      int(claims[gi]) + th, m, n, CV, CS)
                     inflight[mv] += 1; want[mv] += 1
                 claims[gi] += Tn
             assert ((cur[0][gi].astype(np.int64) - prev[0][gi]) == want).all(), (gi, claims[gi], cur[0][gi].astype(np.int64) - prev[0][gi], want)
-        prev = cur
+        prev, in_tree = cur, eng.node_stats(roots)[5]
     assert (claims == n).all(), claims
     return N0, vhat, prev
 
 
 @pytest.mark.parametrize("threads,m,n", [(1, 4, 16), (2, 4, 16), (2, 16, 32)])
 def test_a_host_stepped_search_follows_the_restatement_pass_by_pass(threads, m, n):
-    eng = _engine(threads, n)
+    host_stepped_search_follows_the_restatement(threads, m, n, False)
+
+
+def test_sharp_host_stepped_search_follows_the_restatement_pass_by_pass():
+    """the smallest shape on the sharp net of that seed: logits of zero priors at the FLT_MIN clamp, completed Q from values of +-1"""
+    host_stepped_search_follows_the_restatement(1, 4, 16, True)
+
+
+def host_stepped_search_follows_the_restatement(threads, m, n, sharp):
+    eng = _engine(threads, n, sharp)
     seeds = np.arange(4100, 4100 + SLOTS, dtype=np.uint32)
     eng.new_games(seeds)                                                           # setup phase: no descent ends in a finished game
     eng.set_gumbel(m, CV, CS)
@@ -154,7 +164,7 @@ def test_a_host_stepped_search_follows_the_restatement_pass_by_pass(threads, m, 
         assert eng.root_gumbel().tobytes() == g.tobytes()
         ns = N.astype(np.int64) - N0
         assert (ns.sum(1) == n).all() and ((ns > 0).sum(1) <= m).all()
-        if d == 0 and (threads, m, n) == (1, 4, 16):
+        if d == 0 and (threads, m, n) == (1, 4, 16) and not sharp:
             assert not N0.any() and all(sorted(r[r > 0].tolist()) == [2, 2, 6, 6] for r in ns), ns
         reused += int(N0.any(1).sum())
         pi, qhat = eng.gumbel_policy()

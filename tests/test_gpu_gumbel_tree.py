@@ -5,6 +5,7 @@ node_stats against root_stats, on unknown states and as a read-only call; every 
 host at every depth, down to the leaf the device handed out; device self-play against its host-stepped retrace (all five new tree
 steps); off is the engine that never called it, and toggling keeps the trees; slot independence; refusals.
 Engines of 8 games, one block, NET_F32, budgets of 16 and 32."""
+import ctypes as C
 import zlib
 
 import numpy as np
@@ -195,6 +196,26 @@ class _Replay:
 
 @pytest.mark.parametrize("threads,m,n", [(1, 4, 16), (2, 4, 16), (2, 16, 32)])
 def test_every_selection_of_a_host_stepped_search_is_the_restatement(threads, m, n):
+    every_selection_is_the_restatement(threads, m, n, _peaked)
+
+
+def _sharp(x):
+    """the oracle's sharp stub as the host's evaluator: priors of exactly 0 and 1, denormal priors, values of +-1"""
+    stub = T.stub_fn("orc_sharp_eval")
+    pi, v, vv = np.zeros((len(x), 43), f32), np.zeros(len(x), f32), C.c_float(0)
+    for r in range(len(x)):
+        stub(None, x[r].ctypes.data_as(T.u8p), pi[r].ctypes.data_as(T.f32p), C.byref(vv))
+        v[r] = vv.value
+    return pi, v
+
+
+def test_sharp_every_selection_of_a_host_stepped_search_is_the_restatement():
+    """the smallest shape with the leaves evaluated by orc_sharp_eval: the improved policy of rows whose priors are all zero (every
+    logit at the FLT_MIN clamp) and whose completed Q are +-1"""
+    every_selection_is_the_restatement(1, 4, 16, _sharp)
+
+
+def every_selection_is_the_restatement(threads, m, n, evaluate):
     eng, rul, plain = _engine(threads, n), _engine(threads, n), _engine(threads, n)
     for e in (eng, plain):
         e.new_games(SEEDS)                                                          # set-up phase
@@ -204,15 +225,15 @@ def test_every_selection_of_a_host_stepped_search_is_the_restatement(threads, m,
     for d in range(3):
         g, rng = _draws(eng, d), eng.get_rng()
         replay = _Replay(eng, rul, g, m, n)
-        leaves = _search(eng, g, replay, _peaked)
+        leaves = _search(eng, g, replay, evaluate)
         assert (replay.claims == n).all() and eng.get_rng().tobytes() == rng.tobytes()   # no dice were thrown: nothing random in a descent
         deep1, deep2 = deep1 + replay.deep1, deep2 + replay.deep2
         if d == 0:   # the same games from the same empty trees under PUCT below the root
-            differ = _search(plain, g, None, _peaked) != leaves
+            differ = _search(plain, g, None, evaluate) != leaves
         assert (eng.make_moves(eng.gumbel_pick()) == 0).all()
     print("largest prior met below the root in the last decision: %.3f" % replay.top)
     print("selections checked at depth >= 1: %d, at depth >= 2: %d; the first decision's leaves differ from PUCT's: %s" % (deep1, deep2, differ))
-    assert deep1 > 0 and deep2 > 0 and differ
+    assert deep1 > 0 and (evaluate is _sharp or (deep2 > 0 and differ))   # (on the sharp stub depth 2 and the difference are printed only)
     for e in (eng, rul, plain):
         e.close()
 

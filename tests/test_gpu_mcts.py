@@ -15,7 +15,7 @@ import pytest
 
 import azr_testlib as T
 import rules_settings as RS
-from gpu_common import pkg
+from gpu_common import pkg, search_decisions, selfplay_games
 
 pytestmark = pytest.mark.gpu
 FM = T.data_field_mask()
@@ -40,56 +40,6 @@ def test_search_off_the_defaults_bit_exact(orc, threads):
     roots = RS.search_roots(48)
     assert len(roots) == 48 and len(set(roots[:, 149])) == 4
     search_decisions(orc, "orc_hash_eval", 24, threads, roots, 4, **RS.FIVE)
-
-
-def search_decisions(orc, stub_name, sims, threads, states, decisions, **kw):
-    stub = getattr(orc, stub_name)
-    stub.argtypes = [C.c_void_p, T.u8p, T.f32p, C.c_void_p]
-    G = len(states)
-    cfg = T.default_settings(mcts_simulations=sims, mcts_threads=threads, **kw)
-    eng = pkg().Engine(G, blocks=1, sims=sims, dtype=pkg().NET_F32, threads=threads, **kw)
-    eng.set_states(states)
-    seeds = np.arange(500, 500 + G, dtype=np.uint32)
-    eng.set_rng(seeds)
-    S, R, M = [], [], []
-    for g in range(G):
-        s, r = T.OrcState(), T.OrcRng()
-        orc.orc_state_unpack(C.byref(s), T.ptr(states[g]))
-        r.x = int(seeds[g])
-        S.append(s); R.append(r); M.append(orc.orc_mcts_create(C.byref(cfg)))
-    evalfn = C.cast(stub, C.c_void_p)
-    d = np.zeros(160, np.uint8)
-    for step in range(decisions):
-        status = eng.status()
-        T.host_stub_search(eng, orc, stub)
-        n_gpu, q_gpu, p_gpu = eng.root_stats()
-        pi_gpu = eng.policy()
-        sample = step % 2 == 1
-        moves = eng.pick(sample=sample)
-        moves[status != -1] = 255
-        assert (eng.make_moves(moves) == 0).all()
-        after, rng_after = eng.get_states(), eng.get_rng()
-        n, q, p, pi = (np.zeros(43, np.uint32), np.zeros(43, np.float32), np.zeros(43, np.float32),
-                       np.zeros(43, np.float32))
-        for g in range(G):
-            if status[g] != -1:
-                continue
-            assert orc.orc_mcts_simulate(M[g], C.byref(S[g]), C.byref(R[g]), evalfn, None) == 0
-            orc.orc_mcts_root_stats(M[g], C.byref(S[g]), T.ptr(n), T.ptr(q), T.ptr(p), None)
-            assert (n == n_gpu[g]).all(), (step, g, n, n_gpu[g])
-            assert (q.view(np.uint32) == q_gpu[g].view(np.uint32)).all(), (step, g)
-            assert (p.view(np.uint32) == p_gpu[g].view(np.uint32)).all(), (step, g)
-            orc.orc_mcts_policy(M[g], C.byref(S[g]), T.ptr(pi))
-            assert (pi.view(np.uint32) == pi_gpu[g].view(np.uint32)).all(), (step, g)
-            mv = orc.orc_pick_random(T.ptr(pi), C.byref(R[g])) if sample else orc.orc_pick_highest(T.ptr(pi))
-            assert mv == moves[g], (step, g)
-            assert orc.orc_make_move(C.byref(S[g]), mv, C.byref(R[g]), C.byref(cfg)) == 0
-            orc.orc_state_pack(C.byref(S[g]), T.ptr(d))
-            assert (d == after[g]).all(), (step, g)
-            assert R[g].x == rng_after[g], (step, g)
-    for m in M:
-        orc.orc_mcts_destroy(m)
-    eng.close()
 
 
 def test_player_seam_extra_trim_empties_the_tree(orc):
@@ -126,48 +76,6 @@ def test_full_selfplay_games_off_the_defaults_vs_oracle(orc):
     """the same with every rule switch off its default, one search thread; without yield every game runs its 36 rounds, so two games
     (six take 13.6 s).  On an MI355X 5.8 s; the default test beside it takes 12 s."""
     selfplay_games(orc, 1, G=2, limit_attack=1, limit_reinforcement=0, min_unit_move=1, allow_yield=0, max_game_rounds=36)
-
-
-def selfplay_games(orc, threads, G=6, **kw):
-    sims, B = 6, 1
-    P = pkg()
-    eng = P.Engine(G, blocks=B, sims=sims, dtype=P.NET_F32, threads=threads, **kw)
-    flat = T.make_net_flat(B, seed=11, perturb_bn=True)
-    eng.set_weights(flat)
-    base = 4242
-    eng.selfplay_start(base)
-    recs = []
-    for _ in range(400):
-        eng.selfplay_run(64)
-        c = eng.counters()
-        if c["games_finished"] >= G:
-            break
-    c = eng.counters()
-    assert c["games_finished"] >= G and c["errors"] == 0 and c["nodes_dropped"] == 0
-    recs = eng.drain()
-    assert len(recs) == c["samples"]
-
-    @T.EVAL_FN
-    def hip_eval(ctx, in88, pi, v):
-        x = np.ctypeslib.as_array(in88, shape=(88,)).copy()[None]
-        p, vv = eng.predict(x)
-        C.memmove(pi, p.ctypes.data, 43 * 4)
-        v[0] = float(vv[0])
-
-    cfg = T.default_settings(mcts_simulations=sims, mcts_threads=threads, **kw)
-    # records of one game are contiguous in the ring; games finish in any order: match by content
-    want = {}
-    for g in range(G):
-        buf = np.zeros((4096, 265), np.uint8)
-        st, rounds = C.c_int(0), C.c_int(0)
-        n = orc.orc_selfplay_game(C.byref(cfg), base + g, hip_eval, None, T.ptr(buf), 4096, C.byref(st),
-                                  C.byref(rounds), None, 0, None, None)
-        assert n > 0
-        want[g] = buf[:n].copy()
-    blob = recs.tobytes()
-    for g in range(G):
-        assert want[g].tobytes() in blob, f"game {g} record stream not found in the device's output"
-    eng.close()
 
 
 def test_selfplay_from_midgame_states_vs_oracle(orc):

@@ -119,10 +119,19 @@ def test_equal_budgets_only_gate_the_records(orc, threads):
 # ---- 4. mixed budgets against the oracle ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("threads", [1, 2])
 def test_mixed_budgets_vs_oracle(threads):
+    mixed_budgets_vs_oracle(threads, 6, T.make_net_flat(1, seed=11, perturb_bn=True))
+
+
+def test_sharp_mixed_budgets_vs_oracle():
+    """the same on the sharp net of that seed (two games, two search threads): fast searches of 2 simulations on priors of exactly 0"""
+    mixed_budgets_vs_oracle(2, 2, T.make_sharp_net_flat(1, seed=11))
+
+
+def mixed_budgets_vs_oracle(threads, G, flat):
     P = pkg()
-    G, sims, fast = 6, 6, 2
+    sims, fast = 6, 2
     eng = P.Engine(G, blocks=1, sims=sims, dtype=P.NET_F32, max_game_rounds=36, threads=threads)
-    eng.set_weights(T.make_net_flat(1, seed=11, perturb_bn=True))
+    eng.set_weights(flat)
     eng.selfplay_set_playout_cap(0.5, fast, 99)
     recs, c = _selfplay(eng, G, quota=G)             # exactly the games of seeds BASE .. BASE + 5, each played to its end
     assert c["games_finished"] == G

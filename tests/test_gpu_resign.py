@@ -85,8 +85,8 @@ def test_a_run_saturates_on_the_device():
 
 
 # ---- 2. a resigned game is a prefix of the game without resignation ----------------------------------------------------------------
-def _run(threads, cap=False, psw=False, mix=False):
-    return SR.Run(BASE, QUOTA, threads, SIMS, surprise=(SHARE, MAXW, PSEED) if psw else None, value_mix=QSHARE if mix else None,
+def _run(threads, cap=False, psw=False, mix=False, net="base"):
+    return SR.Run(BASE, QUOTA, threads, SIMS, surprise=(SHARE, MAXW, PSEED) if psw else None, value_mix=QSHARE if mix else None, net=net,
                   **(dict(fast=FAST, cap=(0.5, CSEED)) if cap else {}))
 
 
@@ -196,6 +196,30 @@ def test_a_resigned_game_is_a_prefix_of_the_retraced_game(threads, streak, cap, 
         assert c["decisions"] == decisions and c["simulations"] == decisions * (SIMS - SIMS % threads), (c, decisions)
     else:
         assert c["decisions"] < tot["decisions"] and c["simulations"] < tot["simulations"]
+
+
+@pytest.mark.parametrize("threads", [1, 2])
+def test_sharp_net_resigns_on_saturated_values(threads):
+    """the same comparison on the sharp net (selfplay_retrace's Run.net), streak 1 and q_resign = -0.9: the root values that trigger it
+    are means of Q = -1 exactly, and a resigned game is still the prefix of the retraced one"""
+    run = _run(threads, net="sharp")
+    games, tot = SR.cached("retrace", run)
+    series = [_series(g) for g in games]
+    q_resign, streak = -0.9, 1
+    cuts = _cuts(series, q_resign, streak)
+    allq = np.concatenate([s[0] for s in series])
+    print("cut rows %s of %s rows, resigners %s; root values of exactly -1: %d, of exactly +1: %d" %
+          ([c[0] for c in cuts], [len(s[0]) for s in series], [c[1] for c in cuts], (allq == -1).sum(), (allq == 1).sum()))
+    resigned = sum(1 for row, _ in cuts if row >= 0)
+    assert resigned > 0 and (allq <= f32(q_resign)).any()                  # the condition of the case, on the retrace: somebody gives up
+    recs, c, stats = _play(run, q_resign, streak)
+    streams = [_expected(game, s, row, who, False, False, BASE + g) for g, (game, s, (row, who)) in enumerate(zip(games, series, cuts))]
+    assert_exactly_these_streams(recs, streams)
+    decisions = sum(len(s[0]) if row < 0 else row + 1 for s, (row, _) in zip(series, cuts))
+    assert len(recs) == sum(len(w) for w, _ in streams) == c["samples"] and c["games_finished"] == QUOTA
+    assert c["errors"] == 0 and c["nodes_dropped"] == 0 and c["records_dropped"] == 0
+    assert c["decisions"] == decisions and c["simulations"] == decisions * (SIMS - SIMS % threads), (c, decisions)
+    assert stats == dict(resigned=resigned, holdout_games=0, holdout_would_resign=0, holdout_not_lost=0), stats
 
 
 # ---- 3. the holdout ---------------------------------------------------------------------------------------------------------------

@@ -19,10 +19,9 @@ FULL = (1 << 43) - 1
 
 
 # ---- 1. the constant vector is today's search ------------------------------------------------------------------------------
-def _two_decisions(orc, threads, eta_value):
+def _two_decisions(orc, threads, eta_value, stub_name="orc_hash_eval"):
     """two consecutive decisions (the second search reuses the tree) of 8 new games; everything the search leaves behind"""
-    stub = orc.orc_hash_eval
-    stub.argtypes = [C.c_void_p, T.u8p, T.f32p, C.c_void_p]
+    stub = T.stub_fn(stub_name)
     P = pkg()
     G, sims = 8, 16
     eng = P.Engine(G, blocks=1, sims=sims, dtype=P.NET_F32, threads=threads)
@@ -47,17 +46,26 @@ def _two_decisions(orc, threads, eta_value):
 
 @pytest.mark.parametrize("threads", [1, 2])
 def test_constant_vector_is_the_constant_search_and_the_oracles(orc, threads):
+    constant_vector_is_the_oracles(orc, threads, "orc_hash_eval")
+
+
+@pytest.mark.parametrize("threads", [1, 2])
+def test_sharp_constant_vector_is_the_constant_search_and_the_oracles(orc, threads):
+    """the same on the sharp stub: the mix (1 - eps) * P + eps * eta[m] on priors of exactly 0 and on denormal ones"""
+    constant_vector_is_the_oracles(orc, threads, "orc_sharp_eval")
+
+
+def constant_vector_is_the_oracles(orc, threads, stub_name):
     P = pkg()
     s = P.Settings()
     P.load_library().azr_default_settings(C.byref(s))
-    a = _two_decisions(orc, threads, f32(s.dir_noise_value))
-    b = _two_decisions(orc, threads, None)
+    a = _two_decisions(orc, threads, f32(s.dir_noise_value), stub_name)
+    b = _two_decisions(orc, threads, None, stub_name)
     for step in range(2):
         for key in a[step]:
             assert a[step][key].tobytes() == b[step][key].tobytes(), (step, key)
     # ... and both are the oracle's search (the harness of test_gpu_mcts.py)
-    stub = orc.orc_hash_eval
-    evalfn = C.cast(stub, C.c_void_p)
+    evalfn = C.cast(T.stub_fn(stub_name), C.c_void_p)
     cfg = T.default_settings(mcts_simulations=16, mcts_threads=threads)
     d = np.zeros(160, np.uint8)
     for g in range(8):
@@ -103,7 +111,16 @@ def puct_pick(orc, N, Q, Pr, valid, eta, eps, hp):
 
 
 def test_root_formula_bit_for_bit_random_vector(orc):
-    eng = setup_engine(24)
+    root_formula_random_vector(orc, False)
+
+
+def test_sharp_root_formula_bit_for_bit_random_vector(orc):
+    """the same on the sharp net of that seed: a random vector mixed into priors of exactly 0 and into denormal ones"""
+    root_formula_random_vector(orc, True)
+
+
+def root_formula_random_vector(orc, sharp):
+    eng = setup_engine(24, sharp)
     valid = eng.valid_moves()
     r = np.random.default_rng(5).random((8, 43))
     eta = (r / r.sum(1, keepdims=True)).astype(f32)

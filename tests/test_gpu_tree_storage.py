@@ -83,6 +83,39 @@ def test_colliding_table(orc, monkeypatch, name, sims, threads, capacity):
         assert run["dropped"] > 0 and run["evictions"] > 0
 
 
+# ---- the same pools on the sharp stub (orc_sharp_eval): one-hot priors and values of +-1 dig one line deep instead of spreading ----------
+SHARP = "orc_sharp_eval"
+
+
+@pytest.mark.parametrize("sims,threads", SHAPES)
+def test_sharp_pool_that_fits_exactly(orc, sims, threads):
+    run = T.orc_tree_run(sims, threads, stub=SHARP)
+    assert 8 < run["peak"] < 16 * (sims + 1)
+    c = run_engine(run, node_capacity=run["peak"])
+    assert c["nodes_dropped"] == 0
+
+
+@pytest.mark.parametrize("capacity", [8, 16])
+@pytest.mark.parametrize("sims,threads", SHAPES)
+def test_sharp_short_pool(orc, sims, threads, capacity):
+    """the path stack is min(C, 1024) = 8 or 16 deep and the sharp stub's lines are the deepest the suite searches: AZR_E_CAPACITY
+    where the oracle plays on would show as an error"""
+    run = T.orc_tree_run(sims, threads, limit=capacity, stub=SHARP)
+    assert run["dropped"] > 0 and run["evictions"] > 0
+    c = run_engine(run, node_capacity=capacity)
+    assert c["nodes_dropped"] == run["dropped"]
+
+
+@pytest.mark.parametrize("capacity", [0, 16], ids=["default_pool", "pool16"])
+@pytest.mark.parametrize("name", ["one_chain_equal_tags", "wrapping_chains"])
+def test_sharp_colliding_table(orc, monkeypatch, name, capacity):
+    run = T.orc_tree_run(25, 2, limit=capacity, stride=2, stub=SHARP)
+    c = run_engine(run, monkeypatch, HASHES[name], node_capacity=capacity)
+    assert c["nodes_dropped"] == run["dropped"]
+    if capacity:
+        assert run["dropped"] > 0 and run["evictions"] > 0
+
+
 def test_selfplay_and_arena_on_the_one_chain_table(monkeypatch):
     """device self-play (24 games on 16 slots: the game turnover) and the two-net concurrent-mirror arena (tree 2, the two trims in a
     row at a turn's first decision) with every key in one chain of equal tags: records in canonical order and arena results are the
